@@ -27,12 +27,6 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# The step uses two HIP streams (crop2seg_amd/engine.py: weight gradients next to the data-gradient chain).  RCCL
-# creates streams of its own; with the runtime's default of 4 hardware queues the side stream then shares a queue with
-# the main stream and the overlap turns into a 0.6 ms loss per step (measured with a world-size-1 process group).
-# Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import torch  # noqa: E402
 
 PEAK_F32_TFLOPS = 157.3      # MI355X dense fp32 MFMA/vector peak (MI355X_MICROARCH.md, chip-level parameters)
@@ -112,6 +106,25 @@ def cpu_baseline(B, T, H, W, threads):
             "configs0_sample": f"BASELINE.json configs[0]: U-TAE B=2 T=16 128x128, 1 warm-up + 3 timed steps, {dt_c1:.2f} s/step"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write what the timed path returned in its last step as DIR/<name>.npy (float32).  If the arrays together exceed
+    DUMP_LIMIT_BYTES, each is replaced by the same share of its flattened elements, chosen by a fixed seed (identical
+    indices from run to run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, 0.95 * DUMP_LIMIT_BYTES / total)     # 5 % left for the .npy headers
+    for name, a in arrays.items():
+        if share < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(1, int(a.size * share)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -133,7 +146,12 @@ def main():
                     help="replay the step as a captured hipGraph (single-stream) instead of launching eagerly; eager is the "
                          "default because the weight gradients then overlap the data-gradient chain on a side stream")
     ap.add_argument("--no-graph", action="store_true", help="(default; kept for older command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss, logits, updated parameters and gradients "
+                         "(rank 0) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # stdout carries exactly one line (the JSON): anything libraries write to file descriptor 1 while the bench runs --
     # RCCL prints a five-line version banner there when its communicator is created -- goes to stderr instead
     sys.stdout.flush()
@@ -191,12 +209,16 @@ def main():
     E.PROFILE = {"match": dict(KH=3, S=1, C0=64, C1=0, Cout=64, Hin=H, N=B * T, reflect_adjoint=0), "events": [], "ltae_events": []} if not use_graph else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = run()
+        loss, logits = run()
     t_issue = time.perf_counter() - t0                     # host time to issue the launches (eager mode: must stay < dt)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: in graph mode the roofline steps below would move the parameters on
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "logits": logits, "params": step.flat_param,
+                                         "grads": step.flat_grad})
     prof = E.PROFILE
     E.PROFILE = None
     if use_graph:

@@ -46,21 +46,31 @@ class FlatDataParallel:
 
     def reduce_async(self, bucket: torch.Tensor, after=()):
         """Start the sum of `bucket` (a view of the flat gradient buffer) over ranks while the caller keeps launching the rest
-        of the backward pass.  On HIP tensors the collective is issued from a communication stream that first waits for the
-        caller's current stream and for every stream in `after` (the weight-gradient side stream), so it starts as soon as the
-        bucket's producers have finished and runs next to the encoder's backward pass.  Returns a handle whose wait() orders
-        the caller's current stream (HIP) or the host (gloo) behind the collective; None when no collective is needed."""
+        of the backward pass.  On HIP tensors the collective is enqueued on the first stream of `after` (the weight-gradient
+        side stream) -- or on a communication stream when `after` is empty -- once that stream has waited for the caller's
+        current stream and the other streams of `after`, so it starts as soon as the bucket's producers have finished and runs
+        next to the encoder's backward pass.  It is issued as a blocking collective, which the process group enqueues on that
+        same stream: an asynchronous one would run on the group's internal stream behind a wait for the side stream, and with
+        the runtime's default number of hardware queues that stream can share a queue with the caller's, stalling the
+        backward pass until the side stream catches up.  Returns a handle whose wait() orders the caller's current stream (HIP)
+        or the host (gloo) behind the collective; None when no collective is needed."""
         if not self.active:
             return None
         if bucket.is_cuda:
-            comm = getattr(self, "_comm", None)
-            if comm is None:
-                comm = self._comm = torch.cuda.Stream(device=bucket.device)
-            comm.wait_stream(torch.cuda.current_stream(bucket.device))
-            for st in after:
-                comm.wait_stream(st)
-            with torch.cuda.stream(comm):
-                return dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+            if after:
+                stream = after[0]
+            else:
+                stream = getattr(self, "_comm", None)
+                if stream is None:
+                    stream = self._comm = torch.cuda.Stream(device=bucket.device)
+            stream.wait_stream(torch.cuda.current_stream(bucket.device))
+            for st in after[1:]:
+                stream.wait_stream(st)
+            with torch.cuda.stream(stream):
+                dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group)
+                done = torch.cuda.Event()
+                done.record(stream)
+            return _StreamWork(done)
         return dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     def reduce_gradients(self, flat_grad: torch.Tensor) -> float:
@@ -69,3 +79,13 @@ class FlatDataParallel:
         if self.active and flat_grad.numel() > 0:     # (C2S_BENCH_FORCE_DIST rehearses the launch on one GPU)
             dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group)
         return 1.0 / self.world
+
+
+class _StreamWork:
+    """Handle of a collective enqueued on a HIP stream: wait() orders the caller's current stream behind it."""
+
+    def __init__(self, event: "torch.cuda.Event"):
+        self.event = event
+
+    def wait(self) -> None:
+        torch.cuda.current_stream().wait_event(self.event)

@@ -20,40 +20,93 @@ def _abs_only(name, training):
     return name in ("temporal_encoder.mlp.0.bias", "temporal_encoder.inconv.bias", "temporal_encoder.in_norm.bias")
 
 
-@pytest.mark.parametrize("name", golden_names())
-def test_oracle_matches_reference_forward(goldens, name):
-    g = goldens(name)
+def _forward(g, dtype):
+    """Oracle forward of fixture `g` in `dtype`: logits, attention, loss, boundary logits (or None), BatchNorm updates."""
     bn = O.BNState()
+    kw = g.dropout_kwargs()
+    if g.cfg.model == "wtae":
+        kw.pop("mlp_keep", None)
+    sd, x = g.sd, g.x
+    if dtype != torch.float32:
+        sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+        x, kw = x.to(dtype), {k: v.to(dtype) for k, v in kw.items()}
     with torch.no_grad():
-        kw = g.dropout_kwargs()
-        if g.cfg.model == "wtae":
-            kw.pop("mlp_keep", None)
-        logits, att = O.forward(g.sd, g.x, g.dates, g.cfg, training=g.training, bn=bn, **kw)
+        logits, att = O.forward(sd, x, g.dates, g.cfg, training=g.training, bn=bn, **kw)
         loss = O.cross_entropy(logits, g.y, g.cfg.out_conv[-1])
+        out_b = None
         if g.cfg.add_boundary_loss:          # second head + focal term (utae.py:236-238; src/learning/utils.py:283-285,318-324)
             from oracle import tail_oracle as TO
             out_b = O.LAST_BOUNDARY[0]
-            ref_b = torch.from_numpy(g.z["logits_b"])
-            assert (out_b - ref_b).abs().max() <= 2e-5 * ref_b.abs().max()
             loss = loss + TO.focal_ce(out_b, TO.boundary_target(g.y, 15), 2.0)
+    return logits, att, loss, out_b, bn.updates
+
+
+class _Anchor:
+    """The bounds below were set against the fp32 summation order of the CPU libraries (oneDNN, MKL) the goldens were written
+    with; another host's vector ISA or thread count rounds differently, by more than the tightest bounds (measured: attention
+    up to 12x its 2e-6 bound, logits up to 3x, with the oracle itself unchanged).  Each check therefore first applies its bound
+    to the fp32 oracle; only if that fails does it require the reference's fp32 output to lie within 5 x this host's own fp32
+    rounding of the fp64 oracle (measured <= 4.5x over 1 thread, AVX2-only and scalar builds) -- the fp64-anchored protocol of
+    the backward test.  A wrong oracle is off by O(1) under either form."""
+
+    FACTOR = 5.0
+
+    def __init__(self, g):
+        self.g, self._r64 = g, None
+
+    def r64(self):
+        if self._r64 is None:
+            self._r64 = _forward(self.g, torch.float64)
+        return self._r64
+
+    def close(self, got, ref, bound, got64):
+        got, ref = got.double(), ref.double()
+        if float((got - ref).abs().max()) <= bound:
+            return True
+        got64 = got64().double()                 # evaluated only where the host's fp32 rounding differs
+        rounding = float((got - got64).abs().max())
+        return float((got64 - ref).abs().max()) <= self.FACTOR * rounding
+
+    def same_argmax(self, logits, ref_logits):
+        """Class maps equal; failing that, every differing pixel is one where the fp64 oracle's top-2 margin lies within the
+        fp32 rounding band (a tie that the summation order decides)."""
+        a, b = logits.argmax(1), ref_logits.argmax(1)
+        if torch.equal(a, b):
+            return True
+        l64 = self.r64()[0]
+        band = self.FACTOR * float((logits.double() - l64).abs().max())
+        top2 = l64.topk(2, dim=1).values
+        margin = (top2[:, 0] - top2[:, 1])[a != b]
+        return bool((margin <= band).all()) and torch.equal(l64.argmax(1)[a == b], b[a == b])
+
+
+@pytest.mark.parametrize("name", golden_names())
+def test_oracle_matches_reference_forward(goldens, name):
+    g = goldens(name)
+    logits, att, loss, out_b, bn_updates = _forward(g, torch.float32)
+    A = _Anchor(g)
+    if out_b is not None:
+        ref_b = torch.from_numpy(g.z["logits_b"])
+        assert A.close(out_b, ref_b, 2e-5 * float(ref_b.abs().max()), lambda: A.r64()[3])
     ref_logits = torch.from_numpy(g.z["logits"])
     ref_att = torch.from_numpy(g.z["att"])
     scale = ref_logits.abs().max()
     # train mode under weight_init-style BN gains is ill-conditioned: the fp32 reference differs from
     # ITSELF by 1e-4 between 1 and 8 CPU threads (SURVEY.md 8c, BASELINE.md section 2)
     tol = 5e-4 if (g.training and g.meta["flavour"] == "wi") else 2e-5
-    assert (logits - ref_logits).abs().max() <= tol * scale, (logits - ref_logits).abs().max() / scale
-    assert (att - ref_att).abs().max() <= 2e-6
-    assert abs(float(loss) - float(g.z["loss"])) <= 1e-5 * abs(float(g.z["loss"]))
+    assert A.close(logits, ref_logits, tol * float(scale), lambda: A.r64()[0]), (logits - ref_logits).abs().max() / scale
+    assert A.close(att, ref_att, 2e-6, lambda: A.r64()[1]), (att - ref_att).abs().max()
+    ref_loss = torch.tensor(float(g.z["loss"]))
+    assert A.close(loss.reshape(()), ref_loss, 1e-5 * abs(float(ref_loss)), lambda: A.r64()[2].reshape(())), (float(loss), float(ref_loss))
     if not g.training:
         # argmax class map bit-exact (ties -> lowest index, like torch.argmax)
-        assert torch.equal(logits.argmax(1), ref_logits.argmax(1))
+        assert A.same_argmax(logits, ref_logits)
     else:
         for k in g.z.files:
             if k.startswith("bn/") and not g.dummy_pass_pollutes(k[3:]):
                 ref = torch.from_numpy(g.z[k])
-                got = bn.updates[k[3:]]
-                assert (got - ref).abs().max() <= 1e-5 * max(1.0, float(ref.abs().max())), k
+                got = bn_updates[k[3:]]
+                assert A.close(got, ref, 1e-5 * max(1.0, float(ref.abs().max())), lambda: A.r64()[4][k[3:]]), k
 
 
 @pytest.mark.parametrize("name", golden_names())
