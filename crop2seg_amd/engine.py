@@ -69,6 +69,7 @@ class Workspace:
         self.pack_record: Dict[Tuple, Tuple] = {}
         self.pack_plan: Optional[dict] = None
         self.reduce_jobs: List[Tuple] = []          # slice sums of the weight gradients recorded during this backward pass
+        self.reduce_post: List[Tuple] = []          # accumulating slice sums (their slab tensors held): launched after the batch
         self.reduce_plan: Optional[dict] = None     # their one-launch table (built once, reused while the jobs stay the same)
 
     def finalize_pack_plan(self) -> None:
@@ -94,10 +95,18 @@ class Workspace:
     def run_reduce_batch(self) -> None:
         """Sum the split-K slabs of every weight gradient recorded during this backward pass in one launch
         (c2s_wgrad_reduce_batch).  The job table is built on the host the first time (and again if a job changed) -- outside
-        hipGraph capture; under capture a matching table must exist, otherwise the sums are launched one by one."""
+        hipGraph capture; under capture a matching table must exist, otherwise the sums are launched one by one.
+        The accumulating sums (a weight written a second time in the tape) follow, in recording order: the batch holds the
+        first, overwriting sum of the same weight, so an accumulating sum launched before it would be lost."""
         jobs, self.reduce_jobs = self.reduce_jobs, []
-        if not jobs:
-            return
+        post, self.reduce_post = self.reduce_post, []
+        if jobs:
+            self._reduce_batch(jobs, {j[0].data_ptr() for j in post})
+        for (slabs, dst_ptr, so, sc, taps, d) in post:
+            check(lib().c2s_wgrad_reduce(C.byref(d), slabs.data_ptr(), dst_ptr, so, sc, _tap_array(taps), 1, _stream()),
+                  "wgrad_reduce")
+
+    def _reduce_batch(self, jobs: List[Tuple], post_slabs: set) -> None:
         L_ = lib()
         key = tuple(j[:-1] for j in jobs)
         plan = self.reduce_plan
@@ -119,7 +128,7 @@ class Workspace:
             plan = self.reduce_plan = {"key": key, "table": table.to(self.device), "njobs": len(jobs), "blocks": block}
             # one slab buffer per weight lives as long as the plan (nslices * taps * CinP * CoutB floats each, ~70 MB for a U-TAE
             # step): buffers of an older plan (re-allocated gradient tensors) are dropped here
-            live = {j[1] for j in jobs}
+            live = {j[1] for j in jobs} | post_slabs
             for name in [k for k, b in self.bufs.items() if k.startswith("wgrad_slabs:") and b.data_ptr() not in live]:
                 del self.bufs[name]
         check(L_.c2s_wgrad_reduce_batch(plan["table"].data_ptr(), plan["njobs"], plan["blocks"], _stream()), "wgrad_reduce_batch")
@@ -489,13 +498,18 @@ def _wgrad_launch(ctx: Ctx, srcs: Sequence[Tensor], gout: Tensor, Cout: int, Hou
     d = WgradDesc(N, C0, C1, Hin, Win, Cout, Hout, Wout, K, K, S, pad, pad, pad_mode,
                   _wgrad_slices(ctx, N, Hout, Wout, S, C0 + C1, Cout))
     nfl = lib().c2s_wgrad_workspace_floats(C.byref(d))
-    batched = REDUCE_BATCH and ctx.tape is not None and not accumulate
-    # batched slice sums: one slab buffer per weight (they all live until the end of the backward pass)
-    slabs = ctx.ws.get(f"wgrad_slabs:{dst.data_ptr()}:{so}:{taps[0]}" if batched else "wgrad_slabs", nfl)
+    batched = REDUCE_BATCH and ctx.tape is not None
+    # batched slice sums: one slab buffer per weight and write (they all live until the end of the backward pass); an
+    # accumulating sum is ordered after the batch, which holds the first write of the same weight
+    tag = f":acc{len(ctx.ws.reduce_post)}" if accumulate else ""
+    slabs = ctx.ws.get(f"wgrad_slabs:{dst.data_ptr()}:{so}:{taps[0]}{tag}" if batched else "wgrad_slabs", nfl)
     check(lib().c2s_conv_wgrad(C.byref(d), s0.data_ptr(), _ptr(s1), gout.data_ptr(), slabs.data_ptr(), slabs.numel(),
                                _ptr(valid), _stream()), "conv_wgrad")
     if batched:
-        ctx.ws.reduce_jobs.append((bytes(d), slabs.data_ptr(), dst.data_ptr(), so, sc, tuple(taps), accumulate, d))
+        if accumulate:
+            ctx.ws.reduce_post.append((slabs, dst.data_ptr(), so, sc, tuple(taps), d))
+        else:
+            ctx.ws.reduce_jobs.append((bytes(d), slabs.data_ptr(), dst.data_ptr(), so, sc, tuple(taps), accumulate, d))
         ctx.tape.finalizers[id(ctx.ws)] = ctx.ws.run_reduce_batch
     else:
         check(lib().c2s_wgrad_reduce(C.byref(d), slabs.data_ptr(), dst.data_ptr(), so, sc, _tap_array(taps), accumulate,
