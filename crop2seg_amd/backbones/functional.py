@@ -165,8 +165,8 @@ def up_conv_block(ctx, x, skip, prefix, spec):
     sk = E.conv2d(ctx, [skip], prefix + ".skip_conv.0.weight", prefix + ".skip_conv.0.bias", 1, 1, 0, _lib.PAD_ZEROS, None)
     sk = E.norm_act(ctx, sk, prefix + ".skip_conv.1", _lib.NORM_BATCH, 1, True, None, None,
                     conv_bias=prefix + ".skip_conv.0.bias")
-    assert spec.str_conv_k == 4 and spec.str_conv_s == 2 and spec.str_conv_p == 1, "only k=4,s=2,p=1 up-convs are built"
-    up = E.conv_transpose2d(ctx, x, prefix + ".up.0.weight", prefix + ".up.0.bias")
+    assert spec.str_conv_s == 2, "only stride-2 up-convs are built"
+    up = E.conv_transpose2d(ctx, x, prefix + ".up.0.weight", prefix + ".up.0.bias", spec.str_conv_k, spec.str_conv_p)
     up = E.norm_act(ctx, up, prefix + ".up.1", _lib.NORM_BATCH, 1, True, None, None, conv_bias=prefix + ".up.0.bias")
     if spec.use_mbconv:             # MBUpConvBlock (mbconv.py:201-250): conv1 -> conv2 (norm 'batch'), no outer residual
         o1 = mbconv_layer(ctx, [up, sk], prefix + ".conv1", 1, "batch", spec, None)

@@ -444,6 +444,11 @@ class _Backbone(nn.Module):
         return lead if boundary is not None else head
 
 
+# (str_conv_k, str_conv_s, str_conv_p) of the down / up convolutions: the default and the stride-2 geometries whose transposed
+# convolution exactly doubles the plane (k = 2p + 2) with 1x1 / 3x3 parity sub-kernels
+STR_CONV_GEOMETRIES = ((4, 2, 1), (2, 2, 0), (6, 2, 2))
+
+
 def _common_init(self, model, input_dim, encoder_widths, decoder_widths, out_conv, str_conv_k, str_conv_s, str_conv_p,
                  agg_mode, encoder_norm, n_head, d_model, d_k, encoder, return_maps, pad_value, padding_mode, conv_type,
                  use_mbconv, add_squeeze_excit, use_abs_rel_enc, num_queries, use_doy, add_linear, add_boundary_loss):
@@ -460,10 +465,11 @@ def _common_init(self, model, input_dim, encoder_widths, decoder_widths, out_con
         raise NotImplementedError(
             f"crop2seg_amd: the L-TAE kernels are built for n_head=16, d_model=256, d_k=4 (the reference's defaults, train.py:40-43); "
             f"got n_head={n_head}, d_model={d_model}, d_k={d_k}")
-    if (str_conv_k, str_conv_s, str_conv_p) != (4, 2, 1):
+    if (str_conv_k, str_conv_s, str_conv_p) not in STR_CONV_GEOMETRIES:
         raise NotImplementedError(
             f"crop2seg_amd: the strided / transposed convolutions are built for str_conv_k=4, str_conv_s=2, str_conv_p=1 (the "
-            f"reference's defaults, train.py:35-37); got k={str_conv_k}, s={str_conv_s}, p={str_conv_p}")
+            f"reference's defaults, train.py:35-37) and for (str_conv_k, str_conv_s, str_conv_p) in {{(2, 2, 0), (6, 2, 2)}}; "
+            f"got k={str_conv_k}, s={str_conv_s}, p={str_conv_p}")
     c_ltae = encoder_widths[0] if model == "timeunet" else encoder_widths[-1]
     if c_ltae % 64 != 0 or c_ltae > 256:
         raise NotImplementedError(

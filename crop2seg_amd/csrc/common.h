@@ -52,6 +52,9 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// taps of the largest packed kernel (the 6x6 stride-2 convolutions): tap tables of the weight packs and slice sums
+constexpr int C2S_MAX_TAPS = 36;
+
 __device__ __forceinline__ int reflect_idx(int i, int n) {
     // single reflection (pad < n): -1 -> 1, n -> n-2
     i = i < 0 ? -i : i;

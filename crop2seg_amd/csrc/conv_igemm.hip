@@ -28,9 +28,11 @@ struct ConvParams {
     int pad_y, pad_x, pad_mode, osy, osx, ooy, oox, accumulate;
     int log2fc, tiles_x;
     // reflect adjoint (data gradient of a reflect-padded convolution).  Per dimension the fold of the halo gradient
-    // is:  operand(pos == lo, tap K-1) += input[tap position - (K-1)]   and
-    //      operand(pos == hi, tap 0)   += input[tap position + (K-1)]      (-1 = rule absent)
+    // is:  operand(pos == lo, tap K-1) += input[tap position - d_lo]   and
+    //      operand(pos == hi, tap 0)   += input[tap position + d_hi]      (-1 = rule absent; d = K-1 except in the
+    //      parity sub-kernels of the 6x6 stride-2 data gradient, where the mirrored row is one or two rows away)
     int adj, ay_lo, ay_hi, ax_lo, ax_hi;
+    int dy_lo, dy_hi, dx_lo, dx_hi;
 };
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -44,7 +46,7 @@ constexpr int max_plane(int K, int S) {
 template <int K, int S>
 struct Cfg {
     // channels per LDS chunk: enough MFMA k-steps per barrier pair (>= 16) without growing the prefetch registers
-    static constexpr int CK = K == 1 ? 16 : (K == 2 ? 8 : (K == 4 ? 2 : 4));
+    static constexpr int CK = K == 1 ? 16 : (K == 2 ? 8 : (K >= 4 ? 2 : 4));
     static constexpr int NT = K * K;
     static constexpr int MAXE = (CK * max_plane(K, S) + 255) / 256;
 };
@@ -212,20 +214,20 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
             const int ad = boff[q] + 2 * cp * plane + ky * cols + kx;
             float v = Xl[ad];
             if constexpr (ADJ) {
-                // fold of the reflected halo: fixed offsets +-(K-1), always inside the staged tile
-                constexpr int D = K - 1;
+                // fold of the reflected halo: offsets of at most K-1, always inside the staged tile
                 const bool xl = kx == K - 1, xh = kx == 0, yl = ky == K - 1, yh = ky == 0;
+                const int dx = xl ? -p.dx_lo : p.dx_hi;
                 if (xl || xh) {                      // branch-free (0 / 1 lane masks): see conv_xpair.hip
                     const float mx = xl ? mxlo[q] : mxhi[q];
-                    v = fmaf(mx, Xl[ad + (xl ? -D : D)], v);
+                    v = fmaf(mx, Xl[ad + dx], v);
                 }
                 if (yl || yh) {
                     const float my = yl ? mylo[q] : myhi[q];
-                    const int dy = (yl ? -D : D) * cols;
+                    const int dy = (yl ? -p.dy_lo : p.dy_hi) * cols;
                     v = fmaf(my, Xl[ad + dy], v);
                     if (xl || xh) {
                         const float mx = xl ? mxlo[q] : mxhi[q];
-                        v = fmaf(my * mx, Xl[ad + dy + (xl ? -D : D)], v);
+                        v = fmaf(my * mx, Xl[ad + dy + dx], v);
                     }
                 }
             }
@@ -309,7 +311,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
 }
 
 struct TapTable {
-    int off[16];
+    int off[C2S_MAX_TAPS];
 };
 
 __global__ void pack_weights_kernel(const float* __restrict__ src, float* __restrict__ wpk, int cin, int cout,
@@ -340,7 +342,7 @@ void init_hook() {
 #define C2S_RAISE4(K_, S_)                               \
     C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, false>)); \
     C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 2, false>));
-    C2S_RAISE4(3, 1) C2S_RAISE4(1, 1) C2S_RAISE4(2, 1) C2S_RAISE4(4, 2)
+    C2S_RAISE4(3, 1) C2S_RAISE4(1, 1) C2S_RAISE4(2, 1) C2S_RAISE4(4, 2) C2S_RAISE4(2, 2) C2S_RAISE4(6, 2)
 #undef C2S_RAISE4
     C2S_RAISE_LDS((conv_igemm_kernel<3, 1, 1, true>));
     C2S_RAISE_LDS((conv_igemm_kernel<3, 1, 2, true>));
@@ -354,9 +356,9 @@ C2sInitRegistrar registrar(init_hook);
 extern "C" int c2s_pack_weights(const float* src, float* wpk, int cin, int cout, int coutP, int ntaps, long stride_o,
                                 long stride_c, const int* host_tap_off, void* stream) {
     C2S_REQUIRE(src && wpk && host_tap_off, "pack_weights: null pointer");
-    C2S_REQUIRE(ntaps >= 1 && ntaps <= 16 && coutP % 32 == 0 && coutP >= cout, "pack_weights: bad sizes");
+    C2S_REQUIRE(ntaps >= 1 && ntaps <= C2S_MAX_TAPS && coutP % 32 == 0 && coutP >= cout, "pack_weights: bad sizes");
     TapTable tt;
-    for (int i = 0; i < 16; ++i) tt.off[i] = i < ntaps ? host_tap_off[i] : 0;
+    for (int i = 0; i < C2S_MAX_TAPS; ++i) tt.off[i] = i < ntaps ? host_tap_off[i] : 0;
     const long total = (long)ntaps * cin * coutP;
     const int blocks = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
     hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, wpk, cin, cout,
@@ -387,7 +389,21 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
     p.osy = d->osy; p.osx = d->osx; p.ooy = d->ooy; p.oox = d->oox; p.accumulate = d->accumulate;
     p.adj = d->reflect_adjoint;
     p.ay_lo = p.ay_hi = p.ax_lo = p.ax_hi = -1;
-    if (d->reflect_adjoint) {
+    p.dy_lo = p.dy_hi = p.dx_lo = p.dx_hi = d->KH - 1;
+    if (d->reflect_adjoint == 2) {
+        // parity sub-kernel (3x3, pad 1, output rows 2*a + parity) of the dgrad of conv6x6s2(reflect pad 2); per dimension
+        // the input gradient of padded rows -1 / -2 / H / H+1 is the sub-kernel evaluated one row beyond either end:
+        //   parity 0: position 1 / tap 2 additionally reads input tap position - 2, position Ho-1 / tap 0 reads + 1
+        //   parity 1: position 0 / tap 2 reads tap position - 1,                  position Ho-2 / tap 0 reads + 2
+        C2S_REQUIRE(d->pad_mode == C2S_PAD_ZEROS && d->S == 1 && d->KH == 3 && d->pad_y == 1 && d->pad_x == 1 &&
+                    d->osy == 2 && d->osx == 2 && d->ooy >= 0 && d->ooy <= 1 && d->oox >= 0 && d->oox <= 1 &&
+                    d->Hin == d->Hout && d->Win == d->Wout && d->Hin >= 2 && d->Win >= 2,
+                    "conv_igemm: reflect_adjoint 2 applies to the parity launches of the 6x6 stride-2 data gradient");
+        p.ay_lo = d->ooy == 0 ? 1 : 0;   p.dy_lo = d->ooy == 0 ? 2 : 1;
+        p.ay_hi = d->Hout - 1 - d->ooy;  p.dy_hi = d->ooy == 0 ? 1 : 2;
+        p.ax_lo = d->oox == 0 ? 1 : 0;   p.dx_lo = d->oox == 0 ? 2 : 1;
+        p.ax_hi = d->Wout - 1 - d->oox;  p.dx_hi = d->oox == 0 ? 1 : 2;
+    } else if (d->reflect_adjoint) {
         C2S_REQUIRE(d->pad_mode == C2S_PAD_ZEROS && d->S == 1 && (d->KH == 3 || d->KH == 2),
                     "conv_igemm: reflect_adjoint applies to the zero-padded 3x3 / 2x2-parity data-gradient launches");
         C2S_REQUIRE(d->Hin >= 2 && d->Win >= 2 && d->Hin != 3 && d->Win != 3, "conv_igemm: reflect_adjoint needs planes of 2 or >= 4");
@@ -424,6 +440,8 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
     C2S_DISPATCH(2, 1, false)
     C2S_DISPATCH(2, 1, true)
     C2S_DISPATCH(4, 2, false)
+    C2S_DISPATCH(2, 2, false)
+    C2S_DISPATCH(6, 2, false)
 #undef C2S_DISPATCH
     c2s_set_error("conv_igemm: unsupported (K=%d,S=%d)", d->KH, d->S);
     return C2S_EINVAL;

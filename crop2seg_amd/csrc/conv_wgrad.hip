@@ -36,7 +36,11 @@ template <int K, int S>
 struct WCfg {
     static constexpr int TP = (S == 2) ? 64 : 128;     // positions per tile
     static constexpr int NT = K * K;
-    static constexpr int TH = (NT + 1) / 2;            // taps per wave half
+    // tap groups: a 6x6 kernel's 36 taps would need 18 accumulators of 16 VGPRs per wave; three workgroups per
+    // (slice, cin block, cout block) take 12 taps each (the input tile is staged once per group)
+    static constexpr int TG = NT > 16 ? 3 : 1;
+    static constexpr int NTG = NT / TG;                // taps per group
+    static constexpr int TH = (NTG + 1) / 2;           // taps per wave half
     static constexpr int plane_for(int l2) { return (((TP >> l2) - 1) * S + K) * (((1 << l2) - 1) * S + K); }
     static constexpr int MAXPLANE = wg_cmax(wg_cmax(plane_for(2), plane_for(3)), wg_cmax(plane_for(4), plane_for(5))) | 1;
     static constexpr int MAXE = (32 * MAXPLANE + 255) / 256;
@@ -45,7 +49,7 @@ struct WCfg {
 template <int K, int S>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
     using C = WCfg<K, S>;
-    constexpr int TP = C::TP, NT = C::NT, TH = C::TH, MAXE = C::MAXE;
+    constexpr int TP = C::TP, NT = C::NT, TH = C::TH, MAXE = C::MAXE, TG = C::TG, NTG = C::NTG;
     extern __shared__ float lds[];
 
     const int PC = 1 << p.log2pc, PR = TP >> p.log2pc;
@@ -59,7 +63,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
     const int li = lane & 31, lk = lane >> 5;
     const int ofrag = wave & 1, thalf = wave >> 1;
     const int cb = blockIdx.y * 32, ob = blockIdx.z * 64;
-    const int slice = blockIdx.x;
+    const int tg = TG == 1 ? 0 : (int)blockIdx.x / p.nslices;
+    const int slice = TG == 1 ? (int)blockIdx.x : (int)blockIdx.x - tg * p.nslices;
+    const int tbase = tg * NTG;
     const int Cin = p.C0 + p.C1;
     const int HWin = p.Hin * p.Win, HWo = p.Hout * p.Wout;
 
@@ -137,8 +143,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
             const int abase = li * planeP + (qy * S) * cols + qx * S;
 #pragma unroll
             for (int i = 0; i < TH; ++i) {
-                const int t = 2 * i + thalf;
-                if (t < NT) {
+                const int t = tbase + 2 * i + thalf;
+                if (2 * i + thalf < NTG) {
                     const float a = Xl[abase + (t / K) * cols + (t % K)];
                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[i], 0, 0, 0);
                 }
@@ -150,8 +156,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
     // ---- write slab [slice][tap][CinP][CoutB]
 #pragma unroll
     for (int i = 0; i < TH; ++i) {
-        const int t = 2 * i + thalf;
-        if (t < NT) {
+        const int t = tbase + 2 * i + thalf;
+        if (2 * i + thalf < NTG) {
             float* sl = p.slabs + (((size_t)slice * NT + t) * p.CinP + cb) * p.CoutB + ob + ofrag * 32 + li;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1009,7 +1015,7 @@ bool wino_wgrad(const c2s_wgrad_desc* d) {
 }
 
 struct TapTable {
-    int off[16];
+    int off[C2S_MAX_TAPS];
 };
 
 // Slice sum of one output element, shared by the per-layer and the batched kernel.  FOUR lanes per element (a launch has only
@@ -1079,7 +1085,7 @@ int launch_wgrad_tile(const c2s_wgrad_desc* d, WgradParams& p, hipStream_t st) {
 template <int K, int S>
 int launch_wgrad(const c2s_wgrad_desc* d, WgradParams& p, hipStream_t st) {
     using C = WCfg<K, S>;
-    {   // tiled path: 32- or 16-wide aligned tiles
+    if constexpr (S == 1 || K == 4) {   // tiled path: 32- or 16-wide aligned tiles (pad (K-1)/2 kernels)
         constexpr int TP = TCfg<K, S>::TP;
         constexpr int MODE = (K == 4) ? 0 : 1;
         const int pad = (K == 1) ? 0 : 1;
@@ -1097,7 +1103,7 @@ int launch_wgrad(const c2s_wgrad_desc* d, WgradParams& p, hipStream_t st) {
     const int plane = ((PR - 1) * S + K) * ((PC - 1) * S + K);
     const size_t lds = ((size_t)32 * (plane | 1) + (size_t)64 * (C::TP + 1)) * sizeof(float);
     c2s_ensure_init();
-    dim3 grid(p.nslices, p.CinP / 32, p.CoutB / 64);
+    dim3 grid(p.nslices * C::TG, p.CinP / 32, p.CoutB / 64);
     hipLaunchKernelGGL((conv_wgrad_kernel<K, S>), grid, dim3(256), lds, st, p);
     C2S_CHECK_LAUNCH("conv_wgrad");
     return C2S_OK;
@@ -1122,6 +1128,8 @@ void init_hook() {
     C2S_RAISE_LDS((conv_wgrad_kernel<3, 1>));
     C2S_RAISE_LDS((conv_wgrad_kernel<1, 1>));
     C2S_RAISE_LDS((conv_wgrad_kernel<4, 2>));
+    C2S_RAISE_LDS((conv_wgrad_kernel<2, 2>));
+    C2S_RAISE_LDS((conv_wgrad_kernel<6, 2>));
     C2S_RAISE_LDS(conv_wgrad_winograd_kernel<2>);
     C2S_RAISE_LDS(conv_wgrad_s2wino_kernel);
 }
@@ -1194,6 +1202,8 @@ extern "C" int c2s_conv_wgrad(const c2s_wgrad_desc* d, const float* src0, const 
     if (d->KH == 3 && d->S == 1) return launch_wgrad<3, 1>(d, p, st);
     if (d->KH == 1 && d->S == 1) return launch_wgrad<1, 1>(d, p, st);
     if (d->KH == 4 && d->S == 2) return launch_wgrad<4, 2>(d, p, st);
+    if (d->KH == 2 && d->S == 2) return launch_wgrad<2, 2>(d, p, st);
+    if (d->KH == 6 && d->S == 2) return launch_wgrad<6, 2>(d, p, st);
     c2s_set_error("wgrad: unsupported (K=%d,S=%d)", d->KH, d->S);
     return C2S_EINVAL;
 }
@@ -1206,7 +1216,7 @@ struct ReduceJob {
     float* dst;
     long so, sc;
     int nslices, NT, Cin, Cout, CinP, CoutB, accumulate, block_start;
-    int taps[16];
+    int taps[C2S_MAX_TAPS];
 };
 
 __global__ void wgrad_reduce_batch_kernel(const ReduceJob* __restrict__ jobs, int njobs) {
@@ -1248,7 +1258,7 @@ extern "C" int c2s_wgrad_reduce_job_fill(void* host_record, const c2s_wgrad_desc
     j->nslices = d->nslices; j->NT = NT; j->Cin = Cin; j->Cout = d->Cout;
     j->CinP = cdiv(Cin, 32) * 32; j->CoutB = cdiv(d->Cout, 64) * 64;
     j->accumulate = accumulate; j->block_start = block_start;
-    for (int i = 0; i < 16; ++i) j->taps[i] = i < NT ? host_tap_off[i] : 0;
+    for (int i = 0; i < C2S_MAX_TAPS; ++i) j->taps[i] = i < NT ? host_tap_off[i] : 0;
     return C2S_OK;
 }
 
@@ -1267,7 +1277,7 @@ extern "C" int c2s_wgrad_reduce(const c2s_wgrad_desc* d, const float* slabs, flo
     const int NT = d->KH * d->KW;
     const int Cin = d->C0 + d->C1;
     TapTable tt;
-    for (int i = 0; i < 16; ++i) tt.off[i] = i < NT ? host_tap_off[i] : 0;
+    for (int i = 0; i < C2S_MAX_TAPS; ++i) tt.off[i] = i < NT ? host_tap_off[i] : 0;
     const long total = (long)NT * Cin * d->Cout;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(4 * total, 256)), dim3(256), 0, (hipStream_t)stream, slabs, dst,
                        d->nslices, NT, Cin, d->Cout, cdiv(Cin, 32) * 32, cdiv(d->Cout, 64) * 64, stride_o, stride_c, tt,

@@ -429,7 +429,7 @@ struct PackJob {
     int cin, cout, coutP, ntaps;
     int kind;            // 0: wpk[tap][cin][coutP]   1: Winograd U   2: Winograd U in the 8-wave kernel's layout   3: conv_s2wino.hip's   4: conv_s2dgrad.hip's
     int block_start;     // first block of this job
-    int taps[16];
+    int taps[C2S_MAX_TAPS];
 };
 
 __global__ void pack_batch_kernel(const PackJob* __restrict__ jobs, int njobs) {
@@ -568,12 +568,12 @@ extern "C" size_t c2s_pack_job_bytes(void) { return sizeof(PackJob); }
 // Fill one job record of a host-side table (the caller uploads the table once and reuses it every step)
 extern "C" int c2s_pack_job_fill(void* host_record, const float* src, float* dst, int cin, int cout, int coutP, int ntaps,
                                  long stride_o, long stride_c, int winograd, const int* host_tap_off, int block_start) {
-    C2S_REQUIRE(host_record && src && dst && host_tap_off && ntaps >= 1 && ntaps <= 16 && winograd >= 0 && winograd <= 4,
+    C2S_REQUIRE(host_record && src && dst && host_tap_off && ntaps >= 1 && ntaps <= C2S_MAX_TAPS && winograd >= 0 && (winograd == 0 || ntaps <= 16) && winograd <= 4,
                 "pack_job_fill: bad args");
     PackJob* j = reinterpret_cast<PackJob*>(host_record);
     j->src = src; j->dst = dst; j->so = stride_o; j->sc = stride_c;
     j->cin = cin; j->cout = cout; j->coutP = coutP; j->ntaps = ntaps; j->kind = winograd; j->block_start = block_start;
-    for (int i = 0; i < 16; ++i) j->taps[i] = i < ntaps ? host_tap_off[i] : 0;
+    for (int i = 0; i < C2S_MAX_TAPS; ++i) j->taps[i] = i < ntaps ? host_tap_off[i] : 0;
     return C2S_OK;
 }
 

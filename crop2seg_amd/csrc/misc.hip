@@ -175,9 +175,9 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ i
 }
 
 // data gradient, gather form: input pixel j receives from the padded positions that reflect onto it
-// (j itself; -1 if j == 1; n if j == n-2) through every tap whose output index is integral and in range.
-// Per dimension that is a short list of (output index, tap) pairs -- at most 3 for 3x3/s1 plus one mirrored, at most
-// 2 + 2 for 4x4/s2 -- built once per thread without branches in the accumulation loop (invalid slots point at output 0
+// (j itself; -j if 1 <= j <= pad; 2(n-1) - j if n-1-pad <= j <= n-2) through every tap whose output index is integral and
+// in range.  Per dimension that is a short list of (output index, tap) pairs -- at most 3 for 3x3/s1 plus one mirrored,
+// at most 2 + 2 for 4x4/s2, 3 + 1 for 6x6/s2 (pad 2), 1 for 2x2/s2 -- built once per thread without branches in the accumulation loop (invalid slots point at output 0
 // with weight 0); the 2-D gradient is the product of the two lists.  Four adjacent pixels of a row per thread (float4
 // store; the row list is shared).
 template <int K, int S>
@@ -191,8 +191,12 @@ __device__ __forceinline__ void dw_pairs(int j, int n_in, int n_out, int pad, bo
         const bool ok = t >= 0 && (t % S) == 0 && t / S < n_out;
         if (ok && cnt < 4) { o[cnt] = t / S; k[cnt] = kk; ++cnt; }
     }
-    const int qm = (rf && j == 1) ? -1 : ((rf && j == n_in - 2) ? n_in : -2);
-    if (qm != -2) {
+    // mirrored sources: -j on the low side, 2(n-1) - j on the high side (both on planes of at most 2 * pad + 1)
+    const bool lo = rf && j >= 1 && j <= pad, hi = rf && j >= n_in - 1 - pad && j <= n_in - 2;
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        if (side == 0 ? !lo : !hi) continue;
+        const int qm = side == 0 ? -j : 2 * (n_in - 1) - j;
 #pragma unroll
         for (int kk = 0; kk < K; ++kk) {
             const int t = qm + pad - kk;
@@ -513,8 +517,9 @@ extern "C" int c2s_frame_flags(const float* x, int* valid, int N, long frame_ele
 
 static int dw_check(int N, int C, int Hin, int Win, int K, int S, int pad, int pad_mode) {
     C2S_REQUIRE(N > 0 && C > 0 && Hin > 0 && Win > 0, "dwconv: bad shape");
-    C2S_REQUIRE(((K == 3 && S == 1) || (K == 4 && S == 2)) && pad == 1, "dwconv: built for (K,S,pad) = (3,1,1) and (4,2,1)");
-    if (pad_mode == C2S_PAD_REFLECT) C2S_REQUIRE(Hin >= 2 && Win >= 2, "dwconv: reflect needs planes >= 2x2");
+    C2S_REQUIRE((K == 3 && S == 1 && pad == 1) || (K == 4 && S == 2 && pad == 1) || (K == 2 && S == 2 && pad == 0) ||
+                (K == 6 && S == 2 && pad == 2), "dwconv: built for (K,S,pad) = (3,1,1), (4,2,1), (2,2,0) and (6,2,2)");
+    if (pad_mode == C2S_PAD_REFLECT) C2S_REQUIRE(Hin > pad && Win > pad && Hin >= 2 && Win >= 2, "dwconv: reflect needs pad < plane");
     return C2S_OK;
 }
 
@@ -525,7 +530,11 @@ extern "C" int c2s_dwconv_fwd(const float* in, const float* w, float* out, const
     const int Ho = (Hin + 2 * pad - K) / S + 1, Wo = (Win + 2 * pad - K) / S + 1;
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
     hipStream_t st = (hipStream_t)stream;
-    if (Wo % 4 == 0) {
+    if (K == 2 || K == 6) {         // the 4-wide span loader assumes pad 1: one output per thread
+        const dim3 grid(cdiv(Ho * Wo, 256), N * C);
+        if (K == 2) hipLaunchKernelGGL((dw_fwd_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
+        else hipLaunchKernelGGL((dw_fwd_kernel<6, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
+    } else if (Wo % 4 == 0) {
         const dim3 grid(cdiv(Ho * (Wo / 4), 256), N * C);
         if (K == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 1, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
         else hipLaunchKernelGGL((dw_fwd_kernel<4, 2, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
@@ -544,7 +553,11 @@ extern "C" int c2s_dwconv_dgrad(const float* gout, const float* w, float* gin, c
     C2S_REQUIRE(gout && w && gin, "dwconv_dgrad: null pointer");
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
     hipStream_t st = (hipStream_t)stream;
-    if (Win % 4 == 0 && Win >= 8 && Hin >= 4 && (K == 3 || Hin % 2 == 0)) {
+    if (K == 2 || K == 6) {         // the 4-wide stencil is written for pad 1: the gather form
+        const dim3 grid(cdiv(Hin * Win, 256), N * C);
+        if (K == 2) hipLaunchKernelGGL((dw_dgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
+        else hipLaunchKernelGGL((dw_dgrad_kernel<6, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
+    } else if (Win % 4 == 0 && Win >= 8 && Hin >= 4 && (K == 3 || Hin % 2 == 0)) {
         const dim3 grid(cdiv(Hin * (Win / 4), 256), N * C);
         if (K == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
         else hipLaunchKernelGGL((dw_dgrad_kernel<4, 2, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
@@ -565,7 +578,10 @@ extern "C" int c2s_dwconv_wgrad(const float* in, const float* gout, float* parti
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
     const int Wo = (Win + 2 * pad - K) / S + 1;
     const dim3 grid(N * C);
-    if (Wo % 4 == 0) {
+    if (K == 2 || K == 6) {
+        if (K == 2) hipLaunchKernelGGL((dw_wgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
+        else hipLaunchKernelGGL((dw_wgrad_kernel<6, 2, 1>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
+    } else if (Wo % 4 == 0) {
         if (K == 3) hipLaunchKernelGGL((dw_wgrad_kernel<3, 1, 4>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
         else hipLaunchKernelGGL((dw_wgrad_kernel<4, 2, 4>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
     } else {

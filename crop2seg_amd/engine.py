@@ -457,6 +457,34 @@ def _xpair_taps(py: int) -> List[int]:
     return [((3 - py) - 2 * ty) * 4 + ((3 - px) - 2 * tx) for px in range(2) for ty in range(2) for tx in range(2)]
 
 
+# (str_conv_k, str_conv_p) of the stride-2 down / up convolutions besides the default (4, 1): their data gradients and the
+# transposed forward run as four stride-1 parity sub-convolutions of (k/2)x(k/2) taps on the implicit-GEMM kernel
+PARITY_GEOMETRIES = ((2, 0), (6, 2))
+
+
+def _parity_taps(K: int, pad: int, py: int, px: int) -> List[int]:
+    """Taps of the (K/2)x(K/2) parity sub-kernel (stride 1, pad pad/2, output rows 2*a + py) of a stride-2 transposed
+    convolution with kernel K and padding pad = K/2 - 1: sub-tap t reads row a - pad/2 + t through kernel row
+    py + 2*pad - 2*t.  Ordered [ty][tx] as the sub-kernel's taps."""
+    kp = K // 2
+    return [(py + 2 * pad - 2 * ty) * K + (px + 2 * pad - 2 * tx) for ty in range(kp) for tx in range(kp)]
+
+
+def _parity_transpose(ctx: Ctx, key: Tuple, g: Tensor, Wsrc: Tensor, src_off: int, cin: int, cout: int, so: int, sc: int,
+                      K: int, pad: int, bias: Optional[Tensor], out: Tensor, accumulate: int, radj: int,
+                      valid: Optional[Tensor]) -> None:
+    """out (2H x 2W) = stride-2 transposed convolution of g (H x W) with kernel K, padding pad, as four implicit-GEMM
+    launches; radj folds the reflect-pad-2 adjoint into the 3x3 launches (data gradient of a reflect-padded down conv)."""
+    N, _, H, Wd = g.shape
+    kp = K // 2
+    for py in range(2):
+        for px in range(2):
+            wpk, CP = ctx.pack(key + ("par", py, px), Wsrc, src_off, cin, cout, kp * kp, so, sc, _parity_taps(K, pad, py, px))
+            d = ConvDesc(N, cin, 0, H, Wd, cout, CP, H, Wd, 2 * H, 2 * Wd, kp, kp, 1, pad // 2, pad // 2, _lib.PAD_ZEROS,
+                         2, 2, py, px, accumulate, 2 if radj else 0)
+            _igemm(d, g, None, wpk, bias, out, valid)
+
+
 def _xpair(d: ConvDesc, src: Tensor, wpk: Tensor, bias: Optional[Tensor], out: Tensor, valid: Optional[Tensor]) -> None:
     check(lib().c2s_conv_xpair(C.byref(d), src.data_ptr(), wpk.data_ptr(), _ptr(bias), out.data_ptr(), _ptr(valid),
                                _stream()), "conv_xpair")
@@ -605,6 +633,10 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
                     dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Hin, Win, Hin, Win, K, K, 1, K - 1 - pad, K - 1 - pad,
                                   _lib.PAD_ZEROS, 1, 1, 0, 0, accf, radj)
                     _igemm(dd, g, None, wd, None, gin, valid)
+            elif (K, pad) in PARITY_GEOMETRIES:
+                assert S == 2 and Hin == 2 * Ho and Win == 2 * Wo
+                _parity_transpose(ctx, (wname, "dgrad", si), g, W, c_lo * KK, Cout, Cs, KK, Cin * KK, K, pad, None, gin, accf,
+                                  radj, valid)
             else:
                 assert K == 4 and S == 2 and pad == 1
                 assert Hin == 2 * Ho and Win == 2 * Wo
@@ -643,17 +675,23 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
     return out
 
 
-def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str) -> Tensor:
-    """nn.ConvTranspose2d(k=4, s=2, p=1) (reference conv.py:384-390) as four 2x2 parity sub-convolutions."""
+def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str, K: int = 4, pad: int = 1) -> Tensor:
+    """nn.ConvTranspose2d(k, s=2, p) (reference conv.py:384-390) for (k, p) = (4, 1) and PARITY_GEOMETRIES, as four
+    (k/2)x(k/2) parity sub-convolutions."""
     Wt = ctx.p[wname]
     Cin, Cout = Wt.shape[0], Wt.shape[1]
     N, _, H, Wd = x.shape
+    assert (K, pad) == (4, 1) or (K, pad) in PARITY_GEOMETRIES, (K, pad)
+    KK = K * K
     out = torch.empty(N, Cout, 2 * H, 2 * Wd, device=x.device, dtype=torch.float32)
     bias = ctx.p[bname]
-    for py in range(2):
-        wpk, CP = ctx.pack((wname, "fwd", py), Wt, 0, Cin, Cout, 8, 16, Cout * 16, _xpair_taps(py))
-        d = ConvDesc(N, Cin, 0, H, Wd, Cout, CP, H, Wd, 2 * H, 2 * Wd, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS, 2, 2, py, 0, 0)
-        _xpair(d, x, wpk, bias, out, None)
+    if K == 4:
+        for py in range(2):
+            wpk, CP = ctx.pack((wname, "fwd", py), Wt, 0, Cin, Cout, 8, 16, Cout * 16, _xpair_taps(py))
+            d = ConvDesc(N, Cin, 0, H, Wd, Cout, CP, H, Wd, 2 * H, 2 * Wd, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS, 2, 2, py, 0, 0)
+            _xpair(d, x, wpk, bias, out, None)
+    else:
+        _parity_transpose(ctx, (wname, "fwd"), x, Wt, 0, Cin, Cout, KK, Cout * KK, K, pad, bias, out, 0, 0, None)
     if ctx.tape is None:
         return out
     tape = ctx.tape
@@ -664,12 +702,12 @@ def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str) -> Tensor:
         if g is None:
             return
         gw, acc = ctx.grad_sink(wname)
-        # dW[ci,co,k] = sum x[ci,p] * g[co, 2p+k-1]  ==  conv4x4s2 weight gradient with (input=g, gout=x)
-        _wgrad(ctx, [g], x, Cin, H, Wd, 4, 2, 1, _lib.PAD_ZEROS, gw, Cout * 16, 16, list(range(16)), acc, None)
+        # dW[ci,co,k] = sum x[ci,p] * g[co, 2p+k-pad]  ==  convKxKs2 weight gradient with (input=g, gout=x)
+        _wgrad(ctx, [g], x, Cin, H, Wd, K, 2, pad, _lib.PAD_ZEROS, gw, Cout * KK, KK, list(range(KK)), acc, None)
         existing = tape.grad_of(x)
         gin = existing if existing is not None else torch.empty_like(x)
-        wd, CP = ctx.pack((wname, "dgrad"), Wt, 0, Cout, Cin, 16, Cout * 16, 16, list(range(16)))
-        dd = ConvDesc(N, Cout, 0, 2 * H, 2 * Wd, Cin, CP, H, Wd, H, Wd, 4, 4, 2, 1, 1, _lib.PAD_ZEROS, 1, 1, 0, 0,
+        wd, CP = ctx.pack((wname, "dgrad"), Wt, 0, Cout, Cin, KK, Cout * KK, KK, list(range(KK)))
+        dd = ConvDesc(N, Cout, 0, 2 * H, 2 * Wd, Cin, CP, H, Wd, H, Wd, K, K, 2, pad, pad, _lib.PAD_ZEROS, 1, 1, 0, 0,
                       1 if existing is not None else 0)
         _igemm(dd, g, None, wd, None, gin, None)
         if existing is None:
