@@ -55,6 +55,14 @@ __device__ __forceinline__ float wave_max(float v) {
 // taps of the largest packed kernel (the 6x6 stride-2 convolutions): tap tables of the weight packs and slice sums
 constexpr int C2S_MAX_TAPS = 36;
 
+// Packed Winograd layouts: written by pack.hip, read by the convolution kernels named
+constexpr int WN_CK = 8;                            // conv_winograd.hip: input channels per chunk
+constexpr int WN_USLAB = 16 * WN_CK * 64;           // floats of one U chunk
+constexpr int W16_CK = 8;                           // conv_winograd16.hip: input channels per chunk
+constexpr int W16_UP = 16;                          // floats per (c, o): the 16 points, stored [c][xi 4][o 64][nu 4]
+constexpr int S2_UP = 12;                           // conv_s2wino.hip: floats per (c, parity, o): 9 points + 3 zeros
+constexpr int D2_UP = 12;                           // conv_s2dgrad.hip: floats per (k, parity, c): 9 points + 3 zeros
+
 __device__ __forceinline__ int reflect_idx(int i, int n) {
     // single reflection (pad < n): -1 -> 1, n -> n-2
     i = i < 0 ? -i : i;

@@ -310,21 +310,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     }
 }
 
-struct TapTable {
-    int off[C2S_MAX_TAPS];
-};
-
-__global__ void pack_weights_kernel(const float* __restrict__ src, float* __restrict__ wpk, int cin, int cout,
-                                    int coutP, int ntaps, long so, long sc, TapTable tt) {
-    const long total = (long)ntaps * cin * coutP;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int o = (int)(e % coutP);
-        const long tc = e / coutP;
-        const int c = (int)(tc % cin), t = (int)(tc / cin);
-        wpk[e] = o < cout ? src[o * so + c * sc + tt.off[t]] : 0.f;
-    }
-}
-
 template <int K, int S, int MF, bool ADJ>
 int launch_conv(const ConvParams& p, int N, int tiles, hipStream_t st) {
     constexpr int CK = Cfg<K, S>::CK;
@@ -352,20 +337,6 @@ void init_hook() {
 C2sInitRegistrar registrar(init_hook);
 
 }  // namespace
-
-extern "C" int c2s_pack_weights(const float* src, float* wpk, int cin, int cout, int coutP, int ntaps, long stride_o,
-                                long stride_c, const int* host_tap_off, void* stream) {
-    C2S_REQUIRE(src && wpk && host_tap_off, "pack_weights: null pointer");
-    C2S_REQUIRE(ntaps >= 1 && ntaps <= C2S_MAX_TAPS && coutP % 32 == 0 && coutP >= cout, "pack_weights: bad sizes");
-    TapTable tt;
-    for (int i = 0; i < C2S_MAX_TAPS; ++i) tt.off[i] = i < ntaps ? host_tap_off[i] : 0;
-    const long total = (long)ntaps * cin * coutP;
-    const int blocks = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, wpk, cin, cout,
-                       coutP, ntaps, stride_o, stride_c, tt);
-    C2S_CHECK_LAUNCH("pack_weights");
-    return C2S_OK;
-}
 
 extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const float* src1, const float* wpk,
                               const float* bias, float* out, const int* valid, void* stream) {

@@ -36,7 +36,6 @@ struct S2dParams {
     int N, tiles, tiles_x, nchunks;
 };
 
-constexpr int D2_UP = 12;
 constexpr int D2_UHALF = 4 * 128 * D2_UP;            // one k-step (4 gy channels x 128 virtual channels): 6,144 floats = 24 KB
 constexpr int D2_USLAB = 2 * D2_UHALF;               // a chunk of 8 gy channels: 48 KB
 constexpr int D2_URING = 5 * D2_UHALF;               // 120 KB
@@ -337,69 +336,12 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
     }
 }
 
-struct TapTable16d {
-    int off[16];
-};
-
-// U = G g Gt of the 2x2 sub-filter of output parity (ey, ex): rows ky = (3, 1) for ey = 0, (2, 0) for ey = 1 (columns likewise);
-// element w(k = gy channel, c = input channel, ky, kx) = src[c * so + k * sc + tap[ky * 4 + kx]];
-// stored [ey][cin block][chunk][2 k-steps][4 k][128 = ex * 64 + (c & 63)][12]
-__global__ void pack_s2dgrad_kernel(const float* __restrict__ src, float* __restrict__ upk, int kc, int cs, int csP, long so,
-                                    long sc, TapTable16d tt) {
-    const int nchunks = kc / 8;
-    const long total = (long)4 * kc * csP;               // (ey, ex, k, c)
-    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int c = (int)(e % csP);
-    const int k = (int)((e / csP) % kc);
-    const int par = (int)(e / csP / kc);
-    const int ey = par >> 1, ex = par & 1;
-    const bool real = c < cs;
-    float g[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int ky = (ey == 0 ? 3 : 2) - 2 * a, kx = (ex == 0 ? 3 : 2) - 2 * b;
-            g[a][b] = real ? src[c * so + k * sc + tt.off[ky * 4 + kx]] : 0.f;
-        }
-    const int cblocks = csP / 64;
-    float* base = upk + ((((size_t)(ey * cblocks + (c >> 6)) * nchunks + (k >> 3)) * 2 + ((k >> 2) & 1)) * 4 + (k & 3)) * 128 * D2_UP +
-                  (size_t)(ex * 64 + (c & 63)) * D2_UP;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float u0 = i == 0 ? g[0][0] : (i == 1 ? g[0][0] + g[1][0] : g[1][0]);
-        const float u1 = i == 0 ? g[0][1] : (i == 1 ? g[0][1] + g[1][1] : g[1][1]);
-        base[i * 3 + 0] = u0;
-        base[i * 3 + 1] = u0 + u1;
-        base[i * 3 + 2] = u1;
-    }
-#pragma unroll
-    for (int i = 9; i < D2_UP; ++i) base[i] = 0.f;
-}
-
 void init_hook() {
     C2S_RAISE_LDS(conv_s2dgrad_kernel);
 }
 C2sInitRegistrar registrar(init_hook);
 
 }  // namespace
-
-extern "C" size_t c2s_s2dgrad_packed_floats(int kc, int csP) {
-    return (size_t)4 * kc * csP * D2_UP;
-}
-
-extern "C" int c2s_pack_weights_s2dgrad(const float* src, float* upk, int kc, int cs, int csP, long stride_c, long stride_k,
-                                        const int* host_tap_off, void* stream) {
-    C2S_REQUIRE(src && upk && host_tap_off && kc > 0 && kc % 8 == 0 && cs > 0 && csP % 64 == 0 && csP >= cs, "pack_s2dgrad: bad args");
-    TapTable16d tt;
-    for (int i = 0; i < 16; ++i) tt.off[i] = host_tap_off[i];
-    const long total = (long)4 * kc * csP;
-    hipLaunchKernelGGL(pack_s2dgrad_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src, upk, kc, cs, csP,
-                       stride_c, stride_k, tt);
-    C2S_CHECK_LAUNCH("pack_s2dgrad");
-    return C2S_OK;
-}
 
 // d: the FORWARD convolution's geometry seen from the gradient: C0 = gy channels (the forward Cout), Hin x Win = the gy plane
 // (forward output), Cout / CoutP = the forward input channels of this source, Hout x Wout = 2 Hin x 2 Win = the gx plane

@@ -35,7 +35,6 @@ struct S2wParams {
     int N, tiles, tiles_x, nchunks;
 };
 
-constexpr int S2_UP = 12;                            // floats per (c, parity, o): 9 points + 3
 constexpr int S2_UHALF = 4 * 64 * S2_UP;             // one k-step (one input channel, four parities): 3,072 floats = 12 KB
 constexpr int S2_USLAB = 2 * S2_UHALF;               // a chunk of two input channels: 24 KB
 constexpr int S2_URING = 5 * S2_UHALF;               // 60 KB
@@ -315,66 +314,12 @@ __global__ __launch_bounds__(512, 1) void conv_s2wino_kernel(S2wParams p) {
     }
 }
 
-struct TapTable16s {
-    int off[16];
-};
-
-// U = G g Gt of the four 2x2 parity sub-filters of the 4x4 filter w[ky][kx] = src[o*so + c*sc + tap[ky*4+kx]]:
-// parity 0 of a dimension uses taps (1, 3), parity 1 taps (0, 2); stored [cout block][chunk][2 c][4 parities][64 o][12]
-__global__ void pack_s2wino_kernel(const float* __restrict__ src, float* __restrict__ upk, int cin, int cout, int coutP,
-                                   long so, long sc, TapTable16s tt) {
-    const int nchunks = (cin + 1) / 2;
-    const long total = (long)nchunks * 2 * 4 * coutP;
-    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int o = (int)(e % coutP);
-    const int par = (int)((e / coutP) & 3), c = (int)(e / coutP / 4);
-    const int py = par >> 1, px = par & 1;
-    const bool real = o < cout && c < cin;
-    float g[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int ky = (py == 0 ? 1 : 0) + 2 * a, kx = (px == 0 ? 1 : 0) + 2 * b;
-            g[a][b] = real ? src[o * so + c * sc + tt.off[ky * 4 + kx]] : 0.f;
-        }
-    float u[3][2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) { u[0][b] = g[0][b]; u[1][b] = g[0][b] + g[1][b]; u[2][b] = g[1][b]; }
-    float* base = upk + ((((size_t)(o >> 6) * nchunks + (c >> 1)) * 2 + (c & 1)) * 4 + par) * 64 * S2_UP + (size_t)(o & 63) * S2_UP;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        base[i * 3 + 0] = u[i][0];
-        base[i * 3 + 1] = u[i][0] + u[i][1];
-        base[i * 3 + 2] = u[i][1];
-    }
-#pragma unroll
-    for (int i = 9; i < S2_UP; ++i) base[i] = 0.f;
-}
-
 void init_hook() {
     C2S_RAISE_LDS(conv_s2wino_kernel);
 }
 C2sInitRegistrar registrar(init_hook);
 
 }  // namespace
-
-extern "C" size_t c2s_s2wino_packed_floats(int cin, int coutP) {
-    return (size_t)((cin + 1) / 2) * 2 * 4 * coutP * S2_UP;
-}
-
-extern "C" int c2s_pack_weights_s2wino(const float* src, float* upk, int cin, int cout, int coutP, long stride_o,
-                                       long stride_c, const int* host_tap_off, void* stream) {
-    C2S_REQUIRE(src && upk && host_tap_off && cin > 0 && cout > 0 && coutP % 64 == 0 && coutP >= cout, "pack_s2wino: bad args");
-    TapTable16s tt;
-    for (int i = 0; i < 16; ++i) tt.off[i] = host_tap_off[i];
-    const long total = (long)((cin + 1) / 2) * 2 * 4 * coutP;
-    hipLaunchKernelGGL(pack_s2wino_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src, upk, cin, cout,
-                       coutP, stride_o, stride_c, tt);
-    C2S_CHECK_LAUNCH("pack_s2wino");
-    return C2S_OK;
-}
 
 extern "C" int c2s_conv4x4s2_winograd_supported(const c2s_conv_desc* d) {
     return d && d->KH == 4 && d->KW == 4 && d->S == 2 && d->pad_y == 1 && d->pad_x == 1 && d->C1 == 0 && d->C0 % 2 == 0 &&

@@ -36,8 +36,6 @@ struct WinoParams {
     int N, tiles, tiles_x, nchunks;
 };
 
-constexpr int WN_CK = 8;
-constexpr int WN_USLAB = 16 * WN_CK * 64;          // floats of one U chunk
 constexpr int WN_EXCH = 4 * 2 * 16 * 64;           // floats of the epilogue exchange [xi][x][row group][lane][4 rows] (one 32-channel half)
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -385,162 +383,6 @@ __global__ __launch_bounds__(256, 2) void conv_winograd_kernel(WinoParams p) {
     WN_STAMP_FLUSH;
 }
 
-struct TapTable9 {
-    int off[9];
-};
-
-// U = G g Gt of the 3x3 filter g[k] = src[o*so + c*sc + tap[k]], stored [cout block][chunk][xn 16][c 8][o 64]
-// (zero for channels / outputs past the real counts)
-__global__ void pack_winograd_kernel(const float* __restrict__ src, float* __restrict__ upk, int cin, int cout, int coutP,
-                                     long so, long sc, TapTable9 tt) {
-    const int nchunks = (cin + WN_CK - 1) / WN_CK;
-    const long total = (long)nchunks * WN_CK * coutP;
-    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int o = (int)(e % coutP), c = (int)(e / coutP);
-    const bool real = o < cout && c < cin;
-    float g[3][3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = real ? src[o * so + c * sc + tt.off[k]] : 0.f;
-    float t[4][3];                                  // G g
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        t[0][j] = g[0][j];
-        t[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-        t[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
-        t[3][j] = g[2][j];
-    }
-    float* base = upk + ((size_t)(o >> 6) * nchunks + (c >> 3)) * WN_USLAB + (c & 7) * 64 + (o & 63);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        base[(i * 4 + 0) * WN_CK * 64] = t[i][0];
-        base[(i * 4 + 1) * WN_CK * 64] = 0.5f * (t[i][0] + t[i][1] + t[i][2]);
-        base[(i * 4 + 2) * WN_CK * 64] = 0.5f * (t[i][0] - t[i][1] + t[i][2]);
-        base[(i * 4 + 3) * WN_CK * 64] = t[i][2];
-    }
-}
-
-// ---- all per-step weight packs in one launch: a device table of jobs (plain tap-major packs for the direct / transposed
-// kernels and Winograd transforms); block -> job by the table's block offsets
-struct PackJob {
-    const float* src;
-    float* dst;
-    long so, sc;
-    int cin, cout, coutP, ntaps;
-    int kind;            // 0: wpk[tap][cin][coutP]   1: Winograd U   2: Winograd U in the 8-wave kernel's layout   3: conv_s2wino.hip's   4: conv_s2dgrad.hip's
-    int block_start;     // first block of this job
-    int taps[C2S_MAX_TAPS];
-};
-
-__global__ void pack_batch_kernel(const PackJob* __restrict__ jobs, int njobs) {
-    int j = 0;
-    while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].block_start) ++j;      // <= ~64 jobs: linear scan
-    const PackJob& jb = jobs[j];
-    const long e = (long)(blockIdx.x - jb.block_start) * blockDim.x + threadIdx.x;
-    if (jb.kind == 0) {
-        const long total = (long)jb.ntaps * jb.cin * jb.coutP;
-        if (e >= total) return;
-        const int o = (int)(e % jb.coutP);
-        const long tc = e / jb.coutP;
-        const int c = (int)(tc % jb.cin), t = (int)(tc / jb.cin);
-        jb.dst[e] = o < jb.cout ? jb.src[o * jb.so + c * jb.sc + jb.taps[t]] : 0.f;
-        return;
-    }
-    if (jb.kind == 3) {          // F(2x2,2x2) parity sub-filters of a 4x4 stride-2 filter (conv_s2wino.hip): [cout block][chunk][2 c][4][64 o][12]
-        const int nch2 = (jb.cin + 1) / 2;
-        const long total3 = (long)nch2 * 2 * 4 * jb.coutP;
-        if (e >= total3) return;
-        const int o = (int)(e % jb.coutP);
-        const int par = (int)((e / jb.coutP) & 3), c = (int)(e / jb.coutP / 4);
-        const int py = par >> 1, px = par & 1;
-        const bool real = o < jb.cout && c < jb.cin;
-        float g2[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int ky = (py == 0 ? 1 : 0) + 2 * a, kx = (px == 0 ? 1 : 0) + 2 * b;
-                g2[a][b] = real ? jb.src[o * jb.so + c * jb.sc + jb.taps[ky * 4 + kx]] : 0.f;
-            }
-        float* base = jb.dst + ((((size_t)(o >> 6) * nch2 + (c >> 1)) * 2 + (c & 1)) * 4 + par) * 64 * 12 + (size_t)(o & 63) * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float u0 = i == 0 ? g2[0][0] : (i == 1 ? g2[0][0] + g2[1][0] : g2[1][0]);
-            const float u1 = i == 0 ? g2[0][1] : (i == 1 ? g2[0][1] + g2[1][1] : g2[1][1]);
-            base[i * 3 + 0] = u0;
-            base[i * 3 + 1] = u0 + u1;
-            base[i * 3 + 2] = u1;
-        }
-        return;
-    }
-    if (jb.kind == 4) {          // per-parity sub-filters of the 4x4 stride-2 data gradient (conv_s2dgrad.hip); here cin = gy
-                                 // channels k, cout / coutP = input channels c: element at src[c * so + k * sc + tap]
-        const long total4 = (long)4 * jb.cin * jb.coutP;
-        if (e >= total4) return;
-        const int c = (int)(e % jb.coutP);
-        const int k = (int)((e / jb.coutP) % jb.cin);
-        const int par = (int)(e / jb.coutP / jb.cin);
-        const int ey = par >> 1, ex = par & 1;
-        const bool real = c < jb.cout;
-        float g2[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int ky = (ey == 0 ? 3 : 2) - 2 * a, kx = (ex == 0 ? 3 : 2) - 2 * b;
-                g2[a][b] = real ? jb.src[c * jb.so + k * jb.sc + jb.taps[ky * 4 + kx]] : 0.f;
-            }
-        const int cblocks = jb.coutP / 64, nch8 = jb.cin / 8;
-        float* base = jb.dst + ((((size_t)(ey * cblocks + (c >> 6)) * nch8 + (k >> 3)) * 2 + ((k >> 2) & 1)) * 4 + (k & 3)) * 128 * 12 +
-                      (size_t)(ex * 64 + (c & 63)) * 12;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float u0 = i == 0 ? g2[0][0] : (i == 1 ? g2[0][0] + g2[1][0] : g2[1][0]);
-            const float u1 = i == 0 ? g2[0][1] : (i == 1 ? g2[0][1] + g2[1][1] : g2[1][1]);
-            base[i * 3 + 0] = u0;
-            base[i * 3 + 1] = u0 + u1;
-            base[i * 3 + 2] = u1;
-        }
-        return;
-    }
-    const int nchunks = (jb.cin + WN_CK - 1) / WN_CK;
-    const long total = (long)nchunks * WN_CK * jb.coutP;
-    if (e >= total) return;
-    const int o = (int)(e % jb.coutP), c = (int)(e / jb.coutP);
-    const bool real = o < jb.cout && c < jb.cin;
-    float g[3][3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = real ? jb.src[o * jb.so + c * jb.sc + jb.taps[k]] : 0.f;
-    float t[4][3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        t[0][q] = g[0][q];
-        t[1][q] = 0.5f * (g[0][q] + g[1][q] + g[2][q]);
-        t[2][q] = 0.5f * (g[0][q] - g[1][q] + g[2][q]);
-        t[3][q] = g[2][q];
-    }
-    if (jb.kind == 2) {          // the 8-wave kernel's layout (conv_winograd16.hip): [cout block][chunk][8 c][4 xi][64 o][4 nu]
-        float* wide = jb.dst + (((size_t)(o >> 6) * nchunks + (c >> 3)) * WN_CK + (c & 7)) * 64 * 16 + (size_t)(o & 63) * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float* w4 = wide + i * 256;
-            w4[0] = t[i][0];
-            w4[1] = 0.5f * (t[i][0] + t[i][1] + t[i][2]);
-            w4[2] = 0.5f * (t[i][0] - t[i][1] + t[i][2]);
-            w4[3] = t[i][2];
-        }
-        return;
-    }
-    float* base = jb.dst + ((size_t)(o >> 6) * nchunks + (c >> 3)) * WN_USLAB + (c & 7) * 64 + (o & 63);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        base[(i * 4 + 0) * WN_CK * 64] = t[i][0];
-        base[(i * 4 + 1) * WN_CK * 64] = 0.5f * (t[i][0] + t[i][1] + t[i][2]);
-        base[(i * 4 + 2) * WN_CK * 64] = 0.5f * (t[i][0] - t[i][1] + t[i][2]);
-        base[(i * 4 + 3) * WN_CK * 64] = t[i][2];
-    }
-}
-
 void init_hook() {
     C2S_RAISE_LDS((conv_winograd_kernel<4, false>));
     C2S_RAISE_LDS((conv_winograd_kernel<4, true>));
@@ -553,57 +395,11 @@ C2sInitRegistrar registrar(init_hook);
 
 }  // namespace
 
-extern "C" size_t c2s_winograd_packed_floats(int cin, int coutP) {
-    return (size_t)(coutP / 64) * cdiv(cin, WN_CK) * WN_USLAB;
-}
-
 #ifdef C2S_WN_STAMP
 extern "C" int c2s_debug_winograd_stamps(unsigned long long* host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(wn_stamps), sizeof(unsigned long long) * 8192 * 8) == hipSuccess ? 0 : 1;
 }
 #endif
-
-extern "C" size_t c2s_pack_job_bytes(void) { return sizeof(PackJob); }
-
-// Fill one job record of a host-side table (the caller uploads the table once and reuses it every step)
-extern "C" int c2s_pack_job_fill(void* host_record, const float* src, float* dst, int cin, int cout, int coutP, int ntaps,
-                                 long stride_o, long stride_c, int winograd, const int* host_tap_off, int block_start) {
-    C2S_REQUIRE(host_record && src && dst && host_tap_off && ntaps >= 1 && ntaps <= C2S_MAX_TAPS && winograd >= 0 && (winograd == 0 || ntaps <= 16) && winograd <= 4,
-                "pack_job_fill: bad args");
-    PackJob* j = reinterpret_cast<PackJob*>(host_record);
-    j->src = src; j->dst = dst; j->so = stride_o; j->sc = stride_c;
-    j->cin = cin; j->cout = cout; j->coutP = coutP; j->ntaps = ntaps; j->kind = winograd; j->block_start = block_start;
-    for (int i = 0; i < C2S_MAX_TAPS; ++i) j->taps[i] = i < ntaps ? host_tap_off[i] : 0;
-    return C2S_OK;
-}
-
-// blocks (of 256 threads) a job needs
-extern "C" int c2s_pack_job_blocks(int cin, int coutP, int ntaps, int winograd) {
-    const long total = winograd == 4 ? (long)4 * cin * coutP : winograd == 3 ? (long)((cin + 1) / 2) * 2 * 4 * coutP
-                       : (winograd ? (long)cdiv(cin, WN_CK) * WN_CK * coutP : (long)ntaps * cin * coutP);
-    return cdiv(total, 256);
-}
-
-extern "C" int c2s_pack_batch(const void* device_table, int njobs, int total_blocks, void* stream) {
-    C2S_REQUIRE(device_table && njobs > 0 && total_blocks > 0, "pack_batch: bad args");
-    hipLaunchKernelGGL(pack_batch_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const PackJob*>(device_table), njobs);
-    C2S_CHECK_LAUNCH("pack_batch");
-    return C2S_OK;
-}
-
-extern "C" int c2s_pack_weights_winograd(const float* src, float* upk, int cin, int cout, int coutP, long stride_o,
-                                         long stride_c, const int* host_tap_off, void* stream) {
-    C2S_REQUIRE(src && upk && host_tap_off, "pack_weights_winograd: null pointer");
-    C2S_REQUIRE(coutP % 64 == 0 && coutP >= cout && cin > 0, "pack_weights_winograd: CoutP must be a multiple of 64");
-    TapTable9 tt;
-    for (int i = 0; i < 9; ++i) tt.off[i] = host_tap_off[i];
-    const long total = (long)cdiv(cin, WN_CK) * WN_CK * coutP;
-    hipLaunchKernelGGL(pack_winograd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src, upk, cin, cout,
-                       coutP, stride_o, stride_c, tt);
-    C2S_CHECK_LAUNCH("pack_weights_winograd");
-    return C2S_OK;
-}
 
 extern "C" int c2s_conv3x3_winograd(const c2s_conv_desc* d, const float* src0, const float* src1, const float* upk,
                                     const float* bias, float* out, const int* valid, void* stream) {

@@ -53,8 +53,6 @@ struct Wino16Params {
     int N, tiles, tiles_x, nchunks;
 };
 
-constexpr int W16_CK = 8;
-constexpr int W16_UP = 16;                          // floats per (c, o): the 16 points, stored [c][xi 4][o 64][nu 4] (see the pack kernel)
 constexpr int W16_USLAB = W16_CK * 64 * W16_UP;     // 8,192 floats = 32 KB per chunk
 constexpr int W16_UHALF = W16_USLAB / 2;            // a k-step's half slab (4 channels): 16 KB; ring of five
 constexpr int W16_URING = 5 * W16_UHALF;            // 80 KB
@@ -485,43 +483,6 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
 #endif
 }
 
-struct TapTable9w {
-    int off[9];
-};
-
-// U = G g Gt of the 3x3 filter g[k] = src[o*so + c*sc + tap[k]], stored [cout block][chunk][c 8][xi 4][o 64][nu 4]
-__global__ void pack_winograd16_kernel(const float* __restrict__ src, float* __restrict__ upk, int cin, int cout, int coutP,
-                                       long so, long sc, TapTable9w tt) {
-    const int nchunks = (cin + W16_CK - 1) / W16_CK;
-    const long total = (long)nchunks * W16_CK * coutP;
-    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int o = (int)(e % coutP), c = (int)(e / coutP);
-    const bool real = o < cout && c < cin;
-    float g[3][3];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = real ? src[o * so + c * sc + tt.off[k]] : 0.f;
-    float tmp[4][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        tmp[0][j] = g[0][j];
-        tmp[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-        tmp[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
-        tmp[3][j] = g[2][j];
-    }
-    // row xi of the 4x4 points of (c, o) at [c][xi][o][nu]: the 16 lanes of an MFMA operand read (16 consecutive output channels,
-    // one xi) touch 256 contiguous bytes -- conflict-free without the four floats of padding per (c, o) that round 3 carried
-    float* base = upk + (((size_t)(o >> 6) * nchunks + (c >> 3)) * W16_CK + (c & 7)) * 64 * W16_UP + (size_t)(o & 63) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float* b4 = base + i * 256;
-        b4[0] = tmp[i][0];
-        b4[1] = 0.5f * (tmp[i][0] + tmp[i][1] + tmp[i][2]);
-        b4[2] = 0.5f * (tmp[i][0] - tmp[i][1] + tmp[i][2]);
-        b4[3] = tmp[i][2];
-    }
-}
-
 void init_hook() {
     C2S_RAISE_LDS((conv_winograd16_kernel<false, 4, 16>));
     C2S_RAISE_LDS((conv_winograd16_kernel<true, 4, 16>));
@@ -535,22 +496,6 @@ extern "C" int c2s_debug_w16_stamps(unsigned long long* host_out) {
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(w16_stamps), sizeof(unsigned long long) * 1024 * 4) == hipSuccess ? 0 : 1;
 }
 #endif
-
-extern "C" size_t c2s_winograd16_packed_floats(int cin, int coutP) {
-    return (size_t)((cin + W16_CK - 1) / W16_CK) * W16_CK * coutP * W16_UP;
-}
-
-extern "C" int c2s_pack_weights_winograd16(const float* src, float* upk, int cin, int cout, int coutP, long stride_o,
-                                           long stride_c, const int* host_tap_off, void* stream) {
-    C2S_REQUIRE(src && upk && host_tap_off && cin > 0 && cout > 0 && coutP % 64 == 0 && coutP >= cout, "pack_winograd16: bad args");
-    TapTable9w tt;
-    for (int i = 0; i < 9; ++i) tt.off[i] = host_tap_off[i];
-    const long total = (long)((cin + W16_CK - 1) / W16_CK) * W16_CK * coutP;
-    hipLaunchKernelGGL(pack_winograd16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src, upk, cin, cout,
-                       coutP, stride_o, stride_c, tt);
-    C2S_CHECK_LAUNCH("pack_winograd16");
-    return C2S_OK;
-}
 
 extern "C" int c2s_conv3x3_winograd16_supported(const c2s_conv_desc* d) {
     return d && d->KH == 3 && d->KW == 3 && d->S == 1 && d->pad_y == 1 && d->pad_x == 1 && d->Hin % 2 == 0 && d->Win % 2 == 0 &&

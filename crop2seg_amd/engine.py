@@ -8,7 +8,7 @@ tracing, no autograd graph, stream-ordered launches only (hipGraph-capturable).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -51,6 +51,30 @@ def _side_stream():
     return _SIDE
 
 
+class PackRecord(NamedTuple):
+    """One weight pack of a step, as c2s_pack_job_fill takes it (the field order is the positional record's of earlier
+    versions: callers that index it keep working)."""
+    src_ptr: int
+    cin: int
+    cout: int
+    coutP: int
+    ntaps: int
+    so: int
+    sc: int
+    kind: int
+    taps: Tuple[int, ...]
+    nfloats: int
+
+
+# pack kind -> (output-channel padding, packed-size export, pack export): 0 wpk[tap][cin][coutP]; 1 / 2 Winograd U of the
+# 4-wave / 8-wave 3x3 kernels; 3 / 4 F(2x2,2x2) U of the 4x4 stride-2 forward / data gradient (the layouts: pack.hip)
+PACK_KINDS = {0: (32, None, "c2s_pack_weights"),
+              1: (64, "c2s_winograd_packed_floats", "c2s_pack_weights_winograd"),
+              2: (64, "c2s_winograd16_packed_floats", "c2s_pack_weights_winograd16"),
+              3: (64, "c2s_s2wino_packed_floats", "c2s_pack_weights_s2wino"),
+              4: (64, "c2s_s2dgrad_packed_floats", "c2s_pack_weights_s2dgrad")}
+
+
 def _tap_array(offs: Sequence[int]):
     return (C.c_int * len(offs))(*offs)
 
@@ -66,7 +90,7 @@ class Workspace:
                 _lib.init_device(idx)              # one-time per device, before any launch or hipGraph capture
         self.bufs: Dict[str, Tensor] = {}
         # weight-pack plan: the jobs recorded during one step become a device table that later steps run in one launch
-        self.pack_record: Dict[Tuple, Tuple] = {}
+        self.pack_record: Dict[Tuple, PackRecord] = {}
         self.pack_plan: Optional[dict] = None
         self.reduce_jobs: List[Tuple] = []          # slice sums of the weight gradients recorded during this backward pass
         self.reduce_post: List[Tuple] = []          # accumulating slice sums (their slab tensors held): launched after the batch
@@ -83,12 +107,12 @@ class Workspace:
         table = torch.zeros(len(jobs) * rec_bytes, dtype=torch.uint8).pin_memory() if torch.cuda.is_available() else \
             torch.zeros(len(jobs) * rec_bytes, dtype=torch.uint8)
         outs, block = {}, 0
-        for i, (key, (src_ptr, cin, cout, coutP, ntaps, so, sc, wino, taps, nfloats)) in enumerate(jobs):
-            out = torch.empty(nfloats, device=self.device, dtype=torch.float32)
-            check(L_.c2s_pack_job_fill(table.data_ptr() + i * rec_bytes, src_ptr, out.data_ptr(), cin, cout, coutP, ntaps, so, sc,
-                                       wino, _tap_array(taps), block), "pack_job_fill")
-            block += L_.c2s_pack_job_blocks(cin, coutP, ntaps, wino)
-            outs[key] = (out, src_ptr)
+        for i, (key, r) in enumerate(jobs):
+            out = torch.empty(r.nfloats, device=self.device, dtype=torch.float32)
+            check(L_.c2s_pack_job_fill(table.data_ptr() + i * rec_bytes, r.src_ptr, out.data_ptr(), r.cin, r.cout, r.coutP,
+                                       r.ntaps, r.so, r.sc, r.kind, _tap_array(r.taps), block), "pack_job_fill")
+            block += L_.c2s_pack_job_blocks(r.cin, r.coutP, r.ntaps, r.kind)
+            outs[key] = (out, r.src_ptr)
         self.pack_plan = {"table": table.to(self.device), "njobs": len(jobs), "blocks": block, "outs": outs}
         self.pack_record = {}
 
@@ -312,22 +336,28 @@ class Ctx:
             self._plan_ran = True
         return hit[0]
 
-    def pack(self, key: Tuple, src: Tensor, src_off: int, cin: int, cout: int, ntaps: int, so: int, sc: int,
-             taps: Sequence[int]) -> Tuple[Tensor, int]:
-        """Pack (cached per forward) weights into [ntaps][cin][coutP]."""
+    def pack(self, key: Tuple, src: Tensor, src_off: int, cin: int, cout: int, so: int, sc: int, taps: Sequence[int],
+             kind: int = 0) -> Tuple[Tensor, int]:
+        """Weights packed in the layout `kind` (PACK_KINDS) and the padded output-channel count; cached per forward, taken
+        from the step's one-launch plan when it covers `key`, else packed alone and recorded for the next plan.  The filter
+        element (o, c, tap t) is src[src_off + o * so + c * sc + taps[t]]."""
+        step, floats_fn, pack_fn = PACK_KINDS[kind]
+        coutP = (cout + step - 1) // step * step
         hit = self._packed.get(key)
-        coutP = (cout + 31) // 32 * 32
         if hit is not None:
             return hit, coutP
         src_ptr = src.data_ptr() + 4 * src_off
-        wpk = self._planned(key, src_ptr)
-        if wpk is None:
-            wpk = torch.empty(ntaps * cin * coutP, device=self.device, dtype=torch.float32)
-            check(lib().c2s_pack_weights(src_ptr, wpk.data_ptr(), cin, cout, coutP, ntaps, so, sc, _tap_array(taps), _stream()),
-                  "pack_weights")
-            self.ws.pack_record[key] = (src_ptr, cin, cout, coutP, ntaps, so, sc, 0, tuple(taps), ntaps * cin * coutP)
-        self._packed[key] = wpk
-        return wpk, coutP
+        out = self._planned(key, src_ptr)
+        if out is None:
+            L_ = lib()
+            ntaps = len(taps)
+            nfl = ntaps * cin * coutP if kind == 0 else getattr(L_, floats_fn)(cin, coutP)
+            out = torch.empty(nfl, device=self.device, dtype=torch.float32)
+            lead = (src_ptr, out.data_ptr(), cin, cout, coutP) + ((ntaps,) if kind == 0 else ())
+            check(getattr(L_, pack_fn)(*lead, so, sc, _tap_array(taps), _stream()), pack_fn)
+            self.ws.pack_record[key] = PackRecord(src_ptr, cin, cout, coutP, ntaps, so, sc, kind, tuple(taps), nfl)
+        self._packed[key] = out
+        return out, coutP
 
 
 def _pack_bf16x3(ctx: "Ctx", key: Tuple, src: Tensor, src_off: int, cin: int, cout: int, so: int, sc: int,
@@ -343,26 +373,6 @@ def _pack_bf16x3(ctx: "Ctx", key: Tuple, src: Tensor, src_off: int, cin: int, co
                                         len(taps), so, sc, _tap_array(taps), _stream()), "pack_weights_bf16x3")
     ctx._packed[key] = (whi, wlo)
     return whi, wlo, coutP
-
-
-def _pack_winograd(ctx: "Ctx", key: Tuple, src: Tensor, src_off: int, cin: int, cout: int, so: int, sc: int,
-                   taps: Sequence[int], wide: bool = False) -> Tuple[Tensor, int]:
-    """U = G g Gt of every 3x3 filter, [16][cin][coutP] (cached per forward); `wide` = the layout of the 8-wave kernel
-    (conv_winograd16.hip: [cout block][chunk][8 c][4 xi][64 o][4 nu])."""
-    hit = ctx._packed.get(key)
-    coutP = (cout + 63) // 64 * 64
-    if hit is not None:
-        return hit, coutP
-    src_ptr = src.data_ptr() + 4 * src_off
-    upk = ctx._planned(key, src_ptr)
-    if upk is None:
-        nfl = (lib().c2s_winograd16_packed_floats if wide else lib().c2s_winograd_packed_floats)(cin, coutP)
-        upk = torch.empty(nfl, device=ctx.device, dtype=torch.float32)
-        fn = lib().c2s_pack_weights_winograd16 if wide else lib().c2s_pack_weights_winograd
-        check(fn(src_ptr, upk.data_ptr(), cin, cout, coutP, so, sc, _tap_array(taps), _stream()), "pack_weights_winograd")
-        ctx.ws.pack_record[key] = (src_ptr, cin, cout, coutP, 9, so, sc, 2 if wide else 1, tuple(taps), nfl)
-    ctx._packed[key] = upk
-    return upk, coutP
 
 
 def _use_winograd(K: int, S: int, pad: int, chans: Sequence[int], cout: int, H: int, W: int) -> bool:
@@ -479,7 +489,7 @@ def _parity_transpose(ctx: Ctx, key: Tuple, g: Tensor, Wsrc: Tensor, src_off: in
     kp = K // 2
     for py in range(2):
         for px in range(2):
-            wpk, CP = ctx.pack(key + ("par", py, px), Wsrc, src_off, cin, cout, kp * kp, so, sc, _parity_taps(K, pad, py, px))
+            wpk, CP = ctx.pack(key + ("par", py, px), Wsrc, src_off, cin, cout, so, sc, _parity_taps(K, pad, py, px))
             d = ConvDesc(N, cin, 0, H, Wd, cout, CP, H, Wd, 2 * H, 2 * Wd, kp, kp, 1, pad // 2, pad // 2, _lib.PAD_ZEROS,
                          2, 2, py, px, accumulate, 2 if radj else 0)
             _igemm(d, g, None, wpk, bias, out, valid)
@@ -560,7 +570,7 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
     out = torch.empty(N, Cout, Ho, Wo, device=s0.device, dtype=torch.float32)
     if _use_winograd(K, S, pad, [C0, C1] if C1 else [C0], Cout, Hin, Win):
         wide = _wide_winograd(Hin, Win, [C0, C1] if C1 else [C0]) and N <= 65536
-        upk, CoutP = _pack_winograd(ctx, (wname, "fwd", "wino"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)), wide)
+        upk, CoutP = ctx.pack((wname, "fwd", "wino"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)), kind=2 if wide else 1)
         d = ConvDesc(N, C0, C1, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
         _winograd(d, s0, s1, upk, ctx.p[bname] if bname else None, out, valid, wide)
     elif _use_bf16x3(K, S, pad, [C0, C1]):
@@ -571,23 +581,12 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
               "conv3x3_bf16x3")
     elif (S2WINO and CONV_MODE == "f32" and K == 4 and S == 2 and C1 == 0 and lib().c2s_conv4x4s2_winograd_supported(C.byref(
             ConvDesc(N, C0, 0, Hin, Win, Cout, (Cout + 63) // 64 * 64, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)))):
-        CoutP = (Cout + 63) // 64 * 64
-        key = (wname, "fwd", "s2w")
-        upk = ctx._packed.get(key)
-        if upk is None:
-            upk = ctx._planned(key, W.data_ptr())
-            if upk is None:
-                nfl = lib().c2s_s2wino_packed_floats(Cin, CoutP)
-                upk = torch.empty(nfl, device=ctx.device, dtype=torch.float32)
-                check(lib().c2s_pack_weights_s2wino(W.data_ptr(), upk.data_ptr(), Cin, Cout, CoutP, Cin * KK, KK,
-                                                    _tap_array(list(range(KK))), _stream()), "pack_weights_s2wino")
-                ctx.ws.pack_record[key] = (W.data_ptr(), Cin, Cout, CoutP, 16, Cin * KK, KK, 3, tuple(range(KK)), nfl)
-            ctx._packed[key] = upk
+        upk, CoutP = ctx.pack((wname, "fwd", "s2w"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)), kind=3)
         d = ConvDesc(N, C0, 0, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
         check(lib().c2s_conv4x4s2_winograd(C.byref(d), s0.data_ptr(), upk.data_ptr(), _ptr(ctx.p[bname] if bname else None),
                                            out.data_ptr(), _ptr(valid), _stream()), "conv4x4s2_winograd")
     else:
-        wpk, CoutP = ctx.pack((wname, "fwd"), W, 0, Cin, Cout, KK, Cin * KK, KK, list(range(KK)))
+        wpk, CoutP = ctx.pack((wname, "fwd"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)))
         d = ConvDesc(N, C0, C1, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
         if lib().c2s_conv3x3_smallcin_supported(C.byref(d)):      # the first layer
             check(lib().c2s_conv3x3_smallcin(C.byref(d), s0.data_ptr(), wpk.data_ptr(), _ptr(ctx.p[bname] if bname else None),
@@ -618,7 +617,8 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
                 taps = [(K - 1 - ky) * K + (K - 1 - kx) for ky in range(K) for kx in range(K)]
                 if _use_winograd(K, S, pad, [Cout], Cs, Hin, Win):
                     wide = _wide_winograd(Hin, Win, [Cout]) and N <= 65536
-                    upk, CP = _pack_winograd(ctx, (wname, "dgrad", "wino", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, taps, wide)
+                    upk, CP = ctx.pack((wname, "dgrad", "wino", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, taps,
+                                       kind=2 if wide else 1)
                     dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Hin, Win, Hin, Win, K, K, 1, 1, 1, _lib.PAD_ZEROS, 1, 1, 0, 0,
                                   accf, radj)
                     _winograd(dd, g, None, upk, None, gin, valid, wide)
@@ -629,7 +629,7 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
                     check(lib().c2s_conv3x3_bf16x3(C.byref(dd), g.data_ptr(), None, whi.data_ptr(), wlo.data_ptr(), None,
                                                    gin.data_ptr(), _ptr(valid), _stream()), "conv3x3_bf16x3")
                 else:
-                    wd, CP = ctx.pack((wname, "dgrad", si), W, c_lo * KK, Cout, Cs, KK, KK, Cin * KK, taps)
+                    wd, CP = ctx.pack((wname, "dgrad", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, taps)
                     dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Hin, Win, Hin, Win, K, K, 1, K - 1 - pad, K - 1 - pad,
                                   _lib.PAD_ZEROS, 1, 1, 0, 0, accf, radj)
                     _igemm(dd, g, None, wd, None, gin, valid)
@@ -643,30 +643,16 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
                 CsP = (Cs + 63) // 64 * 64
                 dw = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CsP, Hin, Win, Hin, Win, 4, 4, 2, 1, 1, _lib.PAD_ZEROS, 1, 1, 0, 0, accf, radj)
                 if S2WINO and CONV_MODE == "f32" and lib().c2s_conv4x4s2_dgrad_winograd_supported(C.byref(dw)):
-                    key = (wname, "dgrad", "s2d", si)
-                    upk = ctx._packed.get(key)
-                    if upk is None:
-                        src_ptr = W.data_ptr() + 4 * c_lo * KK
-                        upk = ctx._planned(key, src_ptr)
-                        if upk is None:
-                            nfl = lib().c2s_s2dgrad_packed_floats(Cout, CsP)
-                            upk = torch.empty(nfl, device=ctx.device, dtype=torch.float32)
-                            check(lib().c2s_pack_weights_s2dgrad(src_ptr, upk.data_ptr(), Cout, Cs, CsP, KK, Cin * KK,
-                                                                 _tap_array(list(range(KK))), _stream()), "pack_weights_s2dgrad")
-                            # (pack-plan record: cin = gy channels, cout = input channels, strides as passed to the pack)
-                            ctx.ws.pack_record[key] = (src_ptr, Cout, Cs, CsP, 16, KK, Cin * KK, 4, tuple(range(KK)), nfl)
-                        ctx._packed[key] = upk
+                    # (cin = gy channels, cout = input channels of this source)
+                    upk, _ = ctx.pack((wname, "dgrad", "s2d", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, list(range(KK)), kind=4)
                     check(lib().c2s_conv4x4s2_dgrad_winograd(C.byref(dw), g.data_ptr(), upk.data_ptr(), gin.data_ptr(), _ptr(valid),
                                                              _stream()), "conv4x4s2_dgrad_winograd")
-                    if existing is None:
-                        tape.grads[src.data_ptr()] = gin
-                    c_lo += Cs
-                    continue
-                for py in range(2):         # one launch per output-row parity, both column parities fused
-                    wd, CP = ctx.pack((wname, "dgrad", si, py), W, c_lo * KK, Cout, Cs, 8, KK, Cin * KK, _xpair_taps(py))
-                    dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Ho, Wo, Hin, Win, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS,
-                                  2, 2, py, 0, accf, radj)
-                    _xpair(dd, g, wd, None, gin, valid)
+                else:
+                    for py in range(2):         # one launch per output-row parity, both column parities fused
+                        wd, CP = ctx.pack((wname, "dgrad", si, py), W, c_lo * KK, Cout, Cs, KK, Cin * KK, _xpair_taps(py))
+                        dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Ho, Wo, Hin, Win, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS,
+                                      2, 2, py, 0, accf, radj)
+                        _xpair(dd, g, wd, None, gin, valid)
             if existing is None:
                 tape.grads[src.data_ptr()] = gin
             c_lo += Cs
@@ -687,7 +673,7 @@ def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str, K: int = 4, pa
     bias = ctx.p[bname]
     if K == 4:
         for py in range(2):
-            wpk, CP = ctx.pack((wname, "fwd", py), Wt, 0, Cin, Cout, 8, 16, Cout * 16, _xpair_taps(py))
+            wpk, CP = ctx.pack((wname, "fwd", py), Wt, 0, Cin, Cout, 16, Cout * 16, _xpair_taps(py))
             d = ConvDesc(N, Cin, 0, H, Wd, Cout, CP, H, Wd, 2 * H, 2 * Wd, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS, 2, 2, py, 0, 0)
             _xpair(d, x, wpk, bias, out, None)
     else:
@@ -706,7 +692,7 @@ def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str, K: int = 4, pa
         _wgrad(ctx, [g], x, Cin, H, Wd, K, 2, pad, _lib.PAD_ZEROS, gw, Cout * KK, KK, list(range(KK)), acc, None)
         existing = tape.grad_of(x)
         gin = existing if existing is not None else torch.empty_like(x)
-        wd, CP = ctx.pack((wname, "dgrad"), Wt, 0, Cout, Cin, KK, Cout * KK, KK, list(range(KK)))
+        wd, CP = ctx.pack((wname, "dgrad"), Wt, 0, Cout, Cin, Cout * KK, KK, list(range(KK)))
         dd = ConvDesc(N, Cout, 0, 2 * H, 2 * Wd, Cin, CP, H, Wd, H, Wd, K, K, 2, pad, pad, _lib.PAD_ZEROS, 1, 1, 0, 0,
                       1 if existing is not None else 0)
         _igemm(dd, g, None, wd, None, gin, None)
@@ -751,7 +737,8 @@ def depthwise_conv2d(ctx: Ctx, x: Tensor, wname: str, K: int, S: int, pad: int, 
                 check(lib().c2s_add_inplace(gw.data_ptr(), tgt.data_ptr(), tgt.numel(), _stream()), "add_inplace")
 
         if _side_ok():
-            tape.defer(wgrad, [x, g, tgt])              # side stream, next to the data-gradient chain
+            tape.defer(wgrad, [x, g, tgt, part])        # side stream, next to the data-gradient chain (part: a later, larger
+                                                        # request replaces the workspace buffer before this launch ends)
         else:
             wgrad()
         existing = tape.grad_of(x)                      # e.g. the residual branch of the block: accumulate in the kernel

@@ -94,6 +94,27 @@ def test_winograd_family_predicates_without_gpu():
     assert L.c2s_s2wino_packed_floats(64, 64) == 32 * 2 * 4 * 64 * 12 and L.c2s_s2dgrad_packed_floats(64, 64) == 4 * 64 * 64 * 12
     assert L.c2s_winograd16_packed_floats(64, 64) == 8 * 8 * 64 * 16       # 16 points per (c, o): no padding since round 4
 
+    # the pack plan's job table takes the layouts' own preconditions, and sizes each job like the single packs
+    rec = ctypes.create_string_buffer(L.c2s_pack_job_bytes())
+    taps = (ctypes.c_int * 16)(*range(16))
+
+    def fill(kind, cin, cout, coutP, ntaps):
+        return L.c2s_pack_job_fill(rec, 16, 16, cin, cout, coutP, ntaps, 16, 1, kind, taps, 0)
+
+    assert fill(4, 24, 10, 64, 16) == 0
+    assert fill(4, 20, 10, 64, 16) == -1                                   # gy channels not a multiple of 8: would write past
+    for kind, ntaps in ((1, 9), (2, 9), (3, 16), (4, 16)):
+        assert fill(kind, 16, 40, 64, ntaps) == 0
+        assert fill(kind, 16, 40, 96, ntaps) == -1                         # CoutP a multiple of 32 only
+    assert fill(0, 16, 40, 96, 16) == 0 and fill(0, 16, 40, 80, 16) == -1
+    floats = {1: L.c2s_winograd_packed_floats, 2: L.c2s_winograd16_packed_floats, 3: L.c2s_s2wino_packed_floats,
+              4: L.c2s_s2dgrad_packed_floats}
+    per_thread = {1: 16, 2: 16, 3: 12, 4: 12}                              # floats one pack thread writes
+    for kind, cin, coutP in ((1, 13, 128), (2, 40, 64), (3, 7, 192), (4, 24, 64), (4, 72, 128)):
+        blocks = L.c2s_pack_job_blocks(cin, coutP, 16, kind)
+        assert (blocks - 1) * 256 * per_thread[kind] < floats[kind](cin, coutP) <= blocks * 256 * per_thread[kind]
+    assert L.c2s_pack_job_blocks(13, 64, 36, 0) == -(-36 * 13 * 64 // 256)
+
 
 @pytest.mark.parametrize("name", ["utae_eval_pad_wi", "timeunet_eval_pad_wi", "wtae_eval_pad_wi"])
 def test_state_dict_layout_matches_reference(goldens, name):

@@ -800,13 +800,19 @@ def test_conv3x3_bf16x3_fwd_bwd(case):
 
 def test_pack_plan_matches_individual_packs():
     """From the second step on all weight packs (tap-major and Winograd) run as one launch from a job table built during
-    the first step: the convolution results must be bit-identical to the individually packed ones."""
+    the first step: the convolution results must be bit-identical to the individually packed ones.  The layers cover
+    every pack layout: tap-major (the direct 4x4 stride-2 forward and its x-pair data gradient), both Winograd 3x3 kernels
+    (planes of 32 and 16) and the F(2x2,2x2) forward and data gradient of a 4x4 stride-2 layer on a 64x64 input."""
     E, L = _engine()
     g = torch.Generator().manual_seed(23)
     dev = torch.device("cuda")
     params = {"w3": (torch.randn(64, 64, 3, 3, generator=g) / 24).to(dev), "b3": torch.randn(64, generator=g).to(dev),
-              "w4": (torch.randn(64, 64, 4, 4, generator=g) / 32).to(dev), "b4": torch.randn(64, generator=g).to(dev)}
+              "w4": (torch.randn(64, 64, 4, 4, generator=g) / 32).to(dev), "b4": torch.randn(64, generator=g).to(dev),
+              "w5": (torch.randn(64, 16, 4, 4, generator=g) / 16).to(dev), "b5": torch.randn(64, generator=g).to(dev),
+              "w6": (torch.randn(64, 64, 3, 3, generator=g) / 24).to(dev), "b6": torch.randn(64, generator=g).to(dev)}
     x = torch.randn(2, 64, 32, 32, generator=g).to(dev)
+    x5 = torch.randn(2, 16, 64, 64, generator=g).to(dev)
+    x6 = torch.randn(2, 64, 16, 16, generator=g).to(dev)
     ws = E.Workspace(dev)
 
     def run():
@@ -814,17 +820,70 @@ def test_pack_plan_matches_individual_packs():
         ctx = E.Ctx(params, {}, grads, ws, True, E.Tape())
         y3 = E.conv2d(ctx, [x], "w3", "b3", 3, 1, 1, L.PAD_REFLECT, None)          # Winograd forward + data gradient packs
         y4 = E.conv2d(ctx, [y3], "w4", "b4", 4, 2, 1, L.PAD_REFLECT, None)         # direct forward, transposed data gradient packs
-        ctx.tape.grads[y4.data_ptr()] = torch.ones_like(y4)
+        y5 = E.conv2d(ctx, [x5], "w5", "b5", 4, 2, 1, L.PAD_REFLECT, None)         # F(2x2,2x2) forward + data gradient packs
+        y6 = E.conv2d(ctx, [x6], "w6", "b6", 3, 1, 1, L.PAD_REFLECT, None)         # 4-wave Winograd packs
+        for y in (y4, y5, y6):
+            ctx.tape.grads[y.data_ptr()] = torch.ones_like(y)
         ctx.tape.backward()
-        return y3.clone(), y4.clone(), ctx.tape.grads[x.data_ptr()].clone(), grads["w3"].clone(), grads["w4"].clone()
+        return (y3.clone(), y4.clone(), y5.clone(), y6.clone(), *(ctx.tape.grads[t.data_ptr()].clone() for t in (x, x5, x6)),
+                *(grads[w].clone() for w in ("w3", "w4", "w5", "w6")))
 
     first = run()
-    assert ws.pack_plan is None and len(ws.pack_record) >= 4
+    assert ws.pack_plan is None and {r.kind for r in ws.pack_record.values()} == {0, 1, 2, 3, 4}
     ws.finalize_pack_plan()
-    assert ws.pack_plan is not None and ws.pack_plan["njobs"] >= 4
+    assert ws.pack_plan is not None and ws.pack_plan["njobs"] >= 8
     second = run()
     for a, b in zip(first, second):
         assert torch.equal(a, b)
+
+
+def test_single_and_batched_packs_are_identical():
+    """Each pack layout written by its single-pack export and by one c2s_pack_batch table of all jobs: the same bits,
+    padding included, into NaN-filled buffers.  Ragged channel counts, flipped data-gradient taps, the second source of a
+    concatenation (a non-zero source offset) and 36 taps."""
+    E, L = _engine()
+    lib = L.lib()
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(29)
+    flip9 = [8 - t for t in range(9)]
+    # (kind, weight shape [A, B, K, K], first channel of the source, data gradient (flipped roles), taps)
+    cases = [(0, (37, 13, 3, 3), 0, False, list(range(9))), (0, (37, 20, 3, 3), 8, True, flip9),
+             (0, (70, 5, 6, 6), 0, False, list(range(36))), (0, (40, 24, 4, 4), 16, True, E._xpair_taps(1))]
+    for kind in (1, 2):
+        cases += [(kind, (70, 13, 3, 3), 0, False, list(range(9))), (kind, (40, 24, 3, 3), 16, True, flip9)]
+    cases += [(3, (70, 7, 4, 4), 0, False, list(range(16))), (3, (40, 24, 4, 4), 8, False, list(range(16))),
+              (4, (24, 30, 4, 4), 0, True, list(range(16))), (4, (72, 30, 4, 4), 10, True, list(range(16)))]
+    exports = {0: lib.c2s_pack_weights, 1: lib.c2s_pack_weights_winograd, 2: lib.c2s_pack_weights_winograd16,
+               3: lib.c2s_pack_weights_s2wino, 4: lib.c2s_pack_weights_s2dgrad}
+    floats = {1: lib.c2s_winograd_packed_floats, 2: lib.c2s_winograd16_packed_floats, 3: lib.c2s_s2wino_packed_floats,
+              4: lib.c2s_s2dgrad_packed_floats}
+    rec_bytes = lib.c2s_pack_job_bytes()
+    table = torch.zeros(len(cases) * rec_bytes, dtype=torch.uint8)
+    keep, singles, batched, block = [], [], [], 0
+    for i, (kind, shape, c_lo, dgrad, taps) in enumerate(cases):
+        A, B, K, _ = shape
+        KK = K * K
+        w = torch.randn(shape, generator=g).to(dev)
+        keep.append(w)
+        cin, cout, so, sc = (A, B - c_lo, KK, B * KK) if dgrad else (B - c_lo, A, B * KK, KK)
+        coutP = (cout + 31) // 32 * 32 if kind == 0 else (cout + 63) // 64 * 64
+        nfl = len(taps) * cin * coutP if kind == 0 else floats[kind](cin, coutP)
+        src = w.data_ptr() + 4 * c_lo * KK
+        one = torch.full((nfl,), float("nan"), device=dev)
+        lead = (src, one.data_ptr(), cin, cout, coutP) + ((len(taps),) if kind == 0 else ())
+        L.check(exports[kind](*lead, so, sc, E._tap_array(taps), E._stream()), "pack")
+        many = torch.full((nfl,), float("nan"), device=dev)
+        L.check(lib.c2s_pack_job_fill(table.data_ptr() + i * rec_bytes, src, many.data_ptr(), cin, cout, coutP, len(taps), so,
+                                      sc, kind, E._tap_array(taps), block), "pack_job_fill")
+        block += lib.c2s_pack_job_blocks(cin, coutP, len(taps), kind)
+        singles.append(one)
+        batched.append(many)
+    table = table.to(dev)
+    L.check(lib.c2s_pack_batch(table.data_ptr(), len(cases), block, E._stream()), "pack_batch")
+    torch.cuda.synchronize()
+    for case, one, many in zip(cases, singles, batched):
+        assert not torch.isnan(one).any() and not torch.isnan(many).any(), case
+        assert torch.equal(one, many), case
 
 
 @pytest.mark.parametrize("shape,use_valid", [((4, 64, 32, 32), True), ((3, 128, 8, 8), False), ((2, 64, 128, 128), True),
