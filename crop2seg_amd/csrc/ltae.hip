@@ -3458,6 +3458,26 @@ extern "C" int c2s_ltae_attn_optional(const c2s_ltae_desc* d) {
     return d && check(d) == C2S_OK && d->keep == nullptr && use_reg_bwd(d, true) ? 1 : 0;
 }
 
+// Which kernels c2s_ltae_attn_fwd_ws (called with a workspace and attn_pre) and c2s_ltae_attn_bwd launch for this descriptor.
+// *fwd: 0 = 16-pixel LDS kernel, 1 = three-pass streaming, 2 = register-resident, 3 = LDS-resident 4-pixel.
+// *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>, 2 = streaming heads + gx64, 3 = register-resident heads<false> +
+// gx64, 4 = register-resident heads<true> + gx64 (attn == NULL: d->keep_bits set, RNG mask), 5 = LDS-resident 4-pixel.
+// with_emb: whether the backward gets g_emb.  Pure query; returns C2S_EINVAL for a bad descriptor.
+extern "C" int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd) {
+    if (int rc = check(d)) return rc;
+    C2S_REQUIRE(fwd && bwd, "ltae_paths: null pointer");
+    *fwd = use_reg_fwd(d) ? 2 : (use_stream(d) ? 1 : (use_lds_fwd(d) ? 3 : 0));
+    const bool emb = with_emb != 0;
+    if (emb && use_stream(d)) {
+        static const bool gx64 = [] { const char* e = getenv("C2S_LTAE_GX64"); return !(e && e[0] == '0'); }();
+        if (use_reg_bwd(d, true)) *bwd = d->keep_bits != nullptr && d->keep == nullptr ? 4 : 3;
+        else *bwd = gx64 && d->C == 64 && d->HW % 64 == 0 ? 2 : 1;
+    } else {
+        *bwd = use_lds_bwd(d) ? 5 : 0;
+    }
+    return C2S_OK;
+}
+
 extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, const float* gamma, const float* beta,
                                     const float* U, const float* s0, const float* Wc, const float* bc, const float* pe,
                                     const int* valid, float* attn, float* attn_pre, float* emb, float* stats,

@@ -1059,6 +1059,8 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
     if ctx.tape is None:
         return emb, attn
     tape = ctx.tape
+    if d.keep is not None:              # the backward kernels read the explicit keep mask through the descriptor's raw pointer
+        tape.track(keep)
     if attn is not None:
         tape.track(attn)
     if emb is not None:
@@ -1075,8 +1077,19 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         gs0 = torch.empty(B, T, n_head, device=dev)
         gWc = torch.empty(d_model, Cc, device=dev)
         gbc = torch.empty(d_model, device=dev)
-        ggam, _ = ctx.grad_sink(prefix + ".in_norm.weight")
-        gbet, _ = ctx.grad_sink(prefix + ".in_norm.bias")
+        # the kernels overwrite these outputs: a sink that already holds a gradient gets a scratch tensor, added afterwards
+        pending = []
+
+        def sink(name):
+            dst, acc = ctx.grad_sink(name)
+            if not acc:
+                return dst
+            tmp = torch.empty_like(dst)
+            pending.append((dst, tmp))
+            return tmp
+
+        ggam = sink(prefix + ".in_norm.weight")
+        gbet = sink(prefix + ".in_norm.bias")
         nws = lib().c2s_ltae_bwd_workspace_floats(C.byref(d))
         ws = ctx.ws.get("ltae", nws)
         if mode != 0 and g_emb is not None:          # the positional part of the values: g_a += <g_emb_h, pe_h>
@@ -1102,17 +1115,19 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
                                       _stream()), "ltae_fold_bwd")
         if mode != 0:
             g_pe = torch.empty(B, T, d_model, device=dev, dtype=torch.float32)
-            gW, _ = ctx.grad_sink(enc + ".weight")
-            gb, _ = ctx.grad_sink(enc + ".bias")
+            gW = sink(enc + ".weight")
+            gb = sink(enc + ".bias")
             check(lib().c2s_ltae_pe_bwd(kmode, d0.data_ptr(), _ptr(d1), Q.data_ptr(), Wk.data_ptr(), qwk.data_ptr(),
                                         pe256.data_ptr(), _ptr(sin256), attn.data_ptr(), _ptr(g_emb), gs0.data_ptr(),
                                         g_pe.data_ptr(), sinks[1][0].data_ptr(), sinks[0][0].data_ptr(), gW.data_ptr(),
                                         gb.data_ptr(), B, T, HW, _stream()), "ltae_pe_bwd")
             if enc2 is not None:
-                gW2, _ = ctx.grad_sink(enc2 + ".weight")
-                gb2, _ = ctx.grad_sink(enc2 + ".bias")
+                gW2 = sink(enc2 + ".weight")
+                gb2 = sink(enc2 + ".bias")
                 check(lib().c2s_ltae_pe_abs_bwd(d1.data_ptr(), g_pe.data_ptr(), gW2.data_ptr(), gb2.data_ptr(), B * T, _stream()),
                       "ltae_pe_abs_bwd")
+        for dst, tmp in pending:
+            check(lib().c2s_add_inplace(dst.data_ptr(), tmp.data_ptr(), tmp.numel(), _stream()), "add_inplace")
         tape.add_grad(x5, gx)
 
     tape.record(bwd)

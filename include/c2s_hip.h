@@ -390,6 +390,12 @@ int c2s_ltae_fwd_path(const c2s_ltae_desc* d);
  * write) and the backward reads those (as many floats less to read).  Needs d->keep_bits on both calls, the RNG mask
  * (d->keep == NULL) and the embedding output. */
 int c2s_ltae_attn_optional(const c2s_ltae_desc* d);
+/* Which kernel families c2s_ltae_attn_fwd_ws (with a workspace and attn_pre) and c2s_ltae_attn_bwd (g_emb given iff with_emb)
+ * launch for this descriptor on the current device; a pure query.  *fwd: 0 = 16-pixel LDS kernel, 1 = three-pass streaming,
+ * 2 = register-resident, 3 = LDS-resident 4-pixel.  *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>,
+ * 2 = streaming heads + gx64, 3 = register-resident heads + gx64, 4 = the same re-deriving the keep flags from d->keep_bits
+ * (attn == NULL), 5 = LDS-resident 4-pixel. */
+int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd);
 size_t c2s_ltae_bwd_workspace_floats(const c2s_ltae_desc* d);
 /* g_emb [B,256,hw] or NULL; g_attn [16,B,T,hw] or NULL.  Outputs (all overwritten): gx [B,T,C,hw],
  * gU [16,C], gs0 [B,T,16], gWc [256,C] (embedding path only), gbc [256], ggamma [C], gbeta [C]. */

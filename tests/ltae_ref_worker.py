@@ -1,0 +1,180 @@
+"""Child process of tests/test_ltae_reference_gpu.py: runs L-TAE rows against the float64 reference of tests/ltae_ref.py in a
+process whose environment selects the kernel families (the C2S_LTAE_* switches are read once per process).
+
+argv[1]: JSON list of rows.  Each row prints one line "ROW <json>" (families reached, worst ratio per output); the process
+prints LTAE_REF_OK <n> when every row passed."""
+import ctypes
+import json
+import math
+import os
+import sys
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402
+
+import conv_ref  # noqa: E402
+import ltae_ref as R  # noqa: E402
+
+FROB = {"attn": 2e-6, "emb": 1e-5}      # the forward bars of test_ops_gpu.py; gradients: its 1e-4
+ENC = {"enc": "te.positional_encoder.fc", "enc2": "te.positional_encoder_abs.fc"}
+
+
+def thr_scale(p):
+    thr = int(p * 65536.0 + 0.5)                 # float32 product in the kernel; exact for the p used here
+    return thr, 65536.0 / (65536.0 - thr)
+
+
+def inputs(row):
+    import test_ltae_reference as TR
+    B, T, C, h, w = row["B"], row["T"], row["C"], row["h"], row["w"]
+    pe_mode = row.get("pe", "rel")
+    g = torch.Generator().manual_seed(row.get("seed", 3))
+    sd = TR.state(C, pe_mode)
+    if row.get("kind") == "sharp":              # scores spanning about +-30
+        sd["te.attention_head.Q"] = sd["te.attention_head.Q"] * 6.0
+    x = torch.randn(B, T, C, h, w, generator=g)
+    if row.get("kind") == "offset":
+        x += 20.0
+    valid = torch.ones(B, T, dtype=torch.bool)
+    if row.get("pad") and T > 1:
+        valid[0, max(T - 3, 1):] = False        # trailing run; padded frames keep their random finite values
+        if B > 1:
+            valid[B - 1, 1:] = False            # a batch element with one valid frame
+    rel = (5 * torch.arange(T)[None] + torch.arange(B)[:, None]).long()
+    if pe_mode.startswith("abs_rel"):
+        dates = torch.stack([rel, (rel * 7 + 11) % 365], -1)
+    elif pe_mode == "doy":
+        dates = (rel * 3 + 2) % 365
+    else:
+        dates = rel
+    return sd, x, valid, dates, g
+
+
+def family(L, B, T, C, HW, p, with_emb, keep_bits=False):
+    d = L.LtaeDesc(B, T, C, HW, 16, 256, 1e-5, p, 0, None, None)
+    if keep_bits:
+        d.keep_bits = 8                          # any non-NULL pointer: the query only looks at it
+    f, b = ctypes.c_int(), ctypes.c_int()
+    assert L.lib().c2s_ltae_paths(ctypes.byref(d), int(with_emb), ctypes.byref(f), ctypes.byref(b)) == 0
+    return f.value, b.value
+
+
+def run_row(row, C_F):
+    from crop2seg_amd import _lib as L
+    from crop2seg_amd import engine as E
+    from test_ops_gpu import make_ctx
+    B, T, C, h, w = row["B"], row["T"], row["C"], row["h"], row["w"]
+    HW = h * w
+    with_emb, drop, p = row["emb"], row.get("drop", "keep"), row.get("p", 0.1)
+    pe_mode = row.get("pe", "rel")
+    need_attn = row.get("need_attn", True)
+    sd, x, valid, dates, g = inputs(row)
+    fam = family(L, B, T, C, HW, p, with_emb, keep_bits=not need_attn)
+    assert list(fam) == row["want"], (row, fam)
+    keep = (torch.rand(16, B * HW, T, generator=g) >= p).float() if drop == "keep" else None
+    g_emb = torch.randn(B, 256, HW, generator=g) if with_emb else None
+    g_attn = torch.randn(16, B, T, HW, generator=g) if need_attn else None
+    xd = x.cuda()
+
+    def run(need):
+        ctx = make_ctx(sd, training=True)
+        priors = {}
+        if row.get("acc"):                       # sinks that already hold a gradient: the block must add to them
+            names = ["te.attention_head.Q", "te.attention_head.fc1_k.weight", "te.attention_head.fc1_k.bias",
+                     "te.inconv.weight", "te.inconv.bias", "te.in_norm.weight", "te.in_norm.bias"]
+            names += [k for k in sd if ".positional_encoder" in k]
+            for k in names:
+                ctx.grad_sink(k)
+                priors[k] = torch.randn(ctx.g[k].shape, generator=g)
+                ctx.g[k].copy_(priors[k])
+        emb, attn = E.ltae_attention(ctx, xd, dates.cuda(), valid.int().view(-1).cuda(), "te", 16, 4, 256, 1000.0, p,
+                                     with_emb, row.get("rng_seed", 77), None if keep is None else keep.cuda(),
+                                     pe_mode=pe_mode, need_attn=need)
+        if emb is not None:
+            ctx.tape.grads[emb.data_ptr()] = g_emb.cuda()
+        if attn is not None and g_attn is not None:
+            ctx.tape.grads[attn.data_ptr()] = g_attn.view(attn.shape).cuda()
+        ctx.tape.backward()
+        torch.cuda.synchronize()
+        gx = ctx.tape.grads[xd.data_ptr()].cpu()
+        return (None if emb is None else emb.cpu()), (None if attn is None else attn.cpu()), gx, \
+            {k: v.cpu() for k, v in ctx.g.items()}, priors
+
+    emb, attn, gx, grads, priors = run(need_attn)
+    res = {"row": row.get("name"), "fwd": fam[0], "bwd": fam[1]}
+    if drop == "keep":
+        mask = (keep.view(16, B, HW, T).permute(0, 1, 3, 2) / (1.0 - p)).double()
+    else:
+        # the counter-hash mask, recovered: dropped <=> exactly 0 at a valid position (attn_pre > 0 there, asserted below)
+        a_src = attn
+        if a_src is None:                        # need_attn=False: the same seed with stored weights gives the mask
+            _, a_src, _, _, _ = run(True)
+        thr, scale = thr_scale(p)
+        a4 = a_src.view(16, B, T, HW)
+        mask = (a4 != 0).double() * scale
+        res["mask_crc"] = zlib.crc32(((a4 != 0) & valid[None, :, :, None]).numpy().tobytes())
+    if pe_mode == "rel":
+        pe, A_pe = R.sinusoid_table(dates)
+        pnames = {}
+    else:
+        pnames = {k: v for k, v in ENC.items() if v + ".weight" in sd}
+        pe, A_pe = R.pe_table(pe_mode, dates, {f"{k}.{s}": sd[f"{v}.{s}"] for k, v in pnames.items() for s in ("weight", "bias")})
+    pix = R.pixel_subset(B, HW, n_random=256, seed=row.get("seed", 3))
+    ref, A = R.ltae_ref(x.view(B, T, C, HW), valid, R.params_of(sd), pe, A_pe, mask, g_emb, g_attn, pixels=pix)
+    vmask = valid[pix // HW]                     # [N,T] valid frames of the subset pixels
+    if drop != "keep":
+        assert bool((ref["attn_pre"].permute(0, 2, 1)[vmask] > 0).all()), "attn_pre underflows at a valid frame"
+    b_idx, s_idx = pix // HW, pix % HW
+
+    def check(name, got, key, frob, prior=None):
+        r_, a_ = ref[key], A[key]
+        if prior is not None:
+            r_, a_ = r_ + prior.double(), a_ + prior.double().abs()
+        c = C_F[name]
+        res[name] = conv_ref.assert_within(f"{row.get('name')}: {name}", got, r_, a_, c, frob)
+
+    if attn is not None:
+        check("attn", attn.view(16, B, T, HW)[:, b_idx, :, s_idx], "attn", FROB["attn"])
+    if emb is not None:
+        check("emb", emb.view(B, 256, HW)[b_idx, :, s_idx], "emb", FROB["emb"])
+    check("gx", gx.view(B, T, C, HW)[b_idx, :, :, s_idx], "gx", 1e-4)
+    pr = lambda k: priors.get(k)              # noqa: E731
+    check("dgamma", grads["te.in_norm.weight"], "dgamma", 1e-4, pr("te.in_norm.weight"))
+    # without the embedding, beta and bc only shift every score of a head alike: their gradients are 0 up to rounding, like
+    # gbk always -- no Frobenius bar there, the per-element bound still holds
+    zero = math.inf if not with_emb else 1e-4
+    check("dbeta", grads["te.in_norm.bias"], "dbeta", zero, pr("te.in_norm.bias"))
+    check("gQ", grads["te.attention_head.Q"].view(16, 4), "gQ", 1e-4,
+          None if pr("te.attention_head.Q") is None else pr("te.attention_head.Q").view(16, 4))
+    check("gWk", grads["te.attention_head.fc1_k.weight"], "gWk", 1e-4, pr("te.attention_head.fc1_k.weight"))
+    check("gbk", grads["te.attention_head.fc1_k.bias"], "gbk", math.inf, pr("te.attention_head.fc1_k.bias"))
+    check("gWc", grads["te.inconv.weight"].view(256, C), "gWc", 1e-4,
+          None if pr("te.inconv.weight") is None else pr("te.inconv.weight").view(256, C))
+    check("gbc", grads["te.inconv.bias"], "gbc", zero, pr("te.inconv.bias"))
+    if pnames:
+        gp, Ap = R.pe_param_grads(pe_mode, dates, ref["gpe"], A["gpe"], {})
+        for k, v in gp.items():
+            full = ENC[k.split(".")[0]] + "." + k.split(".")[1]
+            prior = pr(full)
+            rv, av = v, Ap[k]
+            if prior is not None:
+                rv, av = rv + prior.double(), av + prior.double().abs()
+            res["pe_" + k] = conv_ref.assert_within(f"{row.get('name')}: {full}", grads[full], rv, av, C_F["pe"], 1e-4)
+    return res
+
+
+def main():
+    rows = json.loads(sys.argv[1])
+    C_F = json.loads(sys.argv[2])
+    for row in rows:
+        res = run_row(row, C_F)
+        print("ROW " + json.dumps(res), flush=True)
+    print("LTAE_REF_OK", len(rows), flush=True)
+
+
+if __name__ == "__main__":
+    main()

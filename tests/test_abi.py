@@ -235,3 +235,29 @@ def test_wgrad_winograd_launches_without_c2s_init():
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "abi_noinit_worker.py")], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0 and "ABI_NOINIT_OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
+def test_ltae_paths_query_without_gpu():
+    """c2s_ltae_paths: a pure host query of the L-TAE kernel families (no device: 256 CUs assumed by the dispatch)."""
+    from crop2seg_amd import _lib
+    L = _lib.lib()
+
+    def paths(B, T, C, HW, with_emb=1, keep_bits=False):
+        d = _lib.LtaeDesc(B, T, C, HW, 16, 256, 1e-5, 0.1, 0, None, None)
+        if keep_bits:
+            d.keep_bits = 8
+        f, b = ctypes.c_int(-1), ctypes.c_int(-1)
+        assert L.c2s_ltae_paths(ctypes.byref(d), with_emb, ctypes.byref(f), ctypes.byref(b)) == 0
+        return f.value, b.value
+
+    assert paths(2, 9, 64, 128 * 128) == (2, 3)
+    assert paths(2, 9, 64, 128 * 128, keep_bits=True) == (2, 4)
+    assert paths(2, 9, 64, 128 * 128, with_emb=0) == (2, 5)
+    assert paths(2, 7, 64, 132 * 132) == (2, 1)
+    assert paths(1, 13, 64, 180 * 182) == (1, 1)
+    assert paths(2, 39, 128, 64) == (3, 5)
+    assert paths(1, 48, 128, 16) == (3, 0)
+    assert paths(2, 39, 256, 16) == (0, 0)
+    d = _lib.LtaeDesc(2, 9, 48, 16, 16, 256, 1e-5, 0.0, 0, None, None)      # C not a multiple of 64
+    f, b = ctypes.c_int(), ctypes.c_int()
+    assert L.c2s_ltae_paths(ctypes.byref(d), 1, ctypes.byref(f), ctypes.byref(b)) == -1
