@@ -390,9 +390,15 @@ class _Backbone(nn.Module):
         H, W = input.shape[-2:]
         if H % 8 or W % 8 or H < 16 or W < 16:
             raise ValueError("H and W must be multiples of 8 and >= 16")
-        if input.shape[1] > 64:
-            raise NotImplementedError("crop2seg_amd: the L-TAE kernels hold a whole series per workgroup: at most 64 time steps "
-                                      f"(the dataset's longest series has 61, README.md:92); got T={input.shape[1]}")
+        B, T = input.shape[:2]
+        if T > 64:      # the time-chunked L-TAE kernels (csrc/ltae_long.hip)
+            c_ltae = self.spec.encoder_widths[0] if self.spec.model == "timeunet" else self.spec.encoder_widths[-1]
+            if c_ltae not in (64, 128, 256):
+                raise NotImplementedError("crop2seg_amd: series longer than 64 time steps run the L-TAE on 64, 128 or 256 input "
+                                          f"channels; got {c_ltae} channels at T={T}")
+            if self.spec.pe_mode != "rel" and 16 * B * T > 65535 and torch.is_grad_enabled():
+                raise NotImplementedError("crop2seg_amd: the backward of the learnable positional encoders takes 16*B*T <= 65535 "
+                                          f"(c2s_ltae_pe_gattn); got B={B}, T={T}")
         want = 3 if self.spec.pe_mode.startswith("abs_rel") else 2
         if batch_positions.dim() != want or (want == 3 and batch_positions.shape[-1] != 2):
             raise ValueError("batch_positions must be [B,T,2] (relative date, day of year) with use_abs_rel_enc, else [B,T]")

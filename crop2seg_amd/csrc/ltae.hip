@@ -15,6 +15,8 @@
 // fastest axis, so a workgroup owns 16 adjacent pixels and its 256 threads are (pixel, head|group)
 // pairs: lanes 0..15 of every 16-lane group read/write 64 contiguous bytes.
 #include "common.h"
+#include "ltae_drop.h"
+#include "ltae_long.h"
 
 #define C2S_AS1 __attribute__((address_space(1)))
 #define C2S_AS3 __attribute__((address_space(3)))
@@ -57,32 +59,8 @@ struct StreamBwd {
     float* gb64;     // [64-pixel tiles][C][2]  d gamma / d beta partials written by the dx kernel (NULL: the heads kernel wrote part_gb)
 };
 
-// Attention dropout (tae.py:837).  Explicit keep mask [16,P,T] (tests) or a counter-based RNG: ONE 32-bit avalanche hash per
-// pair of time steps (2u, 2u+1) of a (head, pixel) row, 16 bits per element -- drop probability round(p * 2^16) / 2^16 with the
-// matching scale, so E[keep * scale] = 1 exactly.  (Two full hashes per element cost 4 quarter-rate v_mul_lo_u32 each:
-// 6.6k of the 12k cycles the dropout + store phase of a 16-pixel tile took.)
-struct DropCtx {
-    uint32_t key, thr;
-    float inv;
-    int half_t;
-};
-__device__ __forceinline__ DropCtx drop_ctx(const LtaeParams& p) {
-    DropCtx d;
-    const uint64_t seed = p.seed + (p.seed_dev != nullptr ? *p.seed_dev * 0x9E3779B97F4A7C15ull : 0ull);
-    d.key = c2s_hash32((uint32_t)seed ^ c2s_hash32((uint32_t)(seed >> 32) + 0x9E3779B9u));
-    d.thr = (uint32_t)(p.drop_p * 65536.f + 0.5f);
-    d.inv = 65536.f / (65536.f - (float)d.thr);
-    d.half_t = (p.T + 1) >> 1;
-    return d;
-}
-__device__ __forceinline__ uint32_t drop_bits(const DropCtx& d, long row, int u) {
-    const uint64_t i2 = (uint64_t)row * (uint64_t)d.half_t + (uint64_t)u;
-    return c2s_hash32((uint32_t)i2 ^ d.key ^ (uint32_t)(i2 >> 32) * 0x85EBCA6Bu);
-}
-__device__ __forceinline__ float drop_pick(const DropCtx& d, uint32_t bits, int t) {
-    const uint32_t u16 = (t & 1) ? bits >> 16 : bits & 0xffffu;
-    return u16 >= d.thr ? d.inv : 0.f;
-}
+// Attention dropout (tae.py:837): ltae_drop.h.
+__device__ __forceinline__ DropCtx drop_ctx(const LtaeParams& p) { return drop_ctx_of(p.seed, p.seed_dev, p.drop_p, p.T); }
 __device__ __forceinline__ float keep_scale(const LtaeParams& p, int h, long P_total, long pidx, int t) {
     if (p.drop_p <= 0.f) return 1.f;
     if (p.keep != nullptr) return p.keep[((long)h * P_total + pidx) * p.T + t] != 0.f ? 1.f / (1.f - p.drop_p) : 0.f;
@@ -3366,15 +3344,34 @@ size_t bwd2_lds(const c2s_ltae_desc* d) {
     return (256 * PT + 2 * (size_t)d->T * NH * PT + (size_t)d->C * 4 * PT + NH * 4 * PT + (size_t)d->C * 8) * 4;
 }
 
+// Series longer than 64 steps, or every shape under C2S_LTAE_LONG=1 (A/B runs, tests), go to the time-chunked family of
+// ltae_long.hip; every other shape keeps the families below.
+bool use_long(const c2s_ltae_desc* d) {
+    static const bool forced = [] { const char* e = getenv("C2S_LTAE_LONG"); return e && e[0] == '1'; }();
+    return forced || d->T > 64;
+}
+
 int check(const c2s_ltae_desc* d) {
     C2S_REQUIRE(d && d->B > 0 && d->T > 0 && d->C > 0 && d->HW > 0, "ltae: bad shape");
     C2S_REQUIRE(d->n_head == NH && d->d_model == NH * DV, "ltae: only n_head=16, d_model=256 are built");
-    C2S_REQUIRE(d->C % NH == 0 && d->C / NH <= 16 && d->T <= 64, "ltae: C must be a multiple of 16 and <= 256, T <= 64");
-    C2S_REQUIRE(bwd1_lds(d) <= 160 * 1024 && bwd2_lds(d) <= 160 * 1024 && fwd_lds(d) <= 160 * 1024, "ltae: T*C too large for the LDS tile");
+    if (use_long(d)) {
+        C2S_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256, "ltae: the long-series kernels (T > 64) take C = 64, 128 or 256");
+        C2S_REQUIRE((long)d->B * ((d->HW + LONG_PX - 1) / LONG_PX) < (1L << 31), "ltae: too many pixel tiles");
+    } else {
+        C2S_REQUIRE(d->C % NH == 0 && d->C / NH <= 16 && d->T <= 64, "ltae: C must be a multiple of 16 and <= 256, T <= 64");
+        C2S_REQUIRE(bwd1_lds(d) <= 160 * 1024 && bwd2_lds(d) <= 160 * 1024 && fwd_lds(d) <= 160 * 1024, "ltae: T*C too large for the LDS tile");
+    }
     C2S_REQUIRE(d->C % 64 == 0, "ltae: C must be a multiple of 64");
     C2S_REQUIRE(d->HW % 4 == 0, "ltae: h*w must be a multiple of 4");
     C2S_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "ltae: bad dropout p");
     return C2S_OK;
+}
+
+LtaeLongArgs long_args(const c2s_ltae_desc* d) {
+    LtaeLongArgs a = {};
+    a.B = d->B; a.T = d->T; a.C = d->C; a.HW = d->HW; a.eps = d->eps; a.drop_p = d->dropout_p; a.seed = d->seed;
+    a.seed_dev = d->seed_dev; a.keep = d->keep;
+    return a;
 }
 
 void fill(LtaeParams& p, const c2s_ltae_desc* d) {
@@ -3434,11 +3431,12 @@ static bool use_reg_fwd(const c2s_ltae_desc* d) {
 }
 
 extern "C" int c2s_ltae_uses_streaming(const c2s_ltae_desc* d) {
-    return d && check(d) == C2S_OK && (use_stream(d) || use_reg_fwd(d)) ? 1 : 0;
+    return d && check(d) == C2S_OK && !use_long(d) && (use_stream(d) || use_reg_fwd(d)) ? 1 : 0;
 }
 
 extern "C" int c2s_ltae_fwd_path(const c2s_ltae_desc* d) {
     if (!d || check(d) != C2S_OK) return -1;
+    if (use_long(d)) return 4;
     return use_reg_fwd(d) ? 2 : (use_stream(d) ? 1 : 0);
 }
 
@@ -3455,17 +3453,23 @@ static bool use_reg_bwd(const c2s_ltae_desc* d, bool with_emb) {
 // 1 when a caller that never reads the post-dropout weights may pass attn == NULL to c2s_ltae_attn_fwd_ws AND to
 // c2s_ltae_attn_bwd (both take the register-resident kernels for this shape; RNG mask, embedding output)
 extern "C" int c2s_ltae_attn_optional(const c2s_ltae_desc* d) {
-    return d && check(d) == C2S_OK && d->keep == nullptr && use_reg_bwd(d, true) ? 1 : 0;
+    return d && check(d) == C2S_OK && !use_long(d) && d->keep == nullptr && use_reg_bwd(d, true) ? 1 : 0;
 }
 
 // Which kernels c2s_ltae_attn_fwd_ws (called with a workspace and attn_pre) and c2s_ltae_attn_bwd launch for this descriptor.
 // *fwd: 0 = 16-pixel LDS kernel, 1 = three-pass streaming, 2 = register-resident, 3 = LDS-resident 4-pixel.
 // *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>, 2 = streaming heads + gx64, 3 = register-resident heads<false> +
 // gx64, 4 = register-resident heads<true> + gx64 (attn == NULL: d->keep_bits set, RNG mask), 5 = LDS-resident 4-pixel.
+// Time-chunked family (ltae_long.hip: T > 64 or C2S_LTAE_LONG=1): *fwd = 4, *bwd = 6.
 // with_emb: whether the backward gets g_emb.  Pure query; returns C2S_EINVAL for a bad descriptor.
 extern "C" int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd) {
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(fwd && bwd, "ltae_paths: null pointer");
+    if (use_long(d)) {
+        *fwd = 4;
+        *bwd = 6;
+        return C2S_OK;
+    }
     *fwd = use_reg_fwd(d) ? 2 : (use_stream(d) ? 1 : (use_lds_fwd(d) ? 3 : 0));
     const bool emb = with_emb != 0;
     if (emb && use_stream(d)) {
@@ -3486,7 +3490,7 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
     C2S_REQUIRE(x && gamma && beta && U && s0 && stats, "ltae_fwd: null pointer");
     // attn == NULL: the caller never reads the post-dropout weights (TimeUNet without return_att); only the register-resident
     // forward skips the store; a later backward then needs attn_pre and the RNG mask (c2s_ltae_attn_optional)
-    C2S_REQUIRE(attn != nullptr || (use_reg_fwd(d) && emb != nullptr),
+    C2S_REQUIRE(attn != nullptr || (!use_long(d) && use_reg_fwd(d) && emb != nullptr),
                 "ltae_fwd: attn may only be NULL on the register-resident path (c2s_ltae_fwd_path == 2) with an embedding output");
     C2S_REQUIRE(emb == nullptr || (Wc && bc && pe), "ltae_fwd: embedding output needs Wc, bc, pe");
     LtaeParams p = {};
@@ -3494,6 +3498,12 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
     p.x = x; p.gamma = gamma; p.beta = beta; p.U = U; p.s0 = s0; p.Wc = Wc; p.bc = bc; p.pe = pe; p.valid = valid;
     p.attn = attn; p.attn_pre = attn_pre; p.emb = emb; p.stats = stats;
     hipStream_t st = (hipStream_t)stream;
+    if (use_long(d)) {
+        LtaeLongArgs a = long_args(d);
+        a.x = x; a.gamma = gamma; a.beta = beta; a.U = U; a.s0 = s0; a.Wc = Wc; a.bc = bc; a.pe = pe; a.valid = valid;
+        a.attn = attn; a.attn_pre = attn_pre; a.emb = emb; a.stats = stats;
+        return ltae_long_fwd(a, st);
+    }
     if (use_reg_fwd(d)) {
         const bool h32 = (unsigned long long)NH * d->B * d->HW * ((d->T + 1) / 2) <= 0xFFFFFFFFull;
         if (h32) hipLaunchKernelGGL(ltae_reg_fwd_kernel<true>, dim3(d->B * (d->HW / RPX)), dim3(512), R_FLOATS * sizeof(float), st, p);
@@ -3558,12 +3568,13 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
                 "ltae_bwd: null pointer");
     C2S_REQUIRE(ws_floats >= c2s_ltae_bwd_workspace_floats(d), "ltae_bwd: workspace too small");
     (void)s0; (void)valid;
-    const bool stream_path = g_emb != nullptr && use_stream(d);
-    const bool reg_heads = use_reg_bwd(d, g_emb != nullptr);
+    const bool long_path = use_long(d);
+    const bool stream_path = !long_path && g_emb != nullptr && use_stream(d);
+    const bool reg_heads = !long_path && use_reg_bwd(d, g_emb != nullptr);
     C2S_REQUIRE(attn != nullptr || (reg_heads && d->keep_bits != nullptr),
                 "ltae_bwd: attn may only be NULL where the forward could omit it (register-resident path) and left the keep flags in d->keep_bits");
-    const bool lds_path = !stream_path && use_lds_bwd(d);      // fused LDS-resident kernel on 4-pixel tiles (small maps)
-    const int PT = reg_heads ? RPX : (stream_path ? SPT : (lds_path ? 4 : bwd_pt(d)));
+    const bool lds_path = !long_path && !stream_path && use_lds_bwd(d);      // fused LDS-resident kernel on 4-pixel tiles (small maps)
+    const int PT = long_path ? LONG_PX : (reg_heads ? RPX : (stream_path ? SPT : (lds_path ? 4 : bwd_pt(d))));
     const size_t tiles = (size_t)d->B * ((d->HW + PT - 1) / PT);
     const size_t tiles_ws = (size_t)d->B * ((d->HW + 3) / 4);
     LtaeParams p = {};
@@ -3581,7 +3592,18 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
     hipStream_t st = (hipStream_t)stream;
     c2s_ensure_init();
     StreamBwd sb = {};
-    if (stream_path) {
+    if (long_path) {
+        // the V area of the workspace holds M [P][16][2], sum_t attn / sum_t gs [2][16][P] and part_U [tiles][16][C]
+        const size_t P = (size_t)d->B * d->HW;
+        LtaeLongArgs a = long_args(d);
+        a.x = x; a.gamma = gamma; a.beta = beta; a.U = U; a.Wc = Wc; a.bc = bc; a.pe = pe;
+        a.attn_in = attn; a.attn_pre_in = attn_pre; a.stats_in = stats; a.g_emb = g_emb; a.g_attn = g_attn; a.gx = gx;
+        a.GS = p.GS; a.Z = p.Z; a.part_s0 = p.part_s0; a.part_bc = p.part_bc; a.part_gb = p.part_gb;
+        a.M = sb.M = p.V;
+        a.ASG = p.V + P * NH * 2;
+        a.part_U = sb.part_U = a.ASG + 2 * NH * P;
+        if (int rc = ltae_long_bwd(a, st)) return rc;
+    } else if (stream_path) {
         // the V area of the workspace is not used by the streaming kernels: it holds M [P][16][2] and part_U [tiles][16][C]
         sb.M = p.V;
         sb.part_U = p.V + (size_t)d->B * d->HW * NH * 2;
@@ -3628,16 +3650,20 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
         reduce_rows(p.part_gb, ggamma, 1, gb_tiles, 2 * d->C, rtmp, st, gbeta);
         C2S_CHECK_LAUNCH("ltae_reduce_gb");
     }
-    if (stream_path || lds_path) {
+    if (stream_path || lds_path || long_path) {
         reduce_rows(sb.part_U, gU, 1, (int)tiles, NH * d->C, rtmp, st);
     } else {
         hipLaunchKernelGGL(sum_over_pixels_kernel, dim3(NH * d->C), dim3(64), 0, st, p.V, gU, d->B, NH * d->C, d->HW);
     }
     C2S_CHECK_LAUNCH("ltae_gU");
-    if (g_emb != nullptr && stream_path && d->HW % 64 == 0) {
+    const int wc_slices = d->HW % 64 == 0 ? (d->B * (d->HW / 64) >= 32 ? 32 : d->B * (d->HW / 64)) : 0;
+    const bool long_wc = long_path && d->C == 64 && d->HW % 64 == 0 &&      // the slice partials fit in the V area
+                         (size_t)NH * d->B * d->HW * 4 + tiles * NH * d->C + (size_t)wc_slices * 256 * d->C <=
+                             (size_t)d->B * NH * d->C * d->HW;
+    if (g_emb != nullptr && (stream_path || long_wc) && d->HW % 64 == 0) {
         // 32 pixel slices per head; the partials live behind part_U in the (unused) V area of the workspace
         const int ntiles = d->B * (d->HW / 64);
-        const int slices = ntiles >= 32 ? 32 : ntiles;
+        const int slices = wc_slices;
         const int tps = (ntiles + slices - 1) / slices;
         float* part_wc = sb.part_U + tiles * NH * d->C;
         hipLaunchKernelGGL(gwc_mfma_kernel, dim3(NH, slices), dim3(256), 0, st, g_emb, p.Z, part_wc, d->B, d->HW, tps);

@@ -1033,9 +1033,10 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         keep_bits = torch.empty(B * HW * n_head, device=x5.device, dtype=torch.int64)
         d.keep_bits = keep_bits.data_ptr()
         ctx.tape.track(keep_bits)
-    # softmax before dropout: saved for the backward (and the score scratch of the three-pass streaming kernels); a forward
+    # softmax before dropout: saved for the backward (and the score scratch of the three-pass streaming kernels and of the
+    # time-chunked ones, path 4); a forward
     # without a tape (inference) does not store it: 16*B*T*h*w floats less to write
-    need_pre = ctx.tape is not None or lib().c2s_ltae_fwd_path(C.byref(d)) == 1
+    need_pre = ctx.tape is not None or lib().c2s_ltae_fwd_path(C.byref(d)) in (1, 4)
     attn_pre = torch.empty(n_head, B, T, h, w, device=x5.device, dtype=torch.float32) if need_pre else None
     emb = torch.empty(B, d_model, h, w, device=x5.device, dtype=torch.float32) if with_embedding else None
     stats = torch.empty(B * HW * n_head * 2, device=x5.device, dtype=torch.float32)

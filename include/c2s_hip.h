@@ -381,7 +381,8 @@ int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, const float* ga
  * which path they cover. */
 int c2s_ltae_uses_streaming(const c2s_ltae_desc* d);
 /* Which forward kernel c2s_ltae_attn_fwd_ws launches for this shape: 0 = the 16-pixel LDS kernel (ltae_fwd_kernel: small maps),
- * 1 = the three-pass streaming kernels (ltae_prep + ltae_stream_fwd), 2 = the register-resident kernel (ltae_reg_fwd_kernel);
+ * 1 = the three-pass streaming kernels (ltae_prep + ltae_stream_fwd), 2 = the register-resident kernel (ltae_reg_fwd_kernel),
+ * 4 = the time-chunked kernels of T > 64 (ltae_long.hip; attn_pre is their score scratch);
  * -1 = bad descriptor.  (Measurement harnesses label their numbers with it.) */
 int c2s_ltae_fwd_path(const c2s_ltae_desc* d);
 /* 1 when a caller that never reads the post-dropout attention weights (TimeUNet_v1.forward without return_att,
@@ -394,7 +395,9 @@ int c2s_ltae_attn_optional(const c2s_ltae_desc* d);
  * launch for this descriptor on the current device; a pure query.  *fwd: 0 = 16-pixel LDS kernel, 1 = three-pass streaming,
  * 2 = register-resident, 3 = LDS-resident 4-pixel.  *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>,
  * 2 = streaming heads + gx64, 3 = register-resident heads + gx64, 4 = the same re-deriving the keep flags from d->keep_bits
- * (attn == NULL), 5 = LDS-resident 4-pixel. */
+ * (attn == NULL), 5 = LDS-resident 4-pixel.  Series longer than 64 steps (every shape when the environment sets
+ * C2S_LTAE_LONG=1) take the time-chunked family: *fwd = 4, *bwd = 6 (C = 64, 128 or 256; attn and attn_pre required, attn
+ * never optional). */
 int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd);
 size_t c2s_ltae_bwd_workspace_floats(const c2s_ltae_desc* d);
 /* g_emb [B,256,hw] or NULL; g_attn [16,B,T,hw] or NULL.  Outputs (all overwritten): gx [B,T,C,hw],
