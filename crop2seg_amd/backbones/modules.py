@@ -331,12 +331,17 @@ def _pack_outputs(out: "Fn.BackboneOutput"):
 
 
 class _BackboneFunction(torch.autograd.Function):
+    """Differentiable inputs: the parameters that require grad (`names`, in named_parameters order).  The frozen ones come in
+    `frozen` as plain tensors: the engine prunes their gradients and the launches that only they would need."""
+
     @staticmethod
-    def forward(ctx, module, x, dates, drop, names, *params):
-        p = dict(zip(names, params))
-        grads = {n: torch.empty_like(t) for n, t in p.items()}
+    def forward(ctx, module, x, dates, drop, names, frozen, *params):
+        p = dict(frozen)
+        p.update(zip(names, params))
+        grads = {n: torch.empty_like(t) for n, t in zip(names, params)}
         tape = E.Tape()
-        ectx = E.Ctx(p, dict(module.named_buffers()), grads, module._workspace(x.device), module.training, tape)
+        ectx = E.Ctx(p, dict(module.named_buffers()), grads, module._workspace(x.device), module.training, tape,
+                     trainable=names if frozen else None)
         with torch.no_grad():
             out = Fn.FORWARDS[module.spec.model](ectx, module.spec, x, dates, drop)
         diff = _pack_outputs(out)
@@ -360,7 +365,7 @@ class _BackboneFunction(torch.autograd.Function):
                 if n not in ectx._gwritten:
                     g.zero_()
                 out.append(g)
-        return (None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, *out)
 
 
 class _Backbone(nn.Module):
@@ -424,11 +429,12 @@ class _Backbone(nn.Module):
                 seeds = torch.randint(0, 2 ** 62, (2,), device="cpu")   # host RNG (torch.manual_seed reproducible)
                 drop.attn_seed, drop.mlp_seed = int(seeds[0]), int(seeds[1])
         named = [(n, p) for n, p in self.named_parameters()]
-        names = [n for n, _ in named]
-        params = [p for _, p in named]
         spec = self.spec
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            att, *diff = _BackboneFunction.apply(self, x, dates, drop, names, *params)
+        train = [(n, p) for n, p in named if p.requires_grad]
+        if torch.is_grad_enabled() and train:
+            # requires_grad is read here, at the forward: frozen parameters get no gradient and no launch of their own
+            frozen = {n: p.detach() for n, p in named if not p.requires_grad}
+            att, *diff = _BackboneFunction.apply(self, x, dates, drop, [n for n, _ in train], frozen, *[p for _, p in train])
         else:
             with torch.no_grad():
                 ectx = E.Ctx(dict(named), dict(self.named_buffers()), None, self._workspace(x.device), self.training, None)

@@ -55,8 +55,8 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const float* __restrict__ 
     for (int c = 0; c < CPG; ++c) op[(size_t)c * HW] = acc[c];
 }
 
-// gx = up(attn) * gout ;  gup[g,b,t,Y,X] = sum_{c in g} x * gout
-template <int CPG>
+// gx = up(attn) * gout ;  gup[g,b,t,Y,X] = sum_{c in g} x * gout.  GX = false: gup only, gx is neither read nor written
+template <int CPG, bool GX = true>
 __global__ __launch_bounds__(256) void agg_bwd_kernel(const float* __restrict__ x, const float* __restrict__ attn,
                                                       const int* __restrict__ valid, const float* __restrict__ gout,
                                                       float* __restrict__ gx, int gx_acc, float* __restrict__ gup,
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const float* __restrict__ 
         const size_t xo = (((size_t)b * d.T + t) * d.C + g * CPG) * HW + (size_t)Y * d.W + X;
         const size_t uo = ((size_t)(g * d.B + b) * d.T + t) * HW + (size_t)Y * d.W + X;
         if (valid != nullptr && valid[b * d.T + t] == 0) {
-            if (!gx_acc) {
+            if (GX && !gx_acc) {
 #pragma unroll
                 for (int c = 0; c < CPG; ++c) gx[xo + (size_t)c * HW] = 0.f;
             }
@@ -91,9 +91,13 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const float* __restrict__ 
         float s = 0.f;
 #pragma unroll
         for (int c = 0; c < CPG; ++c) {
-            s += x[xo + (size_t)c * HW] * go[c];
-            const float v = a * go[c];
-            if (gx_acc) gx[xo + (size_t)c * HW] += v; else gx[xo + (size_t)c * HW] = v;
+            if constexpr (GX) {
+                s += x[xo + (size_t)c * HW] * go[c];
+                const float v = a * go[c];
+                if (gx_acc) gx[xo + (size_t)c * HW] += v; else gx[xo + (size_t)c * HW] = v;
+            } else {
+                s = fmaf(x[xo + (size_t)c * HW], go[c], s);     // the contraction the form with gx compiles to
+            }
         }
         gup[uo] = s;
     }
@@ -222,19 +226,25 @@ extern "C" int c2s_temporal_aggregate_bwd(const c2s_agg_desc* d, const float* x,
                                           const float* gout, float* gx, int gx_accumulate, float* gattn,
                                           float* workspace, size_t ws_floats, void* stream) {
     if (int rc = check(d)) return rc;
-    C2S_REQUIRE(x && attn && gout && gx && gattn && workspace, "aggregate_bwd: null pointer");
+    // gx == NULL: only gattn (the input needs no gradient); gattn == NULL: only gx (the attention masks need none)
+    C2S_REQUIRE(x && attn && gout && (gx || gattn) && workspace, "aggregate_bwd: null pointer");
     C2S_REQUIRE(ws_floats >= c2s_temporal_aggregate_bwd_workspace_floats(d), "aggregate_bwd: workspace too small");
     const long total = (long)d->B * d->n_head * d->H * d->W;
     dim3 grid(cdiv(total, 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
+#define C2S_AGG_BWD(CPG_)                                                                                                    \
+    if (gx != nullptr) hipLaunchKernelGGL(agg_bwd_kernel<CPG_>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); \
+    else hipLaunchKernelGGL((agg_bwd_kernel<CPG_, false>), grid, block, 0, st, x, attn, valid, gout, gx, 0, workspace, *d);
     switch (d->C / d->n_head) {
-        case 1: hipLaunchKernelGGL(agg_bwd_kernel<1>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); break;
-        case 2: hipLaunchKernelGGL(agg_bwd_kernel<2>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); break;
-        case 4: hipLaunchKernelGGL(agg_bwd_kernel<4>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); break;
-        case 8: hipLaunchKernelGGL(agg_bwd_kernel<8>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); break;
-        default: hipLaunchKernelGGL(agg_bwd_kernel<16>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); break;
+        case 1: C2S_AGG_BWD(1) break;
+        case 2: C2S_AGG_BWD(2) break;
+        case 4: C2S_AGG_BWD(4) break;
+        case 8: C2S_AGG_BWD(8) break;
+        default: C2S_AGG_BWD(16) break;
     }
+#undef C2S_AGG_BWD
     C2S_CHECK_LAUNCH("aggregate_bwd");
+    if (gattn == nullptr) return C2S_OK;
     const long rows = (long)d->n_head * d->B * d->T * d->h;
     const int threads = d->W >= 256 ? 256 : (d->W > 64 ? 128 : 64);
     hipLaunchKernelGGL(agg_upsample_adjoint_kernel, dim3(rows), dim3(threads), (size_t)d->W * sizeof(float), st, workspace,

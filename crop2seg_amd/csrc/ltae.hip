@@ -685,6 +685,8 @@ __global__ __launch_bounds__(256) void ltae_bwd_heads_kernel(LtaeParams p) {
 // ------------------------------------------------------------------------------------------ backward, part 2
 // d xhat[t,c] = sum_h (attn[h,t] r[h,c] + gs[h,t] U[h,c]), then the per-pixel GroupNorm backward.
 // Streaming threads = (quad, slot): slot = (channel c = slot % 64 (+64), time half th = slot / 64).
+// GX = false (no input gradient): the d gamma / d beta partials only; p.gx is not touched.
+template <bool GX = true>
 __global__ __launch_bounds__(256) void ltae_bwd_gx_kernel(LtaeParams p) {
     constexpr int PT = BPT;
     extern __shared__ float lds[];
@@ -726,7 +728,7 @@ __global__ __launch_bounds__(256) void ltae_bwd_gx_kernel(LtaeParams p) {
     }
     __syncthreads();
     const float* xq = p.x + (size_t)b * T * C * HW + pixq;
-    float* gxq = p.gx + (size_t)b * T * C * HW + pixq;
+    float* gxq = GX ? p.gx + (size_t)b * T * C * HW + pixq : nullptr;
     const int th = slot >> 6;
     const int t_beg = th == 0 ? 0 : (T + 1) / 2, t_end = th == 0 ? (T + 1) / 2 : T;
     for (int c = slot & 63; c < C; c += 64) {
@@ -755,10 +757,12 @@ __global__ __launch_bounds__(256) void ltae_bwd_gx_kernel(LtaeParams p) {
             const f32x4 xn = (*reinterpret_cast<const f32x4*>(xq + (size_t)(t * C + c) * HW) - mean) * rstd;
             dg += gxh * xn;
             db += gxh;
-            const f32x4 dxn = gxh * gm;
-            m1 += dxn;
-            m2 += dxn * xn;
-            if (actq) *reinterpret_cast<f32x4*>(gxq + (size_t)(t * C + c) * HW) = dxn;
+            if constexpr (GX) {
+                const f32x4 dxn = gxh * gm;
+                m1 += dxn;
+                m2 += dxn * xn;
+                if (actq) *reinterpret_cast<f32x4*>(gxq + (size_t)(t * C + c) * HW) = dxn;
+            }
         }
         *reinterpret_cast<f32x4*>(Ml + ((c * 2 + th) * 2 + 0) * PT + 4 * q) = m1;
         *reinterpret_cast<f32x4*>(Ml + ((c * 2 + th) * 2 + 1) * PT + 4 * q) = m2;
@@ -785,6 +789,7 @@ __global__ __launch_bounds__(256) void ltae_bwd_gx_kernel(LtaeParams p) {
         p.part_gb[((size_t)blockIdx.x * C + c) * 2] = dg;
         p.part_gb[((size_t)blockIdx.x * C + c) * 2 + 1] = db;
     }
+    if constexpr (!GX) return;
     __syncthreads();
     if (actq) {
         for (int c = slot & 63; c < C; c += 64) {
@@ -816,7 +821,8 @@ __global__ __launch_bounds__(256) void ltae_bwd_gx_kernel(LtaeParams p) {
 //   4 V, Z     V = sum_t gs xhat (-> d U partial), Z = sum_t attn xhat (-> global, for d Wc)   thread = (channel, heads)
 //   5 dx       d xhat[t][c] = sum_h attn r + gs U; GroupNorm backward with the means m1, m2 over (C/16 x T); d gamma / d beta
 //              partials.  gamma d xhat is parked in gx (each thread re-reads only what it wrote) until the means are known.
-template <int C>
+// GX = false (no input gradient): phase 5 forms the d gamma / d beta partials only; p.gx is not touched.
+template <int C, bool GX = true>
 __global__ __launch_bounds__(256) void ltae_lds_bwd_kernel(LtaeParams p, StreamBwd sb) {
     extern __shared__ float lds[];
     constexpr int CP = C + 1;
@@ -1017,7 +1023,7 @@ __global__ __launch_bounds__(256) void ltae_lds_bwd_kernel(LtaeParams p, StreamB
             r[h] = *reinterpret_cast<const f32x4*>(Rl + (size_t)(h * C + sc_) * 4);
             u[h] = p.U[h * C + sc_];
         }
-        float* gxc = p.gx + (size_t)b * T * C * HW + (size_t)sc_ * HW + pix0;
+        float* gxc = GX ? p.gx + (size_t)b * T * C * HW + (size_t)sc_ * HW + pix0 : nullptr;
         f32x4 dg = zero4, db = zero4, m1 = zero4, m2 = zero4;
         for (int t = sth; t < T; t += NTH) {
             f32x4 gxh = zero4;
@@ -1027,15 +1033,19 @@ __global__ __launch_bounds__(256) void ltae_lds_bwd_kernel(LtaeParams p, StreamB
             const f32x4 xn = *reinterpret_cast<const f32x4*>(xs + (size_t)(t * CP + sc_) * 4);
             dg += gxh * xn;
             db += gxh;
-            const f32x4 dxn = gxh * gm;
-            m1 += dxn;
-            m2 += dxn * xn;
-            *reinterpret_cast<f32x4*>(gxc + (size_t)t * C * HW) = dxn;
+            if constexpr (GX) {
+                const f32x4 dxn = gxh * gm;
+                m1 += dxn;
+                m2 += dxn * xn;
+                *reinterpret_cast<f32x4*>(gxc + (size_t)t * C * HW) = dxn;
+            }
         }
         const float inv_n = 1.f / (float)(CPG * T);
         __syncthreads();                           // `red` free again (phase 3 read it before its last barrier)
-        m1 = group_total(m1, red) * inv_n;
-        m2 = group_total(m2, red + 256) * inv_n;
+        if constexpr (GX) {
+            m1 = group_total(m1, red) * inv_n;
+            m2 = group_total(m2, red + 256) * inv_n;
+        }
         // d gamma / d beta partial of the tile: sum over its pixels and the time slices
         const float dgs = (dg.x + dg.y) + (dg.z + dg.w), dbs = (db.x + db.y) + (db.z + db.w);
         if constexpr (NTH > 1) {
@@ -1053,6 +1063,7 @@ __global__ __launch_bounds__(256) void ltae_lds_bwd_kernel(LtaeParams p, StreamB
             p.part_gb[((size_t)tile * C + sc_) * 2] = dgs;
             p.part_gb[((size_t)tile * C + sc_) * 2 + 1] = dbs;
         }
+        if constexpr (!GX) return;
         const f32x4 rstd = *reinterpret_cast<const f32x4*>(STl + g * 8 + 4);
         for (int t = sth; t < T; t += NTH) {
             f32x4* gp = reinterpret_cast<f32x4*>(gxc + (size_t)t * C * HW);
@@ -3149,6 +3160,8 @@ constexpr int GXT = 8;                             // time steps per staged chun
 constexpr int GX_BUF = 2 * GXT * 16 * 64;          // one chunk: [arr 2][GXT][16 h][64 px] = 16,384 floats
 constexpr int GX_FLOATS = 2 * GX_BUF;              // two chunks in flight = 128 KB
 
+// GX = false (no input gradient): the d gamma / d beta partials into sb.gb64 only; p.gx is not touched.
+template <bool GX = true>
 __global__ __launch_bounds__(1024) void ltae_stream_bwd_gx64_kernel(LtaeParams p, StreamBwd sb) {
     constexpr int C = 64, CPG = 4;
     extern __shared__ float lds[];                 // r of 8 heads [8][16 c4][64 px][4], then the attn / gs chunks
@@ -3226,7 +3239,7 @@ __global__ __launch_bounds__(1024) void ltae_stream_bwd_gx64_kernel(LtaeParams p
         for (int cc = 0; cc < CPG; ++cc)
             ug[h][cc] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.U[h * C + g * CPG + cc])));
     const float* xg = p.x + (size_t)b * T * C * HW + (size_t)(g * CPG) * HW + pix;
-    float* gxg = p.gx + (size_t)b * T * C * HW + (size_t)(g * CPG) * HW + pix;
+    float* gxg = GX ? p.gx + (size_t)b * T * C * HW + (size_t)(g * CPG) * HW + pix : nullptr;
     const size_t hstride = (size_t)p.B * T * HW;
     float dgam[CPG] = {0.f, 0.f, 0.f, 0.f}, dbet[CPG] = {0.f, 0.f, 0.f, 0.f};     // sum_t d xhat * xn, sum_t d xhat (this pixel)
 
@@ -3292,7 +3305,7 @@ __global__ __launch_bounds__(1024) void ltae_stream_bwd_gx64_kernel(LtaeParams p
 #pragma unroll
                     for (int cc = 0; cc < CPG; ++cc) {
                         const float xnn = (xv[u][cc] - mean) * rstd;
-                        gxg[(size_t)(t * C + cc) * HW] = gm[cc] * acc[cc] - rstd * fmaf(xnn, m2, m1);
+                        if constexpr (GX) gxg[(size_t)(t * C + cc) * HW] = gm[cc] * acc[cc] - rstd * fmaf(xnn, m2, m1);
                         dgam[cc] = fmaf(acc[cc], xnn, dgam[cc]);
                         dbet[cc] += acc[cc];
                     }
@@ -3388,11 +3401,16 @@ void init_hook() {
     C2S_RAISE_LDS(ltae_lds_bwd_kernel<64>);
     C2S_RAISE_LDS(ltae_lds_bwd_kernel<128>);
     C2S_RAISE_LDS(ltae_lds_bwd_kernel<256>);
+    C2S_RAISE_LDS((ltae_lds_bwd_kernel<64, false>));
+    C2S_RAISE_LDS((ltae_lds_bwd_kernel<128, false>));
+    C2S_RAISE_LDS((ltae_lds_bwd_kernel<256, false>));
     C2S_RAISE_LDS(ltae_bwd_heads_kernel);
-    C2S_RAISE_LDS(ltae_bwd_gx_kernel);
+    C2S_RAISE_LDS(ltae_bwd_gx_kernel<true>);
+    C2S_RAISE_LDS(ltae_bwd_gx_kernel<false>);
     C2S_RAISE_LDS(ltae_stream_bwd_heads_kernel<4>);
     C2S_RAISE_LDS(ltae_stream_bwd_gx_kernel<4>);
-    C2S_RAISE_LDS(ltae_stream_bwd_gx64_kernel);
+    C2S_RAISE_LDS(ltae_stream_bwd_gx64_kernel<true>);
+    C2S_RAISE_LDS(ltae_stream_bwd_gx64_kernel<false>);
     C2S_RAISE_LDS(ltae_reg_bwd_heads_kernel<false>);
     C2S_RAISE_LDS(ltae_reg_bwd_heads_kernel<true>);
     C2S_RAISE_LDS(ltae_reg_fwd_kernel<false>);
@@ -3563,9 +3581,10 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
                                  float* gbc, float* ggamma, float* gbeta, float* workspace, size_t ws_floats,
                                  void* stream) {
     if (int rc = check(d)) return rc;
-    C2S_REQUIRE(x && gamma && beta && U && Wc && bc && pe && attn_pre && stats && gx && gU && gs0 && gWc && gbc &&
-                    ggamma && gbeta && workspace,
+    C2S_REQUIRE(x && gamma && beta && U && Wc && bc && pe && attn_pre && stats && gU && gs0 && gWc && gbc && workspace,
                 "ltae_bwd: null pointer");
+    C2S_REQUIRE((ggamma == nullptr) == (gbeta == nullptr), "ltae_bwd: ggamma and gbeta are NULL together");
+    const bool want_gb = ggamma != nullptr;    // gx == NULL: no input gradient is stored (include/c2s_hip.h)
     C2S_REQUIRE(ws_floats >= c2s_ltae_bwd_workspace_floats(d), "ltae_bwd: workspace too small");
     (void)s0; (void)valid;
     const bool long_path = use_long(d);
@@ -3602,7 +3621,7 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
         a.M = sb.M = p.V;
         a.ASG = p.V + P * NH * 2;
         a.part_U = sb.part_U = a.ASG + 2 * NH * P;
-        if (int rc = ltae_long_bwd(a, st)) return rc;
+        if (int rc = ltae_long_bwd(a, st)) return rc;      // gx == NULL: the vz kernel wrote the partials, no d x kernel
     } else if (stream_path) {
         // the V area of the workspace is not used by the streaming kernels: it holds M [P][16][2] and part_U [tiles][16][C]
         sb.M = p.V;
@@ -3618,8 +3637,13 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
         C2S_CHECK_LAUNCH("ltae_stream_bwd_heads");
         const size_t lds2 = ((size_t)NH * d->C * SPT + 2 * SCH * 4 * SPT * 4) * sizeof(float);
         static const bool gx64 = [] { const char* e = getenv("C2S_LTAE_GX64"); return !(e && e[0] == '0'); }();
-        if ((gx64 || reg_heads) && d->C == 64 && d->HW % 64 == 0) {
-            hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel, dim3(d->B * (d->HW / 64)), dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
+        // without gx: the streaming heads kernel wrote the d gamma / d beta partials itself (paths 1, 2): no d x kernel; the
+        // register-resident one leaves them to gx64 (paths 3, 4), which then runs without its store
+        if (gx == nullptr) {
+            if (reg_heads && want_gb)
+                hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel<false>, dim3(d->B * (d->HW / 64)), dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
+        } else if ((gx64 || reg_heads) && d->C == 64 && d->HW % 64 == 0) {
+            hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel<true>, dim3(d->B * (d->HW / 64)), dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
         } else {
             hipLaunchKernelGGL(ltae_stream_bwd_gx_kernel<4>, dim3(tiles), dim3(1024), lds2, st, p, sb);
         }
@@ -3627,14 +3651,21 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
     } else if (lds_path) {
         sb.part_U = p.V;                           // [tiles][16][C] <= the V area [B][16][C][HW]
         const size_t lb = lds_bwd_bytes(d);
-        if (d->C == 64) hipLaunchKernelGGL(ltae_lds_bwd_kernel<64>, dim3(tiles), dim3(256), lb, st, p, sb);
-        else if (d->C == 128) hipLaunchKernelGGL(ltae_lds_bwd_kernel<128>, dim3(tiles), dim3(256), lb, st, p, sb);
-        else hipLaunchKernelGGL(ltae_lds_bwd_kernel<256>, dim3(tiles), dim3(256), lb, st, p, sb);
+        if (gx != nullptr) {
+            if (d->C == 64) hipLaunchKernelGGL(ltae_lds_bwd_kernel<64>, dim3(tiles), dim3(256), lb, st, p, sb);
+            else if (d->C == 128) hipLaunchKernelGGL(ltae_lds_bwd_kernel<128>, dim3(tiles), dim3(256), lb, st, p, sb);
+            else hipLaunchKernelGGL(ltae_lds_bwd_kernel<256>, dim3(tiles), dim3(256), lb, st, p, sb);
+        } else {                                   // fused kernel: its d x phase forms the d gamma / d beta partials only
+            if (d->C == 64) hipLaunchKernelGGL((ltae_lds_bwd_kernel<64, false>), dim3(tiles), dim3(256), lb, st, p, sb);
+            else if (d->C == 128) hipLaunchKernelGGL((ltae_lds_bwd_kernel<128, false>), dim3(tiles), dim3(256), lb, st, p, sb);
+            else hipLaunchKernelGGL((ltae_lds_bwd_kernel<256, false>), dim3(tiles), dim3(256), lb, st, p, sb);
+        }
         C2S_CHECK_LAUNCH("ltae_lds_bwd");
     } else {
         hipLaunchKernelGGL(ltae_bwd_heads_kernel, dim3(tiles), dim3(256), bwd1_lds(d), st, p);
         C2S_CHECK_LAUNCH("ltae_bwd_heads");
-        hipLaunchKernelGGL(ltae_bwd_gx_kernel, dim3(tiles), dim3(256), bwd2_lds(d), st, p);
+        if (gx != nullptr) hipLaunchKernelGGL(ltae_bwd_gx_kernel<true>, dim3(tiles), dim3(256), bwd2_lds(d), st, p);
+        else if (want_gb) hipLaunchKernelGGL(ltae_bwd_gx_kernel<false>, dim3(tiles), dim3(256), bwd2_lds(d), st, p);
         C2S_CHECK_LAUNCH("ltae_bwd_gx");
     }
     // reductions
@@ -3645,7 +3676,7 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
     }
     reduce_rows(p.part_bc, gbc, 1, (int)tiles, 256, rtmp, st);
     C2S_CHECK_LAUNCH("ltae_reduce_bc");
-    {   // interleaved (dgamma, dbeta) partials -> the two outputs
+    if (want_gb) {   // interleaved (dgamma, dbeta) partials -> the two outputs
         const int gb_tiles = reg_heads ? d->B * (d->HW / 64) : (int)tiles;
         reduce_rows(p.part_gb, ggamma, 1, gb_tiles, 2 * d->C, rtmp, st, gbeta);
         C2S_CHECK_LAUNCH("ltae_reduce_gb");

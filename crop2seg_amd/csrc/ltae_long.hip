@@ -546,6 +546,7 @@ int ltae_long_bwd(const LtaeLongArgs& a, hipStream_t st) {
     else if (a.C == 128) hipLaunchKernelGGL(ltae_long_bwd_vz_kernel<128>, grid, dim3(1024), VZ_LDS, st, a);
     else hipLaunchKernelGGL(ltae_long_bwd_vz_kernel<256>, grid, dim3(1024), VZ_LDS, st, a);
     C2S_CHECK_LAUNCH("ltae_long_bwd_vz");
+    if (a.gx == nullptr) return C2S_OK;       // no input gradient: the vz kernel wrote the d gamma / d beta partials
     hipLaunchKernelGGL(ltae_long_bwd_gx_kernel, grid, dim3(1024), GX_LDS, st, a);
     C2S_CHECK_LAUNCH("ltae_long_bwd_gx");
     return C2S_OK;

@@ -898,7 +898,9 @@ extern "C" int c2s_norm_bwd(const c2s_norm_desc* d, const float* x, const float*
                             float* dbeta, float* dbias, float* workspace, size_t ws_floats, const int* valid,
                             void* stream) {
     if (int rc = check_desc(d)) return rc;
-    C2S_REQUIRE(x && g && gamma && group_stats && row_ab && gx && workspace, "norm_bwd: null pointer");
+    C2S_REQUIRE(x && g && gamma && group_stats && row_ab && workspace, "norm_bwd: null pointer");
+    C2S_REQUIRE(gx != nullptr || (dbias == nullptr && (dgamma != nullptr || dbeta != nullptr)),
+                "norm_bwd: gx == NULL takes dgamma / dbeta only");
     C2S_REQUIRE(ws_floats >= c2s_norm_workspace_floats(d), "norm_bwd: workspace too small");
     const int segs = n_segs(d->HW);
     const long rows = (long)d->N * d->C;
@@ -908,7 +910,7 @@ extern "C" int c2s_norm_bwd(const c2s_norm_desc* d, const float* x, const float*
     hipLaunchKernelGGL(norm_bwd_sums_kernel, dim3(cdiv(nitems, 4)), dim3(256), 0, st, x, g, row_ab, group_stats, part,
                        valid, *d, segs, nitems, relu);
     C2S_CHECK_LAUNCH("norm_bwd_sums");
-    hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(cdiv(nitems, 4)), dim3(256), 0, st, x, g, row_ab, gamma, group_stats, gx,
+    if (gx != nullptr) hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3(cdiv(nitems, 4)), dim3(256), 0, st, x, g, row_ab, gamma, group_stats, gx,
                        part, valid, *d, segs, nitems, relu);
     C2S_CHECK_LAUNCH("norm_bwd_apply");
     if (dgamma != nullptr || dbeta != nullptr || dbias != nullptr) {
@@ -970,6 +972,9 @@ extern "C" int c2s_norm_bwd_onepass(const c2s_norm_desc* d, const float* x, cons
                                     float* dbeta, float* dbias, float* workspace, size_t ws_floats, const int* valid,
                                     void* sync, size_t sync_nbytes, void* stream) {
     if (int rc = check_desc(d)) return rc;
+    // no input gradient: the sums pass of the two-pass form (same arithmetic, same order) and the parameter launch
+    if (gx == nullptr) return c2s_norm_bwd(d, x, g, gamma, group_stats, row_ab, relu, gx, dgamma, dbeta, dbias, workspace,
+                                           ws_floats, valid, stream);
     C2S_REQUIRE(x && g && gamma && group_stats && row_ab && gx && workspace && sync, "norm_bwd_onepass: null pointer");
     C2S_REQUIRE(ws_floats >= c2s_norm_workspace_floats(d), "norm_bwd_onepass: workspace too small");
     const int nk = onepass_nk(d, valid);

@@ -39,6 +39,17 @@ SIDE_FLUSH_POSITIONS = int(_os.environ.get("C2S_WGRAD_FLUSH_POSITIONS", str(1 <<
 GRAPH_SIDE = _os.environ.get("C2S_GRAPH_SIDE", "0") != "0"
 
 
+# Backward launch log: None (default) or a list to which every backward launch appends (op, name, kind), kind "dgrad" (the
+# data gradient into an input), "wgrad" (a weight gradient) or "params" (a fused parameter-gradient launch).  Tests set it to
+# show which launches a frozen parameter pruned.
+BACKWARD_LOG: Optional[list] = None
+
+
+def _log(op: str, name: str, kind: str) -> None:
+    if BACKWARD_LOG is not None:
+        BACKWARD_LOG.append((op, name, kind))
+
+
 def _side_ok() -> bool:
     """Parameter-gradient launches go to the side stream (eager always; under capture when GRAPH_SIDE)."""
     return SIDE_WGRAD and (GRAPH_SIDE or not torch.cuda.is_current_stream_capturing())
@@ -286,10 +297,16 @@ class Ctx:
     """Per-forward context: parameters by name, parameter-gradient views, scratch, tape, mode flags."""
 
     def __init__(self, params: Dict[str, Tensor], buffers: Dict[str, Tensor], grads: Optional[Dict[str, Tensor]],
-                 ws: Workspace, training: bool, tape: Optional[Tape], eps: float = 1e-5, momentum: float = 0.1):
+                 ws: Workspace, training: bool, tape: Optional[Tape], eps: float = 1e-5, momentum: float = 0.1,
+                 trainable: Optional[Sequence[str]] = None):
         self.p = params
         self.b = buffers
         self.g = grads            # name -> gradient tensor (same shape as the parameter), written by backward
+        # names of the parameters that get a gradient; None: all of them, and every op records its full backward as it always
+        # has.  Otherwise requires_grad is propagated on the tape (mark / needs): an op output needs a gradient when an input
+        # tensor or a parameter of the op does (the model input never does), and the backward skips what nothing needs.
+        self.trainable = None if trainable is None else frozenset(trainable)
+        self._needs: set = set()  # data pointers of the op outputs that need a gradient (trainable is not None)
         self.ws = ws
         self.training = training
         self.tape = tape
@@ -305,9 +322,32 @@ class Ctx:
         cus = lib().c2s_device_cus()
         self.cus = cus if cus > 0 else 256
 
+    # -- which tensors need a gradient ---------------------------------------------------------------
+    def trains(self, name: Optional[str]) -> bool:
+        """Whether parameter `name` gets a gradient."""
+        return name is not None and (self.trainable is None or name in self.trainable)
+
+    def needs(self, t: Optional[Tensor]) -> bool:
+        """Whether a gradient must flow into tensor `t` (always, when every parameter trains)."""
+        return self.trainable is None or (t is not None and t.data_ptr() in self._needs)
+
+    def mark(self, outs: Sequence[Optional[Tensor]], inputs: Sequence[Optional[Tensor]] = (),
+             params: Sequence[Optional[str]] = ()) -> bool:
+        """requires_grad propagation of one op: True (and the outputs are marked) when the op records a backward, i.e. a tape
+        exists and an input tensor needs a gradient or a parameter of the op trains."""
+        if self.tape is None:
+            return False
+        if self.trainable is None:
+            return True
+        if not (any(self.needs(t) for t in inputs if t is not None) or any(self.trains(n) for n in params)):
+            return False
+        self._needs.update(o.data_ptr() for o in outs if o is not None)
+        return True
+
     # -- parameter gradient sinks ---------------------------------------------------------------
     def grad_sink(self, name: str) -> Tuple[Tensor, int]:
-        """Returns (gradient tensor, accumulate flag) for parameter `name`."""
+        """Returns (gradient tensor, accumulate flag) for parameter `name` (a trainable one)."""
+        assert self.trains(name), f"grad_sink: {name} is frozen"
         acc = 1 if name in self._gwritten else 0
         self._gwritten.add(name)
         return self.g[name], acc
@@ -593,22 +633,30 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
                                              out.data_ptr(), _ptr(valid), _stream()), "conv3x3_smallcin")
         else:
             _igemm(d, s0, s1, wpk, ctx.p[bname] if bname else None, out, valid)
-    if ctx.tape is None:
+    if not ctx.mark([out], srcs, [wname, bname]):
         return out
     tape = ctx.tape
     tape.track(out)
+    train_w = ctx.trains(wname)
+    need_src = [need_input_grad and ctx.needs(src) for src in srcs]
 
     def bwd():
         g = tape.pop_grad(out)
         if g is None:
             return
-        gw, acc = ctx.grad_sink(wname)
-        _wgrad(ctx, srcs, g, Cout, Ho, Wo, K, S, pad, pad_mode, gw, Cin * KK, KK, list(range(KK)), acc, valid)
-        if not need_input_grad:
+        if train_w:
+            gw, acc = ctx.grad_sink(wname)
+            _log("conv2d", wname, "wgrad")
+            _wgrad(ctx, srcs, g, Cout, Ho, Wo, K, S, pad, pad_mode, gw, Cin * KK, KK, list(range(KK)), acc, valid)
+        if not any(need_src):
             return
         c_lo = 0
         for si, src in enumerate(srcs):
             Cs = src.shape[1]
+            if not need_src[si]:
+                c_lo += Cs
+                continue
+            _log("conv2d", wname, "dgrad")
             existing = tape.grad_of(src)
             gin = existing if existing is not None else torch.empty_like(src)
             accf = 1 if existing is not None else 0
@@ -678,18 +726,24 @@ def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str, K: int = 4, pa
             _xpair(d, x, wpk, bias, out, None)
     else:
         _parity_transpose(ctx, (wname, "fwd"), x, Wt, 0, Cin, Cout, KK, Cout * KK, K, pad, bias, out, 0, 0, None)
-    if ctx.tape is None:
+    if not ctx.mark([out], [x], [wname, bname]):
         return out
     tape = ctx.tape
     tape.track(out)
+    train_w, need_x = ctx.trains(wname), ctx.needs(x)
 
     def bwd():
         g = tape.pop_grad(out)
         if g is None:
             return
-        gw, acc = ctx.grad_sink(wname)
-        # dW[ci,co,k] = sum x[ci,p] * g[co, 2p+k-pad]  ==  convKxKs2 weight gradient with (input=g, gout=x)
-        _wgrad(ctx, [g], x, Cin, H, Wd, K, 2, pad, _lib.PAD_ZEROS, gw, Cout * KK, KK, list(range(KK)), acc, None)
+        if train_w:
+            gw, acc = ctx.grad_sink(wname)
+            _log("conv_transpose2d", wname, "wgrad")
+            # dW[ci,co,k] = sum x[ci,p] * g[co, 2p+k-pad]  ==  convKxKs2 weight gradient with (input=g, gout=x)
+            _wgrad(ctx, [g], x, Cin, H, Wd, K, 2, pad, _lib.PAD_ZEROS, gw, Cout * KK, KK, list(range(KK)), acc, None)
+        if not need_x:
+            return
+        _log("conv_transpose2d", wname, "dgrad")
         existing = tape.grad_of(x)
         gin = existing if existing is not None else torch.empty_like(x)
         wd, CP = ctx.pack((wname, "dgrad"), Wt, 0, Cout, Cin, Cout * KK, KK, list(range(KK)))
@@ -717,30 +771,36 @@ def depthwise_conv2d(ctx: Ctx, x: Tensor, wname: str, K: int, S: int, pad: int, 
     if bname is not None:
         check(lib().c2s_channel_bias_add(out.data_ptr(), ctx.p[bname].data_ptr(), _ptr(valid), N, Cc, Ho * Wo, _stream()),
               "channel_bias_add")
-    if ctx.tape is None:
+    if not ctx.mark([out], [x], [wname, bname]):
         return out
     tape = ctx.tape
     tape.track(out)
+    train_w, need_x = ctx.trains(wname), ctx.needs(x)
 
     def bwd():
         g = tape.pop_grad(out)
         if g is None:
             return
-        gw, acc = ctx.grad_sink(wname)
-        part = ctx.ws.get("dw_partial", N * Cc * K * K)
-        tgt = gw if not acc else torch.empty_like(gw)
+        if train_w:
+            gw, acc = ctx.grad_sink(wname)
+            part = ctx.ws.get("dw_partial", N * Cc * K * K)
+            tgt = gw if not acc else torch.empty_like(gw)
+            _log("depthwise_conv2d", wname, "wgrad")
 
-        def wgrad():
-            check(lib().c2s_dwconv_wgrad(x.data_ptr(), g.data_ptr(), part.data_ptr(), tgt.data_ptr(), _ptr(valid), N, Cc, Hin,
-                                         Win, K, S, pad, pad_mode, _stream()), "dwconv_wgrad")
-            if acc:
-                check(lib().c2s_add_inplace(gw.data_ptr(), tgt.data_ptr(), tgt.numel(), _stream()), "add_inplace")
+            def wgrad():
+                check(lib().c2s_dwconv_wgrad(x.data_ptr(), g.data_ptr(), part.data_ptr(), tgt.data_ptr(), _ptr(valid), N, Cc,
+                                             Hin, Win, K, S, pad, pad_mode, _stream()), "dwconv_wgrad")
+                if acc:
+                    check(lib().c2s_add_inplace(gw.data_ptr(), tgt.data_ptr(), tgt.numel(), _stream()), "add_inplace")
 
-        if _side_ok():
-            tape.defer(wgrad, [x, g, tgt, part])        # side stream, next to the data-gradient chain (part: a later, larger
+            if _side_ok():
+                tape.defer(wgrad, [x, g, tgt, part])    # side stream, next to the data-gradient chain (part: a later, larger
                                                         # request replaces the workspace buffer before this launch ends)
-        else:
-            wgrad()
+            else:
+                wgrad()
+        if not need_x:
+            return
+        _log("depthwise_conv2d", wname, "dgrad")
         existing = tape.grad_of(x)                      # e.g. the residual branch of the block: accumulate in the kernel
         gin = existing if existing is not None else torch.empty_like(x)
         check(lib().c2s_dwconv_dgrad(g.data_ptr(), W.data_ptr(), gin.data_ptr(), _ptr(valid), N, Cc, Hin, Win, K, S, pad,
@@ -803,27 +863,53 @@ def norm_act(ctx: Ctx, x: Tensor, prefix: str, kind: int, groups: int, relu: boo
         check(lib().c2s_norm_fwd(C.byref(d), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(rm), _ptr(rv), _ptr(nbt),
                                  gstats.data_ptr(), row_ab.data_ptr(), _ptr(residual), y.data_ptr(), int(relu),
                                  ws.data_ptr(), ws.numel(), _ptr(valid), float(pad_value), _stream()), "norm_fwd")
-    if ctx.tape is None:
+    pnames = [prefix + ".weight", prefix + ".bias"] if affine else []
+    if not ctx.mark([y], [x, residual], pnames + [conv_bias]):
         return y
     tape = ctx.tape
     tape.track(y)
+    need_x = ctx.needs(x)
+    need_res = residual is not None and ctx.needs(residual)
+    # conv_bias trains => x needs a gradient (x is that convolution's output): without one only gamma / beta can train here
+    train_gamma, train_beta = [affine and ctx.trains(n) for n in pnames] or [False, False]
 
     def bwd():
         g = tape.pop_grad(y)
         if g is None:
             return
-        if residual is not None:
+        if need_res:
             tape.add_grad(residual, g, own=True)      # the residual branch keeps g itself ...
-            gx = torch.empty_like(g)                  # ... and the norm gradient goes to a fresh buffer (no copy of g)
+            gx = torch.empty_like(g) if need_x else None   # ... and the norm gradient goes to a fresh buffer (no copy of g)
         else:
-            gx = g  # in place
-        if affine:
+            gx = g if need_x else None  # in place
+        if not need_x:
+            if train_gamma or train_beta:
+                # no input gradient: the sums pass and the parameter launch, no apply pass (the one-pass form does the same
+                # arithmetic in the same order, so its shapes take this path too)
+                _log("norm", prefix, "params")
+                wsn = ctx.ws.get("norm", nws)
+                check(lib().c2s_norm_bwd(C.byref(d), x.data_ptr(), g.data_ptr(), gamma.data_ptr(), gstats.data_ptr(),
+                                         row_ab.data_ptr(), int(relu), None,
+                                         ctx.grad_sink(pnames[0])[0].data_ptr() if train_gamma else None,
+                                         ctx.grad_sink(pnames[1])[0].data_ptr() if train_beta else None, None,
+                                         wsn.data_ptr(), wsn.numel(), _ptr(valid), _stream()), "norm_bwd")
+            return
+        _log("norm", prefix, "dgrad")
+        if affine and ctx.trainable is not None:
+            dgamma = ctx.grad_sink(pnames[0])[0] if train_gamma else None
+            dbeta = ctx.grad_sink(pnames[1])[0] if train_beta else None
+        elif affine:
             dgamma, _ = ctx.grad_sink(prefix + ".weight")
             dbeta, _ = ctx.grad_sink(prefix + ".bias")
-        else:
+        elif ctx.trainable is None:
             dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
             dbeta = torch.empty(Cc, device=x.device, dtype=torch.float32)
-        dbias = ctx.grad_sink(conv_bias)[0] if conv_bias else None
+        else:
+            dgamma = dbeta = None                     # affine=False: nothing to discard when not formed at all
+        dbias = ctx.grad_sink(conv_bias)[0] if ctx.trains(conv_bias) else None
+        want_params = dgamma is not None or dbeta is not None or dbias is not None
+        if want_params:
+            _log("norm", prefix, "params")
 
         def norm_bwd(ws_, dg_, db_, dbi_):
             if sync_bytes:
@@ -837,12 +923,12 @@ def norm_act(ctx: Ctx, x: Tensor, prefix: str, kind: int, groups: int, relu: boo
                                          row_ab.data_ptr(), int(relu), gx.data_ptr(), _ptr(dg_), _ptr(db_), _ptr(dbi_),
                                          ws_.data_ptr(), ws_.numel(), _ptr(valid), _stream()), "norm_bwd")
 
-        if _side_ok():
+        if _side_ok() and want_params:
             # the parameter gradients (one wave per channel: a launch that leaves the GPU idle) go to the side stream; their
             # partial sums live in a buffer of their own until the join
             ws2 = torch.empty(nws, device=x.device, dtype=torch.float32)
             norm_bwd(ws2, None, None, None)
-            tape.defer(lambda: check(lib().c2s_norm_bwd_params(C.byref(d), ws2.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+            tape.defer(lambda: check(lib().c2s_norm_bwd_params(C.byref(d), ws2.data_ptr(), _ptr(dgamma), _ptr(dbeta),
                                                                _ptr(dbias), _ptr(valid), _stream()), "norm_bwd_params"),
                        [ws2] if affine else [ws2, dgamma, dbeta])     # affine=False: the discarded sums are temporaries too
         else:
@@ -870,22 +956,29 @@ def squeeze_excite(ctx: Ctx, x: Tensor, prefix: str, valid: Optional[Tensor], pa
     ws = ctx.ws.get("se", nws)
     check(lib().c2s_se_fwd(x.data_ptr(), W1.data_ptr(), W2.data_ptr(), pooled.data_ptr(), hidden.data_ptr(), scale.data_ptr(),
                            y.data_ptr(), _ptr(valid), N, Cc, HW, float(pad_value), ws.data_ptr(), ws.numel(), _stream()), "se_fwd")
-    if ctx.tape is None:
+    wn = [prefix + ".sae.1.weight", prefix + ".sae.3.weight"]
+    if not ctx.mark([y], [x], wn):
         return y
     tape = ctx.tape
     tape.track(y)
+    need_x = ctx.needs(x)
 
     def bwd():
         g = tape.pop_grad(y)
         if g is None:
             return
-        g1, a1 = ctx.grad_sink(prefix + ".sae.1.weight")
-        g2, a2 = ctx.grad_sink(prefix + ".sae.3.weight")
+        # one fused launch (the input gradient in place of g): a frozen weight's gradient is formed into scratch
+        (g1, a1), (g2, a2) = [ctx.grad_sink(n) if ctx.trains(n) else (torch.empty_like(ctx.p[n]), 0) for n in wn]
+        if ctx.trains(wn[0]) or ctx.trains(wn[1]):
+            _log("squeeze_excite", prefix, "params")
+        if need_x:
+            _log("squeeze_excite", prefix, "dgrad")
         ws_ = ctx.ws.get("se", nws)
         check(lib().c2s_se_bwd(x.data_ptr(), g.data_ptr(), W1.data_ptr(), W2.data_ptr(), pooled.data_ptr(), hidden.data_ptr(),
                                scale.data_ptr(), g.data_ptr(), g1.data_ptr(), g2.data_ptr(), a1, a2, _ptr(valid), N, Cc, HW,
                                ws_.data_ptr(), ws_.numel(), _stream()), "se_bwd")
-        tape.add_grad(x, g)
+        if need_x:
+            tape.add_grad(x, g)
 
     tape.record(bwd)
     return y
@@ -914,18 +1007,25 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
     out = torch.empty(B, Cc, H, W, device=x5.device, dtype=torch.float32)
     check(lib().c2s_temporal_aggregate_fwd(C.byref(d), x5.data_ptr(), attn.data_ptr(), _ptr(valid), out.data_ptr(),
                                            _stream()), "temporal_aggregate_fwd")
-    if ctx.tape is None:
+    if not ctx.mark([out], [x5, src_attn if mode != "mean" else None]):
         return out
     tape = ctx.tape
     tape.track(out)
+    need_x = ctx.needs(x5)
+    # "mean": the weights derive from the frame flags alone (their gradient is formed and dropped when every parameter trains)
+    need_a = ctx.needs(src_attn) if mode != "mean" else ctx.trainable is None
 
     def bwd():
         g = tape.pop_grad(out)
         if g is None:
             return
-        existing = tape.grad_of(x5)
-        gx = existing if existing is not None else torch.empty_like(x5)
-        if mode == "att_group":
+        existing = tape.grad_of(x5) if need_x else None
+        gx = existing if existing is not None else (torch.empty_like(x5) if need_x else None)
+        if need_x:
+            _log("temporal_aggregate", mode, "dgrad")
+        if not need_a:
+            gattn = None
+        elif mode == "att_group":
             gattn = tape.grad_of(attn)
             if gattn is None:
                 gattn = torch.zeros_like(attn)
@@ -935,16 +1035,16 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
         nws = lib().c2s_temporal_aggregate_bwd_workspace_floats(C.byref(d))
         ws = ctx.ws.get("agg", nws)
         check(lib().c2s_temporal_aggregate_bwd(C.byref(d), x5.data_ptr(), attn.data_ptr(), _ptr(valid), g.data_ptr(),
-                                               gx.data_ptr(), 1 if existing is not None else 0, gattn.data_ptr(),
+                                               _ptr(gx), 1 if existing is not None else 0, _ptr(gattn),
                                                ws.data_ptr(), ws.numel(), _stream()), "temporal_aggregate_bwd")
-        if mode == "att_mean":
+        if mode == "att_mean" and need_a:
             cur = tape.grad_of(src_attn)
             tgt = cur if cur is not None else torch.empty_like(src_attn)
             check(lib().c2s_attn_head_mean_bwd(gattn.data_ptr(), tgt.data_ptr(), n_head, src_attn[0].numel(),
                                                1 if cur is not None else 0, _stream()), "attn_head_mean_bwd")
             if cur is None:
                 tape.grads[src_attn.data_ptr()] = tgt
-        if existing is None:
+        if need_x and existing is None:
             tape.grads[x5.data_ptr()] = gx
 
     tape.record(bwd)
@@ -1057,9 +1157,16 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
     if mode != 0 and emb is not None:
         check(lib().c2s_ltae_pe_fwd(None, pe256.data_ptr(), attn.data_ptr(), None, emb.data_ptr(), B, T, HW, 1, _stream()),
               "ltae_pe_fwd")
-    if ctx.tape is None:
+    fold_names = [prefix + ".attention_head.Q", prefix + ".attention_head.fc1_k.weight",
+                  prefix + ".attention_head.fc1_k.bias", prefix + ".inconv.weight", prefix + ".inconv.bias"]
+    norm_names = [prefix + ".in_norm.weight", prefix + ".in_norm.bias"]
+    pe_names = [] if mode == 0 else [enc + ".weight", enc + ".bias"] + ([] if enc2 is None else [enc2 + ".weight", enc2 + ".bias"])
+    if not ctx.mark([emb, attn], [x5], fold_names + norm_names + pe_names):
         return emb, attn
     tape = ctx.tape
+    need_x = ctx.needs(x5)
+    train_norm = any(ctx.trains(n) for n in norm_names)
+    train_fold = any(ctx.trains(n) for n in fold_names + pe_names)
     if d.keep is not None:              # the backward kernels read the explicit keep mask through the descriptor's raw pointer
         tape.track(keep)
     if attn is not None:
@@ -1072,7 +1179,8 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         g_emb = tape.pop_grad(emb) if emb is not None else None
         if g_attn is None and g_emb is None:
             return
-        gx = torch.empty_like(x5)
+        # gx None: the input needs no gradient (c2s_ltae_attn_bwd stores none); in_norm frozen as well: no d x kernel at all
+        gx = torch.empty_like(x5) if need_x else None
         dev = x5.device
         gU = torch.empty(n_head, Cc, device=dev)
         gs0 = torch.empty(B, T, n_head, device=dev)
@@ -1082,6 +1190,8 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         pending = []
 
         def sink(name):
+            if not ctx.trains(name):                  # frozen: formed into scratch by a launch that runs anyway
+                return torch.empty_like(ctx.p[name])
             dst, acc = ctx.grad_sink(name)
             if not acc:
                 return dst
@@ -1089,8 +1199,12 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
             pending.append((dst, tmp))
             return tmp
 
-        ggam = sink(prefix + ".in_norm.weight")
-        gbet = sink(prefix + ".in_norm.bias")
+        ggam = sink(norm_names[0]) if train_norm else None
+        gbet = sink(norm_names[1]) if train_norm else None
+        if need_x:
+            _log("ltae", prefix, "dgrad")
+        if train_norm or train_fold:
+            _log("ltae", prefix, "params")
         nws = lib().c2s_ltae_bwd_workspace_floats(C.byref(d))
         ws = ctx.ws.get("ltae", nws)
         if mode != 0 and g_emb is not None:          # the positional part of the values: g_a += <g_emb_h, pe_h>
@@ -1101,12 +1215,16 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         check(lib().c2s_ltae_attn_bwd(C.byref(d), x5.data_ptr(), gamma.data_ptr(), beta.data_ptr(), Ud.data_ptr(),
                                       s0d.data_ptr(), Wc.data_ptr(), bc.data_ptr(), pe.data_ptr(), _ptr(valid),
                                       _ptr(attn), attn_pre.data_ptr(), stats.data_ptr(), _ptr(g_emb), _ptr(g_attn),
-                                      gx.data_ptr(), gU.data_ptr(), gs0.data_ptr(), gWc.data_ptr(), gbc.data_ptr(),
-                                      ggam.data_ptr(), gbet.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ltae_bwd")
-        # adjoint of the parameter fold: final gradients of Q, fc1_k, inconv in one launch
-        names = [prefix + ".attention_head.Q", prefix + ".attention_head.fc1_k.weight",
-                 prefix + ".attention_head.fc1_k.bias", prefix + ".inconv.weight", prefix + ".inconv.bias"]
-        sinks = [ctx.grad_sink(nme) for nme in names]
+                                      _ptr(gx), gU.data_ptr(), gs0.data_ptr(), gWc.data_ptr(), gbc.data_ptr(),
+                                      _ptr(ggam), _ptr(gbet), ws.data_ptr(), ws.numel(), _stream()), "ltae_bwd")
+        if not train_fold:
+            for dst, tmp in pending:
+                check(lib().c2s_add_inplace(dst.data_ptr(), tmp.data_ptr(), tmp.numel(), _stream()), "add_inplace")
+            if need_x:
+                tape.add_grad(x5, gx)
+            return
+        # adjoint of the parameter fold: final gradients of Q, fc1_k, inconv in one launch (frozen ones into scratch)
+        sinks = [ctx.grad_sink(nme) if ctx.trains(nme) else (torch.empty_like(ctx.p[nme]), 0) for nme in fold_names]
         acc_mask = sum((1 << i) for i, (_, acc) in enumerate(sinks) if acc)
         fbw = ctx.ws.get("ltae_fold_bwd", lib().c2s_ltae_fold_bwd_workspace_floats())
         check(lib().c2s_ltae_fold_bwd(Q.data_ptr(), Wk.data_ptr(), bk.data_ptr(), Wc3.data_ptr(), bc.data_ptr(), pe.data_ptr(),
@@ -1129,7 +1247,8 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
                       "ltae_pe_abs_bwd")
         for dst, tmp in pending:
             check(lib().c2s_add_inplace(dst.data_ptr(), tmp.data_ptr(), tmp.numel(), _stream()), "add_inplace")
-        tape.add_grad(x5, gx)
+        if need_x:
+            tape.add_grad(x5, gx)
 
     tape.record(bwd)
     return emb, attn
@@ -1143,7 +1262,7 @@ def dropout_nchw(ctx: Ctx, x: Tensor, p: float, seed: int, keep: Optional[Tensor
     HW = x[0, 0].numel()
     y = torch.empty_like(x)
     check(lib().c2s_dropout_nchw(x.data_ptr(), y.data_ptr(), B, Cc, HW, p, seed, _ptr(seed_dev), _ptr(keep), _stream()), "dropout")
-    if ctx.tape is not None:
+    if ctx.mark([y], [x]):
         tape = ctx.tape
         tape.track(y)
 
@@ -1152,6 +1271,7 @@ def dropout_nchw(ctx: Ctx, x: Tensor, p: float, seed: int, keep: Optional[Tensor
             if g is None:
                 return
             gx = torch.empty_like(g)
+            _log("dropout", "", "dgrad")
             check(lib().c2s_dropout_nchw(g.data_ptr(), gx.data_ptr(), B, Cc, HW, p, seed, _ptr(seed_dev), _ptr(keep), _stream()),
                   "dropout_bwd")
             tape.add_grad(x, gx)
@@ -1169,23 +1289,30 @@ def pixel_group_norm(ctx: Ctx, x: Tensor, prefix: str, groups: int) -> Tensor:
     stats = torch.empty(B * groups * HW * 2, device=x.device, dtype=torch.float32)
     check(lib().c2s_pixel_gn_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), stats.data_ptr(), B, Cc,
                                  HW, groups, ctx.eps, _stream()), "pixel_gn_fwd")
-    if ctx.tape is not None:
+    pn = [prefix + ".weight", prefix + ".bias"]
+    if ctx.mark([y], [x], pn):
         tape = ctx.tape
         tape.track(y)
+        need_x = ctx.needs(x)
 
         def bwd():
             g = tape.pop_grad(y)
             if g is None:
                 return
+            # one fused launch: what nothing needs (a frozen gamma / beta, the input gradient) is formed into scratch
             gx = torch.empty_like(x)
-            dg, _ = ctx.grad_sink(prefix + ".weight")
-            db, _ = ctx.grad_sink(prefix + ".bias")
+            dg, db = [ctx.grad_sink(n)[0] if ctx.trains(n) else torch.empty_like(ctx.p[n]) for n in pn]
+            if ctx.trains(pn[0]) or ctx.trains(pn[1]):
+                _log("pixel_group_norm", prefix, "params")
+            if need_x:
+                _log("pixel_group_norm", prefix, "dgrad")
             nws = lib().c2s_pixel_gn_bwd_workspace_floats(B, Cc, HW)
             ws = ctx.ws.get("pixel_gn", nws)
             check(lib().c2s_pixel_gn_bwd(x.data_ptr(), g.data_ptr(), gamma.data_ptr(), stats.data_ptr(), gx.data_ptr(),
                                          dg.data_ptr(), db.data_ptr(), B, Cc, HW, groups, ws.data_ptr(), ws.numel(),
                                          _stream()), "pixel_gn_bwd")
-            tape.add_grad(x, gx)
+            if need_x:
+                tape.add_grad(x, gx)
 
         tape.record(bwd)
     return y

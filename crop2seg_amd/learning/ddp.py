@@ -8,7 +8,7 @@ This module has no HIP dependency so that the N > 1 logic is testable without a 
 from __future__ import annotations
 
 import os
-from typing import Iterable, Optional
+from typing import Iterable, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -73,11 +73,17 @@ class FlatDataParallel:
             return _StreamWork(done)
         return dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
-    def reduce_gradients(self, flat_grad: torch.Tensor) -> float:
+    def reduce_gradients(self, flat_grad: torch.Tensor, runs: Optional[Sequence[Tuple[int, int]]] = None) -> float:
         """Sum the flat gradient buffer over ranks in place; returns the scale (1/world) the optimiser must apply
-        (folded into the Adam kernel instead of a separate divide pass)."""
+        (folded into the Adam kernel instead of a separate divide pass).  runs: [start, end) ranges to sum, one collective
+        each (the trainable slots when parameters are frozen); the rest of the buffer is not touched.  None: all of it."""
         if self.active and flat_grad.numel() > 0:     # (C2S_BENCH_FORCE_DIST rehearses the launch on one GPU)
-            dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group)
+            if runs is None:
+                dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=self.group)
+            else:
+                for b, e in runs:
+                    if e > b:
+                        dist.all_reduce(flat_grad[b:e], op=dist.ReduceOp.SUM, group=self.group)
         return 1.0 / self.world
 
 

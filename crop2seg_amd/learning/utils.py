@@ -72,6 +72,28 @@ def weight_init(m):
             init.normal_(m.bias.data)
 
 
+def trainable_runs(offsets: List[int], total: int, flags: List[bool], steps: Optional[List[int]] = None) -> List[Tuple[int, int]]:
+    """[start, end) ranges of the flat buffers that cover the trainable parameters: slot i is [offsets[i], offsets[i + 1])
+    (the last one ends at `total`), consecutive trainable slots form one run.  With `steps` (the Adam step count of every
+    parameter) a run also ends where the step count changes, so that one Adam launch serves it."""
+    runs: List[List[int]] = []
+    for i, f in enumerate(flags):
+        if not f:
+            continue
+        beg, end = offsets[i], offsets[i + 1] if i + 1 < len(offsets) else total
+        key = None if steps is None else steps[i]
+        if runs and runs[-1][1] == beg and runs[-1][2] == key and flags[i - 1]:
+            runs[-1][1] = end
+        else:
+            runs.append([beg, end, key])
+    return [(b, e) for b, e, _ in runs]
+
+
+def clip_runs(runs: List[Tuple[int, int]], lo: int, hi: int) -> List[Tuple[int, int]]:
+    """The parts of `runs` inside [lo, hi)."""
+    return [(max(b, lo), min(e, hi)) for b, e in runs if min(e, hi) > max(b, lo)]
+
+
 class TrainStep:
     """One optimiser step of the reference's training loop (src/learning/utils.py:314-328) with everything on
     the HIP engine and no autograd graph:
@@ -81,6 +103,10 @@ class TrainStep:
     Parameters, gradients and Adam moments live in three flat fp32 buffers (the module's parameters are
     re-pointed at views of the flat parameter buffer), so data-parallel training needs exactly one all-reduce of
     `flat_grad` per step (RCCL over xGMI; torch.distributed backend "nccl") and the optimiser is one kernel.
+
+    Fine-tuning: a parameter with requires_grad False (read at every eager step; fixed by capture()) gets no gradient, no
+    launch of its own and no update.  The flat layout keeps every parameter; Adam and the gradient exchange cover the runs
+    of trainable slots, and, as in torch.optim.Adam, a parameter's step count advances only on the steps where it trained.
     """
 
     def __init__(self, model, num_classes: int = 15, ignore_index: int = -1, lr: float = 1e-3,
@@ -94,6 +120,7 @@ class TrainStep:
             raise ValueError("TrainStep needs a model with a classification head (encoder=False)")
         self.lr, self.betas, self.eps = lr, betas, eps
         named = list(model.named_parameters())
+        self._named = named                             # requires_grad is read off these at every step
         self.names = [n for n, _ in named]
         dev = named[0][1].device
         sizes = [p.numel() for _, p in named]
@@ -104,6 +131,7 @@ class TrainStep:
             o += (s + 3) // 4 * 4
         self.total = o
         self.offsets = offs
+        self.param_steps = [0] * len(named)             # Adam step count per parameter (advances only where it trained)
         self.flat_param = torch.zeros(o, device=dev, dtype=torch.float32)
         self.flat_grad = torch.zeros(o, device=dev, dtype=torch.float32)
         self.exp_avg = torch.zeros(o, device=dev, dtype=torch.float32)
@@ -129,11 +157,32 @@ class TrainStep:
             self.dp.sync_parameters(self.flat_param, [b for _, b in model.named_buffers()])
 
     # ------------------------------------------------------------------------------------------------
-    def _forward_backward(self, x: Tensor, dates: Tensor, y: Tensor, drop: Fn.DropoutState, overlap_exchange: bool = False) -> Tuple[Tensor, Tensor]:
-        """zero_grad -> forward -> CE -> backward into the flat gradient buffer (stream-ordered, no host sync)."""
+    def trainable_flags(self) -> List[bool]:
+        return [p.requires_grad for _, p in self._named]
+
+    def _xruns(self, flags: List[bool]) -> Optional[List[Tuple[int, int]]]:
+        """Ranges of the gradient exchange: None = the whole buffer (every parameter trains)."""
+        return None if all(flags) else trainable_runs(self.offsets, self.total, flags)
+
+    def _adam_runs(self, flags: List[bool]) -> List[Tuple[int, int, int]]:
+        """(start, end, step count) of every Adam launch: runs of trainable slots with one step count."""
+        runs = trainable_runs(self.offsets, self.total, flags, self.param_steps)
+        first = {}
+        for i in range(len(self.offsets) - 1, -1, -1):
+            first[self.offsets[i]] = i
+        return [(b, e, self.param_steps[first[b]]) for b, e in runs]
+
+    def _forward_backward(self, x: Tensor, dates: Tensor, y: Tensor, drop: Fn.DropoutState, overlap_exchange: bool = False,
+                          flags: Optional[List[bool]] = None) -> Tuple[Tensor, Tensor]:
+        """zero_grad -> forward -> CE -> backward into the flat gradient buffer (stream-ordered, no host sync).  Frozen slots
+        of the buffer (flags False) are not written."""
         model = self.model
+        flags = self.trainable_flags() if flags is None else flags
         tape = E.Tape()
-        ctx = E.Ctx(self.params, dict(model.named_buffers()), self.grads, self.ws, model.training, tape)
+        train = None if all(flags) else [n for n, f in zip(self.names, flags) if f]
+        grads = self.grads if train is None else {n: self.grads[n] for n in train}
+        ctx = E.Ctx(self.params, dict(model.named_buffers()), grads, self.ws, model.training, tape, trainable=train)
+        xruns = self._xruns(flags)
         ctx.want_att = False                             # the step returns (loss, logits): nobody reads the attention masks
         self._early, self._early_off = None, 0
         if (overlap_exchange and self.dp is not None and self.dp.active and OVERLAP_EXCHANGE and not E.REDUCE_BATCH
@@ -144,14 +193,21 @@ class TrainStep:
             # step) still runs; the encoder's own gradients follow after the join.
             def early_exchange():
                 tape.flush_side()                        # the weight-gradient launches queued so far
-                i = len(self.names)
-                while i > 0 and self.names[i - 1] in ctx._gwritten:
+                i = len(self.names)                      # the suffix of final gradients, frozen slots (never written) included
+                while i > 0 and (self.names[i - 1] in ctx._gwritten or not flags[i - 1]):
                     i -= 1
                 if i == 0 or i == len(self.names):
                     return
-                self._early_off = self.offsets[i]
-                self._early = self.dp.reduce_async(self.flat_grad[self._early_off:],
-                                                   after=(E._side_stream(),) if tape.side_used else ())
+                off = self.offsets[i]
+                after = (E._side_stream(),) if tape.side_used else ()
+                if xruns is None:
+                    self._early_off = off
+                    self._early = [self.dp.reduce_async(self.flat_grad[off:], after=after)]
+                    return
+                runs = clip_runs(xruns, off, self.total)     # only the trainable runs of the suffix
+                if runs:
+                    self._early_off = off
+                    self._early = [self.dp.reduce_async(self.flat_grad[b:e], after=after) for b, e in runs]
             ctx.early_hook = early_exchange
         out = Fn.FORWARDS[model.spec.model](ctx, model.spec, x, dates, drop)
         logits = out.logits
@@ -167,8 +223,8 @@ class TrainStep:
         tape.backward()
         if not torch.cuda.is_current_stream_capturing():
             self.ws.finalize_pack_plan()                 # from the second step on, all weight packs are one launch
-        for n in self.names:                             # parameters no kernel wrote to (none in the default models)
-            if n not in ctx._gwritten:
+        for n, f in zip(self.names, flags):              # trainable parameters no kernel wrote to (none in the default models)
+            if f and n not in ctx._gwritten:
                 self.grads[n].zero_()
         return loss, logits
 
@@ -206,19 +262,30 @@ class TrainStep:
         """Eager step.  Returns (loss[1] device tensor, logits).  No host synchronisation inside."""
         self.model._check_inputs(x, dates)
         drop = dropout_state if dropout_state is not None else self._fresh_dropout()
-        loss, logits = self._forward_backward(x.contiguous(), dates.contiguous(), y, drop, overlap_exchange=True)
+        flags = self.trainable_flags()
+        if not any(flags):
+            raise ValueError("TrainStep: no parameter requires grad")
+        loss, logits = self._forward_backward(x.contiguous(), dates.contiguous(), y, drop, overlap_exchange=True, flags=flags)
+        xruns = self._xruns(flags)
         scale = 1.0
         if self.dp is not None:
             if self._early is not None:                                   # the decoder's bucket has been under way since the
-                scale = self.dp.reduce_gradients(self.flat_grad[:self._early_off])     # backward pass entered the encoder
-                self._early.wait()
+                if xruns is None:                                         # backward pass entered the encoder
+                    scale = self.dp.reduce_gradients(self.flat_grad[:self._early_off])
+                else:
+                    scale = self.dp.reduce_gradients(self.flat_grad, runs=clip_runs(xruns, 0, self._early_off))
+                for h in self._early:
+                    if h is not None:
+                        h.wait()
                 self._early = None
             else:
-                scale = self.dp.reduce_gradients(self.flat_grad)          # one 4.3 MB bucket per step
+                scale = self.dp.reduce_gradients(self.flat_grad, runs=xruns)     # one 4.3 MB bucket per step
         if apply_update:
             self.step_count += 1
-            E.adam_flat(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr,
-                        self.betas[0], self.betas[1], self.eps, grad_scale=scale)
+            self.param_steps = [s + 1 if f else s for s, f in zip(self.param_steps, flags)]
+            for b, e, st in self._adam_runs(flags):
+                E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], st, self.lr,
+                            self.betas[0], self.betas[1], self.eps, grad_scale=scale)
         return loss, logits
 
     # ------------------------------------------------------------------------------------------------
@@ -228,11 +295,16 @@ class TrainStep:
     @torch.no_grad()
     def capture(self, x: Tensor, dates: Tensor, y: Tensor) -> None:
         """Capture the step for inputs of this shape.  `x`, `dates`, `y` are copied into static buffers; call
-        `replay(x, dates, y)` (or `replay()` to reuse the buffers' content) afterwards."""
+        `replay(x, dates, y)` (or `replay()` to reuse the buffers' content) afterwards.  The set of parameters that require
+        grad is fixed here: replay() raises once it has changed (capture again)."""
         self.model._check_inputs(x, dates)
         dev = x.device
+        flags = self.trainable_flags()
+        if not any(flags):
+            raise ValueError("TrainStep: no parameter requires grad")
         self.static_x, self.static_dates, self.static_y = x.clone().contiguous(), dates.clone().contiguous(), y.clone()
-        self.step_dev = torch.full((1,), self.step_count, device=dev, dtype=torch.int32)
+        runs = self._adam_runs(flags)                   # one device step counter per Adam launch
+        self.step_dev = torch.tensor([st for _, _, st in runs], device=dev, dtype=torch.int32)
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         drop = self._fresh_dropout()
         drop.seed_dev = self.seed_dev
@@ -244,7 +316,8 @@ class TrainStep:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                   # warm-up on the side stream: lazy one-time initialisation
-                self._forward_backward(self.static_x, self.static_dates, self.static_y, drop)   # (function attributes, workspaces)
+                self._forward_backward(self.static_x, self.static_dates, self.static_y, drop, flags=flags)   # (function
+                                                            # attributes, workspaces)
             torch.cuda.current_stream().wait_stream(side)
             for k, v in self.model.named_buffers():
                 v.copy_(saved[k])
@@ -256,26 +329,34 @@ class TrainStep:
             # (hipEventQuery), which the default global mode forbids while ANY thread captures
             with torch.cuda.graph(self.graph_fb, capture_error_mode="thread_local"):
                 self.seed_dev.add_(1)
-                self.static_loss, self.static_logits = self._forward_backward(self.static_x, self.static_dates, self.static_y, drop)
+                self.static_loss, self.static_logits = self._forward_backward(self.static_x, self.static_dates, self.static_y, drop,
+                                                                              flags=flags)
         finally:
             E.REDUCE_BATCH = batch0
         self.graph_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_opt, capture_error_mode="thread_local"):
             self.step_dev.add_(1)
-            E.adam_flat(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, 0, self.lr, self.betas[0],
-                        self.betas[1], self.eps, grad_scale=scale, step_dev=self.step_dev)
+            for k, (b, e, _) in enumerate(runs):
+                E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], 0, self.lr,
+                            self.betas[0], self.betas[1], self.eps, grad_scale=scale, step_dev=self.step_dev[k:k + 1])
+        self._cap_flags = flags
 
     @torch.no_grad()
     def replay(self, x: Optional[Tensor] = None, dates: Optional[Tensor] = None, y: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         if getattr(self, "graph_fb", None) is None:
             raise RuntimeError("TrainStep.replay(): no captured step (capture() was not called, or check_health() dropped it)")
+        flags = self.trainable_flags()
+        if flags != self._cap_flags:
+            raise RuntimeError("TrainStep.replay(): the set of parameters that require grad has changed since capture(); "
+                               "call capture() again")
         if x is not None:
             self.static_x.copy_(x)
             self.static_dates.copy_(dates)
             self.static_y.copy_(y)
         self.graph_fb.replay()
         if self.dp is not None:
-            self.dp.reduce_gradients(self.flat_grad)          # between the two graphs, on the same stream
+            self.dp.reduce_gradients(self.flat_grad, runs=self._xruns(flags))     # between the two graphs, on the same stream
         self.graph_opt.replay()
         self.step_count += 1
+        self.param_steps = [s + 1 if f else s for s, f in zip(self.param_steps, flags)]
         return self.static_loss, self.static_logits

@@ -284,7 +284,9 @@ int c2s_norm_fwd(const c2s_norm_desc* d, const float* x, const float* gamma, con
                  float* running_mean, float* running_var, long long* num_batches_tracked, float* group_stats, float* row_ab,
                  const float* residual, float* y, int relu, float* workspace, size_t ws_floats, const int* valid,
                  float pad_value, void* stream);
-/* gx may alias g.  dgamma, dbeta, dbias may be NULL (all NULL: the parameter-gradient launch is skipped).  g_residual_out: if non-NULL receives a copy of g (residual branch) */
+/* gx may alias g.  dgamma, dbeta, dbias may be NULL (all NULL: the parameter-gradient launch is skipped).  g_residual_out: if non-NULL receives a copy of g (residual branch)
+ * gx == NULL (the input needs no gradient, a frozen producer): the sums pass and the parameter launch only -- no apply pass;
+ * dgamma / dbeta as with gx (the same sums in the same order), dbias must be NULL and one of dgamma / dbeta not NULL. */
 int c2s_norm_bwd(const c2s_norm_desc* d, const float* x, const float* g, const float* gamma,
                  const float* group_stats, const float* row_ab, int relu, float* gx, float* dgamma,
                  float* dbeta, float* dbias, float* workspace, size_t ws_floats, const int* valid, void* stream);
@@ -310,6 +312,8 @@ int c2s_norm_fwd_onepass(const c2s_norm_desc* d, const float* x, const float* ga
                          float* running_mean, float* running_var, long long* num_batches_tracked, float* group_stats,
                          float* row_ab, const float* residual, float* y, int relu, const int* valid, float pad_value,
                          void* sync, size_t sync_bytes, void* stream);
+/* gx == NULL: as c2s_norm_bwd with gx == NULL (the two-pass sums pass, no frame-wide meeting; `sync` is not touched and may
+ * be NULL); the parameter gradients are bit-identical to the call with gx. */
 int c2s_norm_bwd_onepass(const c2s_norm_desc* d, const float* x, const float* g, const float* gamma,
                          const float* group_stats, const float* row_ab, int relu, float* gx, float* dgamma, float* dbeta,
                          float* dbias, float* workspace, size_t ws_floats, const int* valid, void* sync,
@@ -401,7 +405,11 @@ int c2s_ltae_attn_optional(const c2s_ltae_desc* d);
 int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd);
 size_t c2s_ltae_bwd_workspace_floats(const c2s_ltae_desc* d);
 /* g_emb [B,256,hw] or NULL; g_attn [16,B,T,hw] or NULL.  Outputs (all overwritten): gx [B,T,C,hw],
- * gU [16,C], gs0 [B,T,16], gWc [256,C] (embedding path only), gbc [256], ggamma [C], gbeta [C]. */
+ * gU [16,C], gs0 [B,T,16], gWc [256,C] (embedding path only), gbc [256], ggamma [C], gbeta [C].
+ * gx == NULL: the input needs no gradient.  No [B,T,C,hw] tensor is stored: the d x kernel of the family runs in a mode that
+ * forms the d gamma / d beta partials only (paths 0, 3, 4; path 5 drops the d x phase of its fused kernel), or is not
+ * launched where the heads kernel already wrote them (paths 1, 2, 6).  ggamma / gbeta: NULL together (in_norm frozen); with
+ * gx == NULL as well no d x kernel runs at all.  Every other output is bit-identical to the call with gx. */
 int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const float* gamma, const float* beta,
                       const float* U, const float* s0, const float* Wc, const float* bc, const float* pe,
                       const int* valid, const float* attn, const float* attn_pre, const float* stats,
@@ -487,6 +495,8 @@ int c2s_frame_mean_weights(const int* valid, float* v, int n_head, int B, int T,
 int c2s_temporal_aggregate_fwd(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
                                float* out, void* stream);
 size_t c2s_temporal_aggregate_bwd_workspace_floats(const c2s_agg_desc* d);
+/* gattn is accumulated into.  gx == NULL: gattn only, nothing of [B,T,C,H,W] size is stored (bit-identical gattn);
+ * gattn == NULL: gx only, the upsampling adjoint is not launched.  Not both NULL. */
 int c2s_temporal_aggregate_bwd(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
                                const float* gout, float* gx, int gx_accumulate, float* gattn,
                                float* workspace, size_t ws_floats, void* stream);
