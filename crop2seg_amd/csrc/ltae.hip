@@ -3331,23 +3331,14 @@ size_t lds_fwd_bytes(const c2s_ltae_desc* d) {
     const size_t rows = (size_t)d->T * (d->C + 1) > (size_t)NH * d->C ? (size_t)d->T * (d->C + 1) : (size_t)NH * d->C;
     return (rows * 4 + (size_t)d->T * 64 + (size_t)d->C * 24 + 1024 + 64) * sizeof(float);
 }
-bool use_lds_fwd(const c2s_ltae_desc* d) {
-    static const bool enabled = [] { const char* e = getenv("C2S_LTAE_LDS"); return !(e && e[0] == '0'); }();
-    return enabled && (d->C == 64 || d->C == 128 || d->C == 256) && d->HW % 4 == 0 && lds_fwd_bytes(d) <= 160 * 1024;
-}
 size_t lds_bwd_bytes(const c2s_ltae_desc* d) {
     return ((size_t)d->T * (d->C + 1) * 4 + (size_t)NH * d->C * 4 + 4 * (size_t)d->T * 64 + 1024 + 2 * (size_t)d->C + 128 + 1024 + 128) *
            sizeof(float);
-}
-bool use_lds_bwd(const c2s_ltae_desc* d) {
-    static const bool enabled = [] { const char* e = getenv("C2S_LTAE_LDS_BWD"); return !(e && e[0] == '0'); }();
-    return enabled && (d->C == 64 || d->C == 128 || d->C == 256) && d->HW % 4 == 0 && lds_bwd_bytes(d) <= 160 * 1024;
 }
 size_t fwd_lds(const c2s_ltae_desc* d) {
     const size_t CH = d->C > 64 ? 64 : d->C;
     return ((size_t)d->C * 32 + (size_t)d->T * 256 + 256 + NH * CH * 16) * 4;
 }
-int bwd_pt(const c2s_ltae_desc*) { return BPT; }
 size_t bwd1_lds(const c2s_ltae_desc* d) {
     const size_t PT = BPT;
     return ((size_t)d->C * 2 * PT + 256 * PT + NH * 32 * PT + 4 * (size_t)d->T * NH * PT + 2 * NH * PT) * 4;
@@ -3357,17 +3348,30 @@ size_t bwd2_lds(const c2s_ltae_desc* d) {
     return (256 * PT + 2 * (size_t)d->T * NH * PT + (size_t)d->C * 4 * PT + NH * 4 * PT + (size_t)d->C * 8) * 4;
 }
 
-// Series longer than 64 steps, or every shape under C2S_LTAE_LONG=1 (A/B runs, tests), go to the time-chunked family of
-// ltae_long.hip; every other shape keeps the families below.
-bool use_long(const c2s_ltae_desc* d) {
-    static const bool forced = [] { const char* e = getenv("C2S_LTAE_LONG"); return e && e[0] == '1'; }();
-    return forced || d->T > 64;
+// A/B switches of the family choice (tests and tools set them in child processes), read once per process.  C2S_LTAE_LONG=1
+// sends every shape to the time-chunked family; =0 turns off: C2S_LTAE_LDS / C2S_LTAE_LDS_BWD the LDS-resident 4-pixel
+// forward / backward, C2S_LTAE_REG / C2S_LTAE_REG_BWD the register-resident ones (REG=0 keeps the three-pass streaming
+// forward), C2S_LTAE_GX64 the 64-pixel d x kernel of the streaming backward.
+struct LtaeSwitches {
+    bool long_all, lds_fwd, lds_bwd, reg_fwd, reg_bwd, gx64;
+};
+const LtaeSwitches& ltae_switches() {
+    static const LtaeSwitches s = [] {
+        auto is = [](const char* name, char c) { const char* e = getenv(name); return e && e[0] == c; };
+        return LtaeSwitches{is("C2S_LTAE_LONG", '1'), !is("C2S_LTAE_LDS", '0'), !is("C2S_LTAE_LDS_BWD", '0'),
+                            !is("C2S_LTAE_REG", '0'), !is("C2S_LTAE_REG_BWD", '0'), !is("C2S_LTAE_GX64", '0')};
+    }();
+    return s;
 }
+
+// Series longer than 64 steps, or every shape under C2S_LTAE_LONG=1, go to the time-chunked family of ltae_long.hip; its
+// argument checks differ (check()).
+bool long_series(const c2s_ltae_desc* d) { return ltae_switches().long_all || d->T > 64; }
 
 int check(const c2s_ltae_desc* d) {
     C2S_REQUIRE(d && d->B > 0 && d->T > 0 && d->C > 0 && d->HW > 0, "ltae: bad shape");
     C2S_REQUIRE(d->n_head == NH && d->d_model == NH * DV, "ltae: only n_head=16, d_model=256 are built");
-    if (use_long(d)) {
+    if (long_series(d)) {
         C2S_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256, "ltae: the long-series kernels (T > 64) take C = 64, 128 or 256");
         C2S_REQUIRE((long)d->B * ((d->HW + LONG_PX - 1) / LONG_PX) < (1L << 31), "ltae: too many pixel tiles");
     } else {
@@ -3378,6 +3382,131 @@ int check(const c2s_ltae_desc* d) {
     C2S_REQUIRE(d->HW % 4 == 0, "ltae: h*w must be a multiple of 4");
     C2S_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "ltae: bad dropout p");
     return C2S_OK;
+}
+
+// ------------------------------------------------------------------------------------------ dispatch
+// Kernel families; the values are those c2s_ltae_paths reports (include/c2s_hip.h).
+enum LtaeFwd { FWD_TILE16 = 0, FWD_STREAM = 1, FWD_REG = 2, FWD_LDS4 = 3, FWD_LONG = 4 };
+enum LtaeBwd { BWD_TILE8 = 0, BWD_STREAM = 1, BWD_STREAM_GX64 = 2, BWD_REG = 3, BWD_REG_BITS = 4, BWD_LDS4 = 5, BWD_LONG = 6 };
+// The d x kernel after the heads kernel: ltae_stream_bwd_gx64_kernel<GX>, ltae_stream_bwd_gx_kernel<4>,
+// ltae_bwd_gx_kernel<GX>, or the d x phase of the fused ltae_lds_bwd_kernel<C, GX> (GX: gx given).
+enum LtaeDx { DX_NONE, DX_GX64, DX_GX4, DX_TILE8, DX_FUSED };
+enum LtaeGwc { GWC_ZERO, GWC_DIRECT, GWC_MFMA };     // d Wc: a memset (no g_emb), gwc_kernel, or gwc_mfma_kernel over pixel slices
+
+struct LtaeCall {             // what a call provides
+    bool g_emb;               // backward: g_emb given
+    bool no_attn;             // attn == NULL
+    bool fwd_ws;              // forward: workspace and attn_pre given
+    bool gx;                  // backward: gx given
+    bool gb;                  // backward: ggamma / gbeta given
+};
+
+struct LtaePlan {
+    LtaeFwd fwd;
+    LtaeBwd bwd;
+    int px;                   // pixels per backward tile
+    size_t tiles;             // backward tiles, B * ceil(HW / px)
+    LtaeDx dx;
+    int gb_tiles;             // tiles of the d gamma / d beta partials
+    bool gU_rows;             // gU = reduce_rows over part_U; else sum_over_pixels_kernel over V
+    LtaeGwc gwc;
+    int wc_slices;            // GWC_MFMA: pixel slices per head
+};
+
+// Backward workspace, offsets in floats: GS [16,B,T,HW] | V [B,16,C,HW] | Z [B,16,C,HW] | part_s0 [tiles][T][16] |
+// part_bc [tiles][256] | part_gb [tiles][C][2] | the slice sums of reduce_rows (doubles, behind up to 2 floats of
+// alignment), with tiles counted in 4 pixels, the smallest tile of any family: the total is the same for every plan.  Only
+// the 8-pixel family stores V; the others keep their per-pixel and per-tile data in that area: M [P][16][2] (streaming,
+// register-resident and time-chunked), ASG [2][16][P] (time-chunked), part_U [tiles][16][C] and behind it the d Wc slice
+// partials [slices][256][C].
+struct LtaeBwdWs {
+    size_t GS, V, Z, part_s0, part_bc, part_gb, rtmp, total;
+    size_t M, ASG, part_U, part_wc;
+};
+LtaeBwdWs ltae_bwd_ws(const c2s_ltae_desc* d, const LtaePlan& pl) {
+    const size_t P = (size_t)d->B * d->HW, tiles4 = (size_t)d->B * ((d->HW + 3) / 4);
+    const size_t kmax = (size_t)d->B * d->T * NH > (size_t)NH * d->C ? (size_t)d->B * d->T * NH : (size_t)NH * d->C;
+    LtaeBwdWs w = {};
+    w.V = w.GS + (size_t)NH * d->B * d->T * d->HW;
+    w.Z = w.V + (size_t)d->B * NH * d->C * d->HW;
+    w.part_s0 = w.Z + (size_t)d->B * NH * d->C * d->HW;
+    w.part_bc = w.part_s0 + tiles4 * d->T * NH;
+    w.part_gb = w.part_bc + tiles4 * 256;
+    w.rtmp = w.part_gb + tiles4 * d->C * 2;
+    w.total = w.rtmp + 2 + 2 * (size_t)RR_SLICES * (kmax > 256 ? kmax : 256);      // groups * RR_SLICES * K doubles, widest sum
+    size_t v = w.V;
+    if (pl.bwd != BWD_TILE8 && pl.bwd != BWD_LDS4) {
+        w.M = v;
+        v += P * NH * 2;
+    }
+    if (pl.bwd == BWD_LONG) {
+        w.ASG = v;
+        v += 2 * NH * P;
+    }
+    w.part_U = v;
+    w.part_wc = v + pl.tiles * NH * d->C;
+    return w;
+}
+
+// The kernels c2s_ltae_attn_fwd_ws and c2s_ltae_attn_bwd launch for a valid descriptor (check()) and a call, and how the
+// backward reduces its partials.  Every launch and query takes its family from here.
+LtaePlan ltae_plan(const c2s_ltae_desc* d, const LtaeCall& call) {
+    const LtaeSwitches& sw = ltae_switches();
+    LtaePlan pl = {};
+    if (long_series(d)) {
+        pl.fwd = FWD_LONG;
+        pl.bwd = BWD_LONG;
+    } else {
+        // the streaming kernels pay off once their 64-pixel tiles fill the chip twice
+        const bool stream = d->C == 64 && (long)d->B * ((d->HW + 63) / 64) >= 2L * c2s_cus();
+        // the register-resident forward (16-pixel tiles, x read once) once its tiles fill the chip 4 times; 32-bit element
+        // offsets into attn
+        const bool reg = sw.reg_fwd && d->C == 64 && d->HW % RPX == 0 && (long)d->B * (d->HW / RPX) >= 4L * c2s_cus() &&
+                         (long)NH * d->B * d->T * d->HW < (1L << 30);
+        // the register-resident backward addresses < 2^31 bytes per tensor through its buffer descriptors
+        const bool reg_bwd = reg && sw.reg_bwd && d->HW % 64 == 0 && (size_t)16 * d->B * d->T * d->HW < ((size_t)1 << 29) &&
+                             (size_t)d->T * d->C * d->HW < ((size_t)1 << 29);
+        const bool lds4 = (d->C == 64 || d->C == 128 || d->C == 256) && d->HW % 4 == 0;
+        if (reg) pl.fwd = FWD_REG;
+        else if (stream && call.fwd_ws) pl.fwd = FWD_STREAM;
+        else if (sw.lds_fwd && lds4 && lds_fwd_bytes(d) <= 160 * 1024) pl.fwd = FWD_LDS4;
+        else pl.fwd = FWD_TILE16;
+        if (call.g_emb && stream) {
+            if (reg_bwd) pl.bwd = call.no_attn ? BWD_REG_BITS : BWD_REG;
+            else pl.bwd = sw.gx64 && d->HW % 64 == 0 ? BWD_STREAM_GX64 : BWD_STREAM;
+        } else {
+            pl.bwd = sw.lds_bwd && lds4 && lds_bwd_bytes(d) <= 160 * 1024 ? BWD_LDS4 : BWD_TILE8;
+        }
+    }
+    switch (pl.bwd) {
+    case BWD_TILE8: pl.px = BPT; pl.dx = call.gx || call.gb ? DX_TILE8 : DX_NONE; break;
+    case BWD_STREAM: pl.px = SPT; pl.dx = call.gx ? DX_GX4 : DX_NONE; break;
+    case BWD_STREAM_GX64: pl.px = SPT; pl.dx = call.gx ? DX_GX64 : DX_NONE; break;
+    // the register-resident heads kernel leaves the d gamma / d beta partials to gx64, which then runs without its store
+    case BWD_REG: case BWD_REG_BITS: pl.px = RPX; pl.dx = call.gx || call.gb ? DX_GX64 : DX_NONE; break;
+    case BWD_LDS4: pl.px = 4; pl.dx = DX_FUSED; break;
+    case BWD_LONG: pl.px = LONG_PX; pl.dx = DX_NONE; break;      // ltae_long_bwd launches its d x kernel when gx is given
+    }
+    pl.tiles = (size_t)d->B * ((d->HW + pl.px - 1) / pl.px);
+    pl.gb_tiles = pl.bwd == BWD_REG || pl.bwd == BWD_REG_BITS ? d->B * (d->HW / 64) : (int)pl.tiles;
+    pl.gU_rows = pl.bwd != BWD_TILE8;
+    pl.gwc = call.g_emb ? GWC_DIRECT : GWC_ZERO;
+    // gwc_mfma_kernel (C = 64, 64-pixel tiles) where its slice partials fit behind part_U in the V area
+    if (call.g_emb && pl.bwd != BWD_TILE8 && pl.bwd != BWD_LDS4 && d->C == 64 && d->HW % 64 == 0) {
+        const int slices = d->B * (d->HW / 64) >= 32 ? 32 : d->B * (d->HW / 64);
+        const LtaeBwdWs w = ltae_bwd_ws(d, pl);
+        if (w.part_wc + (size_t)slices * 256 * d->C <= w.Z) {
+            pl.gwc = GWC_MFMA;
+            pl.wc_slices = slices;
+        }
+    }
+    return pl;
+}
+
+// The call the queries describe: a forward with a workspace and attn_pre, a backward that wants gx, ggamma and gbeta.
+LtaePlan query_plan(const c2s_ltae_desc* d, bool g_emb, bool no_attn) {
+    const LtaeCall call = {g_emb, no_attn, true, true, true};
+    return ltae_plan(d, call);
 }
 
 LtaeLongArgs long_args(const c2s_ltae_desc* d) {
@@ -3434,69 +3563,27 @@ extern "C" size_t c2s_ltae_fwd_workspace_floats(const c2s_ltae_desc* d) {
     return (size_t)d->C * NH + NH;          // Ut [C][16], cU [16] of the streaming path
 }
 
-// The streaming kernels pay off once the 64-pixel tiles fill the chip; below that the 16-pixel LDS kernel is used.
-static bool use_stream(const c2s_ltae_desc* d) {
-    const int cus = c2s_cus();
-    return d->C == 64 && (long)d->B * ((d->HW + 63) / 64) >= 2L * cus;
-}
-
-// The register-resident forward (16-pixel tiles, x read once) needs C == 64 and whole tiles; it pays off as soon as the tiles
-// fill the chip a few times over.  C2S_LTAE_REG=0 keeps the three-pass streaming kernel (A/B runs).
-static bool use_reg_fwd(const c2s_ltae_desc* d) {
-    static const bool enabled = [] { const char* e = getenv("C2S_LTAE_REG"); return !(e && e[0] == '0'); }();
-    return enabled && d->C == 64 && d->HW % RPX == 0 && (long)d->B * (d->HW / RPX) >= 4L * c2s_cus() &&
-           (long)NH * d->B * d->T * d->HW < (1L << 30);             // 32-bit element offsets into attn
-}
-
 extern "C" int c2s_ltae_uses_streaming(const c2s_ltae_desc* d) {
-    return d && check(d) == C2S_OK && !use_long(d) && (use_stream(d) || use_reg_fwd(d)) ? 1 : 0;
+    if (!d || check(d) != C2S_OK) return 0;
+    const LtaeFwd fwd = query_plan(d, true, false).fwd;
+    return fwd == FWD_STREAM || fwd == FWD_REG ? 1 : 0;
 }
 
 extern "C" int c2s_ltae_fwd_path(const c2s_ltae_desc* d) {
-    if (!d || check(d) != C2S_OK) return -1;
-    if (use_long(d)) return 4;
-    return use_reg_fwd(d) ? 2 : (use_stream(d) ? 1 : 0);
+    return d && check(d) == C2S_OK ? query_plan(d, true, false).fwd : -1;
 }
 
-static bool reg_bwd_enabled() {
-    static const bool on = [] { const char* e = getenv("C2S_LTAE_REG_BWD"); return !(e && e[0] == '0'); }();
-    return on;
-}
-// register-resident heads kernel + 64-px dx kernel; its buffer descriptors address < 2^31 bytes per tensor
-static bool use_reg_bwd(const c2s_ltae_desc* d, bool with_emb) {
-    return with_emb && use_stream(d) && reg_bwd_enabled() && use_reg_fwd(d) && d->HW % 64 == 0 &&
-           (size_t)16 * d->B * d->T * d->HW < ((size_t)1 << 29) && (size_t)d->T * d->C * d->HW < ((size_t)1 << 29);
-}
-
-// 1 when a caller that never reads the post-dropout weights may pass attn == NULL to c2s_ltae_attn_fwd_ws AND to
-// c2s_ltae_attn_bwd (both take the register-resident kernels for this shape; RNG mask, embedding output)
 extern "C" int c2s_ltae_attn_optional(const c2s_ltae_desc* d) {
-    return d && check(d) == C2S_OK && !use_long(d) && d->keep == nullptr && use_reg_bwd(d, true) ? 1 : 0;
+    return d && check(d) == C2S_OK && d->keep == nullptr && query_plan(d, true, true).bwd == BWD_REG_BITS ? 1 : 0;
 }
 
-// Which kernels c2s_ltae_attn_fwd_ws (called with a workspace and attn_pre) and c2s_ltae_attn_bwd launch for this descriptor.
-// *fwd: 0 = 16-pixel LDS kernel, 1 = three-pass streaming, 2 = register-resident, 3 = LDS-resident 4-pixel.
-// *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>, 2 = streaming heads + gx64, 3 = register-resident heads<false> +
-// gx64, 4 = register-resident heads<true> + gx64 (attn == NULL: d->keep_bits set, RNG mask), 5 = LDS-resident 4-pixel.
-// Time-chunked family (ltae_long.hip: T > 64 or C2S_LTAE_LONG=1): *fwd = 4, *bwd = 6.
-// with_emb: whether the backward gets g_emb.  Pure query; returns C2S_EINVAL for a bad descriptor.
 extern "C" int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd) {
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(fwd && bwd, "ltae_paths: null pointer");
-    if (use_long(d)) {
-        *fwd = 4;
-        *bwd = 6;
-        return C2S_OK;
-    }
-    *fwd = use_reg_fwd(d) ? 2 : (use_stream(d) ? 1 : (use_lds_fwd(d) ? 3 : 0));
-    const bool emb = with_emb != 0;
-    if (emb && use_stream(d)) {
-        static const bool gx64 = [] { const char* e = getenv("C2S_LTAE_GX64"); return !(e && e[0] == '0'); }();
-        if (use_reg_bwd(d, true)) *bwd = d->keep_bits != nullptr && d->keep == nullptr ? 4 : 3;
-        else *bwd = gx64 && d->C == 64 && d->HW % 64 == 0 ? 2 : 1;
-    } else {
-        *bwd = use_lds_bwd(d) ? 5 : 0;
-    }
+    // attn is absent exactly when the forward left the keep flags in d->keep_bits (RNG mask)
+    const LtaePlan pl = query_plan(d, with_emb != 0, d->keep_bits != nullptr && d->keep == nullptr);
+    *fwd = pl.fwd;
+    *bwd = pl.bwd;
     return C2S_OK;
 }
 
@@ -3506,9 +3593,13 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
                                     float* workspace, size_t ws_floats, void* stream) {
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(x && gamma && beta && U && s0 && stats, "ltae_fwd: null pointer");
+    LtaeCall call = {};
+    call.no_attn = attn == nullptr;
+    call.fwd_ws = workspace != nullptr && attn_pre != nullptr;
+    const LtaePlan pl = ltae_plan(d, call);
     // attn == NULL: the caller never reads the post-dropout weights (TimeUNet without return_att); only the register-resident
     // forward skips the store; a later backward then needs attn_pre and the RNG mask (c2s_ltae_attn_optional)
-    C2S_REQUIRE(attn != nullptr || (!use_long(d) && use_reg_fwd(d) && emb != nullptr),
+    C2S_REQUIRE(attn != nullptr || (pl.fwd == FWD_REG && emb != nullptr),
                 "ltae_fwd: attn may only be NULL on the register-resident path (c2s_ltae_fwd_path == 2) with an embedding output");
     C2S_REQUIRE(emb == nullptr || (Wc && bc && pe), "ltae_fwd: embedding output needs Wc, bc, pe");
     LtaeParams p = {};
@@ -3516,20 +3607,22 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
     p.x = x; p.gamma = gamma; p.beta = beta; p.U = U; p.s0 = s0; p.Wc = Wc; p.bc = bc; p.pe = pe; p.valid = valid;
     p.attn = attn; p.attn_pre = attn_pre; p.emb = emb; p.stats = stats;
     hipStream_t st = (hipStream_t)stream;
-    if (use_long(d)) {
+    c2s_ensure_init();
+    switch (pl.fwd) {
+    case FWD_LONG: {
         LtaeLongArgs a = long_args(d);
         a.x = x; a.gamma = gamma; a.beta = beta; a.U = U; a.s0 = s0; a.Wc = Wc; a.bc = bc; a.pe = pe; a.valid = valid;
         a.attn = attn; a.attn_pre = attn_pre; a.emb = emb; a.stats = stats;
         return ltae_long_fwd(a, st);
     }
-    if (use_reg_fwd(d)) {
+    case FWD_REG: {
         const bool h32 = (unsigned long long)NH * d->B * d->HW * ((d->T + 1) / 2) <= 0xFFFFFFFFull;
         if (h32) hipLaunchKernelGGL(ltae_reg_fwd_kernel<true>, dim3(d->B * (d->HW / RPX)), dim3(512), R_FLOATS * sizeof(float), st, p);
         else hipLaunchKernelGGL(ltae_reg_fwd_kernel<false>, dim3(d->B * (d->HW / RPX)), dim3(512), R_FLOATS * sizeof(float), st, p);
         C2S_CHECK_LAUNCH("ltae_reg_fwd");
         return C2S_OK;
     }
-    if (workspace != nullptr && attn_pre != nullptr && use_stream(d)) {
+    case FWD_STREAM: {
         C2S_REQUIRE(ws_floats >= c2s_ltae_fwd_workspace_floats(d), "ltae_fwd: workspace too small");
         float* Ut = workspace;
         float* cU = workspace + (size_t)d->C * NH;
@@ -3539,8 +3632,7 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
         C2S_CHECK_LAUNCH("ltae_stream_fwd");
         return C2S_OK;
     }
-    c2s_ensure_init();
-    if (use_lds_fwd(d)) {
+    case FWD_LDS4: {
         const dim3 grid(d->B * (d->HW / 4));
         const size_t lb = lds_fwd_bytes(d);
         if (d->C == 64) hipLaunchKernelGGL(ltae_lds_fwd_kernel<64>, grid, dim3(256), lb, st, p);
@@ -3549,8 +3641,11 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
         C2S_CHECK_LAUNCH("ltae_lds_fwd");
         return C2S_OK;
     }
-    hipLaunchKernelGGL(ltae_fwd_kernel, dim3(d->B * ((d->HW + 15) / 16)), dim3(256), fwd_lds(d), st, p);
-    C2S_CHECK_LAUNCH("ltae_fwd");
+    case FWD_TILE16:
+        hipLaunchKernelGGL(ltae_fwd_kernel, dim3(d->B * ((d->HW + 15) / 16)), dim3(256), fwd_lds(d), st, p);
+        C2S_CHECK_LAUNCH("ltae_fwd");
+        return C2S_OK;
+    }
     return C2S_OK;
 }
 
@@ -3561,17 +3656,8 @@ extern "C" int c2s_ltae_attn_fwd(const c2s_ltae_desc* d, const float* x, const f
     return c2s_ltae_attn_fwd_ws(d, x, gamma, beta, U, s0, Wc, bc, pe, valid, attn, attn_pre, emb, stats, nullptr, 0, stream);
 }
 
-// workspace: GS [16,B,T,HW] | V [B,16,C,HW] | Z [B,16,C,HW] | part_s0 [tiles][T][16] | part_bc [tiles][256]
-//            | part_gb [tiles][C][2] | the slice sums of reduce_rows (doubles)
-static size_t reduce_tmp_floats(const c2s_ltae_desc* d) {      // groups * RR_SLICES * K doubles for the widest of the three sums
-    const size_t kmax = (size_t)d->B * d->T * NH > (size_t)NH * d->C ? (size_t)d->B * d->T * NH : (size_t)NH * d->C;
-    return 2 * (size_t)RR_SLICES * (kmax > 256 ? kmax : 256);
-}
 extern "C" size_t c2s_ltae_bwd_workspace_floats(const c2s_ltae_desc* d) {
-    if (!d) return 0;
-    const size_t tiles = (size_t)d->B * ((d->HW + 3) / 4);   // upper bound (4-pixel tiles)
-    return (size_t)NH * d->B * d->T * d->HW + 2 * (size_t)d->B * NH * d->C * d->HW + tiles * d->T * NH + tiles * 256 +
-           tiles * d->C * 2 + 2 + reduce_tmp_floats(d);
+    return d ? ltae_bwd_ws(d, LtaePlan{}).total : 0;
 }
 
 extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const float* gamma, const float* beta,
@@ -3584,128 +3670,131 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
     C2S_REQUIRE(x && gamma && beta && U && Wc && bc && pe && attn_pre && stats && gU && gs0 && gWc && gbc && workspace,
                 "ltae_bwd: null pointer");
     C2S_REQUIRE((ggamma == nullptr) == (gbeta == nullptr), "ltae_bwd: ggamma and gbeta are NULL together");
-    const bool want_gb = ggamma != nullptr;    // gx == NULL: no input gradient is stored (include/c2s_hip.h)
     C2S_REQUIRE(ws_floats >= c2s_ltae_bwd_workspace_floats(d), "ltae_bwd: workspace too small");
     (void)s0; (void)valid;
-    const bool long_path = use_long(d);
-    const bool stream_path = !long_path && g_emb != nullptr && use_stream(d);
-    const bool reg_heads = !long_path && use_reg_bwd(d, g_emb != nullptr);
-    C2S_REQUIRE(attn != nullptr || (reg_heads && d->keep_bits != nullptr),
+    LtaeCall call = {};
+    call.g_emb = g_emb != nullptr;
+    call.no_attn = attn == nullptr;
+    call.gx = gx != nullptr;          // gx == NULL: no input gradient is stored (include/c2s_hip.h)
+    call.gb = ggamma != nullptr;
+    const LtaePlan pl = ltae_plan(d, call);
+    C2S_REQUIRE(attn != nullptr || (pl.bwd == BWD_REG_BITS && d->keep_bits != nullptr),
                 "ltae_bwd: attn may only be NULL where the forward could omit it (register-resident path) and left the keep flags in d->keep_bits");
-    const bool lds_path = !long_path && !stream_path && use_lds_bwd(d);      // fused LDS-resident kernel on 4-pixel tiles (small maps)
-    const int PT = long_path ? LONG_PX : (reg_heads ? RPX : (stream_path ? SPT : (lds_path ? 4 : bwd_pt(d))));
-    const size_t tiles = (size_t)d->B * ((d->HW + PT - 1) / PT);
-    const size_t tiles_ws = (size_t)d->B * ((d->HW + 3) / 4);
+    const LtaeBwdWs ws = ltae_bwd_ws(d, pl);
     LtaeParams p = {};
     fill(p, d);
     p.x = x; p.gamma = gamma; p.beta = beta; p.U = U; p.Wc = Wc; p.bc = bc; p.pe = pe;
     p.attn_in = attn; p.attn_pre_in = attn_pre; p.stats_in = stats; p.g_emb = g_emb; p.g_attn = g_attn; p.gx = gx;
-    p.GS = workspace;
-    p.V = p.GS + (size_t)NH * d->B * d->T * d->HW;
-    p.Z = p.V + (size_t)d->B * NH * d->C * d->HW;
-    p.part_s0 = p.Z + (size_t)d->B * NH * d->C * d->HW;
-    p.part_bc = p.part_s0 + tiles_ws * d->T * NH;
-    p.part_gb = p.part_bc + tiles_ws * 256;
-    float* rt_ = p.part_gb + tiles_ws * d->C * 2;
+    p.GS = workspace + ws.GS;
+    p.V = workspace + ws.V;
+    p.Z = workspace + ws.Z;
+    p.part_s0 = workspace + ws.part_s0;
+    p.part_bc = workspace + ws.part_bc;
+    p.part_gb = workspace + ws.part_gb;
+    float* rt_ = workspace + ws.rtmp;
     double* rtmp = reinterpret_cast<double*>(rt_ + (((uintptr_t)rt_ >> 2) & 1));      // 8-byte aligned
+    float* part_U = workspace + ws.part_U;
     hipStream_t st = (hipStream_t)stream;
     c2s_ensure_init();
     StreamBwd sb = {};
-    if (long_path) {
-        // the V area of the workspace holds M [P][16][2], sum_t attn / sum_t gs [2][16][P] and part_U [tiles][16][C]
-        const size_t P = (size_t)d->B * d->HW;
+    const dim3 tiles(pl.tiles);
+    switch (pl.bwd) {
+    case BWD_LONG: {
         LtaeLongArgs a = long_args(d);
         a.x = x; a.gamma = gamma; a.beta = beta; a.U = U; a.Wc = Wc; a.bc = bc; a.pe = pe;
         a.attn_in = attn; a.attn_pre_in = attn_pre; a.stats_in = stats; a.g_emb = g_emb; a.g_attn = g_attn; a.gx = gx;
         a.GS = p.GS; a.Z = p.Z; a.part_s0 = p.part_s0; a.part_bc = p.part_bc; a.part_gb = p.part_gb;
-        a.M = sb.M = p.V;
-        a.ASG = p.V + P * NH * 2;
-        a.part_U = sb.part_U = a.ASG + 2 * NH * P;
+        a.M = workspace + ws.M;
+        a.ASG = workspace + ws.ASG;
+        a.part_U = part_U;
         if (int rc = ltae_long_bwd(a, st)) return rc;      // gx == NULL: the vz kernel wrote the partials, no d x kernel
-    } else if (stream_path) {
-        // the V area of the workspace is not used by the streaming kernels: it holds M [P][16][2] and part_U [tiles][16][C]
-        sb.M = p.V;
-        sb.part_U = p.V + (size_t)d->B * d->HW * NH * 2;
-        const size_t lds1 = ((size_t)NH * d->C * SPT + NH * 2 * SPT + 2 * NH * SPT + 2 * SCH * 4 * SPT * 4 + (size_t)d->T * DV) * sizeof(float);
-        if (reg_heads) {
-            sb.gb64 = p.part_gb;                   // d gamma / d beta partials come from the dx kernel, one per 64-pixel tile
-            if (attn == nullptr) hipLaunchKernelGGL(ltae_reg_bwd_heads_kernel<true>, dim3(tiles), dim3(512), RB_FLOATS * sizeof(float), st, p, sb);
-            else hipLaunchKernelGGL(ltae_reg_bwd_heads_kernel<false>, dim3(tiles), dim3(512), RB_FLOATS * sizeof(float), st, p, sb);
+        break;
+    }
+    case BWD_STREAM: case BWD_STREAM_GX64: case BWD_REG: case BWD_REG_BITS: {
+        sb.M = workspace + ws.M;
+        sb.part_U = part_U;
+        if (pl.bwd == BWD_STREAM || pl.bwd == BWD_STREAM_GX64) {
+            const size_t lds1 = ((size_t)NH * d->C * SPT + NH * 2 * SPT + 2 * NH * SPT + 2 * SCH * 4 * SPT * 4 + (size_t)d->T * DV) * sizeof(float);
+            hipLaunchKernelGGL(ltae_stream_bwd_heads_kernel<4>, tiles, dim3(1024), lds1, st, p, sb);
         } else {
-            hipLaunchKernelGGL(ltae_stream_bwd_heads_kernel<4>, dim3(tiles), dim3(1024), lds1, st, p, sb);
+            sb.gb64 = p.part_gb;                   // d gamma / d beta partials come from the dx kernel, one per 64-pixel tile
+            if (pl.bwd == BWD_REG_BITS) hipLaunchKernelGGL(ltae_reg_bwd_heads_kernel<true>, tiles, dim3(512), RB_FLOATS * sizeof(float), st, p, sb);
+            else hipLaunchKernelGGL(ltae_reg_bwd_heads_kernel<false>, tiles, dim3(512), RB_FLOATS * sizeof(float), st, p, sb);
         }
         C2S_CHECK_LAUNCH("ltae_stream_bwd_heads");
-        const size_t lds2 = ((size_t)NH * d->C * SPT + 2 * SCH * 4 * SPT * 4) * sizeof(float);
-        static const bool gx64 = [] { const char* e = getenv("C2S_LTAE_GX64"); return !(e && e[0] == '0'); }();
-        // without gx: the streaming heads kernel wrote the d gamma / d beta partials itself (paths 1, 2): no d x kernel; the
-        // register-resident one leaves them to gx64 (paths 3, 4), which then runs without its store
-        if (gx == nullptr) {
-            if (reg_heads && want_gb)
-                hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel<false>, dim3(d->B * (d->HW / 64)), dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
-        } else if ((gx64 || reg_heads) && d->C == 64 && d->HW % 64 == 0) {
-            hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel<true>, dim3(d->B * (d->HW / 64)), dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
-        } else {
-            hipLaunchKernelGGL(ltae_stream_bwd_gx_kernel<4>, dim3(tiles), dim3(1024), lds2, st, p, sb);
-        }
-        C2S_CHECK_LAUNCH("ltae_stream_bwd_gx");
-    } else if (lds_path) {
-        sb.part_U = p.V;                           // [tiles][16][C] <= the V area [B][16][C][HW]
+        break;
+    }
+    case BWD_LDS4: {
+        sb.part_U = part_U;
         const size_t lb = lds_bwd_bytes(d);
         if (gx != nullptr) {
-            if (d->C == 64) hipLaunchKernelGGL(ltae_lds_bwd_kernel<64>, dim3(tiles), dim3(256), lb, st, p, sb);
-            else if (d->C == 128) hipLaunchKernelGGL(ltae_lds_bwd_kernel<128>, dim3(tiles), dim3(256), lb, st, p, sb);
-            else hipLaunchKernelGGL(ltae_lds_bwd_kernel<256>, dim3(tiles), dim3(256), lb, st, p, sb);
-        } else {                                   // fused kernel: its d x phase forms the d gamma / d beta partials only
-            if (d->C == 64) hipLaunchKernelGGL((ltae_lds_bwd_kernel<64, false>), dim3(tiles), dim3(256), lb, st, p, sb);
-            else if (d->C == 128) hipLaunchKernelGGL((ltae_lds_bwd_kernel<128, false>), dim3(tiles), dim3(256), lb, st, p, sb);
-            else hipLaunchKernelGGL((ltae_lds_bwd_kernel<256, false>), dim3(tiles), dim3(256), lb, st, p, sb);
+            if (d->C == 64) hipLaunchKernelGGL(ltae_lds_bwd_kernel<64>, tiles, dim3(256), lb, st, p, sb);
+            else if (d->C == 128) hipLaunchKernelGGL(ltae_lds_bwd_kernel<128>, tiles, dim3(256), lb, st, p, sb);
+            else hipLaunchKernelGGL(ltae_lds_bwd_kernel<256>, tiles, dim3(256), lb, st, p, sb);
+        } else {                                   // its d x phase forms the d gamma / d beta partials only
+            if (d->C == 64) hipLaunchKernelGGL((ltae_lds_bwd_kernel<64, false>), tiles, dim3(256), lb, st, p, sb);
+            else if (d->C == 128) hipLaunchKernelGGL((ltae_lds_bwd_kernel<128, false>), tiles, dim3(256), lb, st, p, sb);
+            else hipLaunchKernelGGL((ltae_lds_bwd_kernel<256, false>), tiles, dim3(256), lb, st, p, sb);
         }
         C2S_CHECK_LAUNCH("ltae_lds_bwd");
-    } else {
-        hipLaunchKernelGGL(ltae_bwd_heads_kernel, dim3(tiles), dim3(256), bwd1_lds(d), st, p);
+        break;
+    }
+    case BWD_TILE8:
+        hipLaunchKernelGGL(ltae_bwd_heads_kernel, tiles, dim3(256), bwd1_lds(d), st, p);
         C2S_CHECK_LAUNCH("ltae_bwd_heads");
-        if (gx != nullptr) hipLaunchKernelGGL(ltae_bwd_gx_kernel<true>, dim3(tiles), dim3(256), bwd2_lds(d), st, p);
-        else if (want_gb) hipLaunchKernelGGL(ltae_bwd_gx_kernel<false>, dim3(tiles), dim3(256), bwd2_lds(d), st, p);
+        break;
+    }
+    switch (pl.dx) {
+    case DX_GX64: {
+        const dim3 grid(d->B * (d->HW / 64));
+        if (gx != nullptr) hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel<true>, grid, dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
+        else hipLaunchKernelGGL(ltae_stream_bwd_gx64_kernel<false>, grid, dim3(1024), GX_FLOATS * sizeof(float) + 8192, st, p, sb);
+        C2S_CHECK_LAUNCH("ltae_stream_bwd_gx");
+        break;
+    }
+    case DX_GX4: {
+        const size_t lds2 = ((size_t)NH * d->C * SPT + 2 * SCH * 4 * SPT * 4) * sizeof(float);
+        hipLaunchKernelGGL(ltae_stream_bwd_gx_kernel<4>, tiles, dim3(1024), lds2, st, p, sb);
+        C2S_CHECK_LAUNCH("ltae_stream_bwd_gx");
+        break;
+    }
+    case DX_TILE8:
+        if (gx != nullptr) hipLaunchKernelGGL(ltae_bwd_gx_kernel<true>, tiles, dim3(256), bwd2_lds(d), st, p);
+        else hipLaunchKernelGGL(ltae_bwd_gx_kernel<false>, tiles, dim3(256), bwd2_lds(d), st, p);
         C2S_CHECK_LAUNCH("ltae_bwd_gx");
+        break;
+    case DX_NONE: case DX_FUSED:
+        break;
     }
     // reductions
-    const int tpb = (d->HW + PT - 1) / PT;
-    {   // gs0[b][t][h] = sum over the tiles of b
-        reduce_rows(p.part_s0, gs0, d->B, tpb, d->T * NH, rtmp, st);
-        C2S_CHECK_LAUNCH("ltae_reduce_s0");
-    }
-    reduce_rows(p.part_bc, gbc, 1, (int)tiles, 256, rtmp, st);
+    reduce_rows(p.part_s0, gs0, d->B, (d->HW + pl.px - 1) / pl.px, d->T * NH, rtmp, st);      // gs0[b][t][h]: the tiles of b
+    C2S_CHECK_LAUNCH("ltae_reduce_s0");
+    reduce_rows(p.part_bc, gbc, 1, (int)pl.tiles, 256, rtmp, st);
     C2S_CHECK_LAUNCH("ltae_reduce_bc");
-    if (want_gb) {   // interleaved (dgamma, dbeta) partials -> the two outputs
-        const int gb_tiles = reg_heads ? d->B * (d->HW / 64) : (int)tiles;
-        reduce_rows(p.part_gb, ggamma, 1, gb_tiles, 2 * d->C, rtmp, st, gbeta);
+    if (call.gb) {   // interleaved (dgamma, dbeta) partials -> the two outputs
+        reduce_rows(p.part_gb, ggamma, 1, pl.gb_tiles, 2 * d->C, rtmp, st, gbeta);
         C2S_CHECK_LAUNCH("ltae_reduce_gb");
     }
-    if (stream_path || lds_path || long_path) {
-        reduce_rows(sb.part_U, gU, 1, (int)tiles, NH * d->C, rtmp, st);
-    } else {
-        hipLaunchKernelGGL(sum_over_pixels_kernel, dim3(NH * d->C), dim3(64), 0, st, p.V, gU, d->B, NH * d->C, d->HW);
-    }
+    if (pl.gU_rows) reduce_rows(part_U, gU, 1, (int)pl.tiles, NH * d->C, rtmp, st);
+    else hipLaunchKernelGGL(sum_over_pixels_kernel, dim3(NH * d->C), dim3(64), 0, st, p.V, gU, d->B, NH * d->C, d->HW);
     C2S_CHECK_LAUNCH("ltae_gU");
-    const int wc_slices = d->HW % 64 == 0 ? (d->B * (d->HW / 64) >= 32 ? 32 : d->B * (d->HW / 64)) : 0;
-    const bool long_wc = long_path && d->C == 64 && d->HW % 64 == 0 &&      // the slice partials fit in the V area
-                         (size_t)NH * d->B * d->HW * 4 + tiles * NH * d->C + (size_t)wc_slices * 256 * d->C <=
-                             (size_t)d->B * NH * d->C * d->HW;
-    if (g_emb != nullptr && (stream_path || long_wc) && d->HW % 64 == 0) {
-        // 32 pixel slices per head; the partials live behind part_U in the (unused) V area of the workspace
-        const int ntiles = d->B * (d->HW / 64);
-        const int slices = wc_slices;
-        const int tps = (ntiles + slices - 1) / slices;
-        float* part_wc = sb.part_U + tiles * NH * d->C;
-        hipLaunchKernelGGL(gwc_mfma_kernel, dim3(NH, slices), dim3(256), 0, st, g_emb, p.Z, part_wc, d->B, d->HW, tps);
+    switch (pl.gwc) {
+    case GWC_MFMA: {
+        float* part_wc = workspace + ws.part_wc;
+        const int tps = (d->B * (d->HW / 64) + pl.wc_slices - 1) / pl.wc_slices;       // 64-pixel tiles per slice
+        hipLaunchKernelGGL(gwc_mfma_kernel, dim3(NH, pl.wc_slices), dim3(256), 0, st, g_emb, p.Z, part_wc, d->B, d->HW, tps);
         C2S_CHECK_LAUNCH("ltae_gWc_mfma");
-        reduce_rows(part_wc, gWc, 1, slices, NH * DV * d->C, nullptr, st);
+        reduce_rows(part_wc, gWc, 1, pl.wc_slices, NH * DV * d->C, nullptr, st);
         C2S_CHECK_LAUNCH("ltae_gWc_reduce");
-    } else if (g_emb != nullptr) {
+        break;
+    }
+    case GWC_DIRECT:
         hipLaunchKernelGGL(gwc_kernel, dim3(NH * d->C), dim3(256), 0, st, g_emb, p.Z, gWc, d->B, d->C, d->HW);
         C2S_CHECK_LAUNCH("ltae_gWc");
-    } else {
+        break;
+    case GWC_ZERO:
         hipMemsetAsync(gWc, 0, (size_t)256 * d->C * sizeof(float), st);
+        break;
     }
     return C2S_OK;
 }

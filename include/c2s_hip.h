@@ -369,42 +369,40 @@ typedef struct c2s_ltae_desc {
 int c2s_ltae_attn_fwd(const c2s_ltae_desc* d, const float* x, const float* gamma, const float* beta,
                       const float* U, const float* s0, const float* Wc, const float* bc, const float* pe,
                       const int* valid, float* attn, float* attn_pre, float* emb, float* stats, void* stream);
-/* Same operation with a caller-provided workspace (c2s_ltae_fwd_workspace_floats).  When the pixel count fills the chip
- * (TimeUNet: L-TAE at full resolution) and C == 64 the full-resolution kernels are used: the register-resident kernel on
- * 16-pixel tiles (x read once; h*w a multiple of 16, >= 4 tiles per CU) or, for other shapes, the streaming kernel on
- * 64-pixel tiles (lane = pixel, 256-byte row segments, weights through the scalar cache); otherwise, or with
- * workspace == NULL, the 16-pixel LDS kernel of c2s_ltae_attn_fwd.  All of them compute the same function to fp32
- * rounding; the choice is made from the descriptor alone. */
+/* Same operation with a caller-provided workspace (c2s_ltae_fwd_workspace_floats).  The kernel family (the table at
+ * c2s_ltae_paths) is chosen from the descriptor, the device's CU count and whether workspace and attn_pre are given: the
+ * three-pass streaming family needs both.  All of them compute the same function to fp32 rounding. */
 size_t c2s_ltae_fwd_workspace_floats(const c2s_ltae_desc* d);
 int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, const float* gamma, const float* beta,
                          const float* U, const float* s0, const float* Wc, const float* bc, const float* pe,
                          const int* valid, float* attn, float* attn_pre, float* emb, float* stats,
                          float* workspace, size_t ws_floats, void* stream);
-/* 1 when this shape runs the full-resolution (register-resident or streaming) kernels on the current device (forward: with
- * a workspace and attn_pre; backward: additionally needs g_emb), 0 for the 16-/8-pixel LDS kernels.  Lets tests assert
- * which path they cover. */
+/* 1 when c2s_ltae_paths reports forward family 1 or 2 (the full-resolution kernels), else 0.  Lets tests assert which
+ * path they cover. */
 int c2s_ltae_uses_streaming(const c2s_ltae_desc* d);
-/* Which forward kernel c2s_ltae_attn_fwd_ws launches for this shape: 0 = the 16-pixel LDS kernel (ltae_fwd_kernel: small maps),
- * 1 = the three-pass streaming kernels (ltae_prep + ltae_stream_fwd), 2 = the register-resident kernel (ltae_reg_fwd_kernel),
- * 4 = the time-chunked kernels of T > 64 (ltae_long.hip; attn_pre is their score scratch);
- * -1 = bad descriptor.  (Measurement harnesses label their numbers with it.) */
+/* The forward family c2s_ltae_paths reports; -1 = bad descriptor.  (Measurement harnesses label their numbers with it.) */
 int c2s_ltae_fwd_path(const c2s_ltae_desc* d);
 /* 1 when a caller that never reads the post-dropout attention weights (TimeUNet_v1.forward without return_att,
- * timeunet.py:176-178,204-205) may pass attn == NULL to c2s_ltae_attn_fwd_ws AND to c2s_ltae_attn_bwd: both then take the
- * register-resident kernels, the forward stores attn_pre and the keep flags as bits (d->keep_bits: 16*B*T*hw floats less to
+ * timeunet.py:176-178,204-205) may pass attn == NULL to c2s_ltae_attn_fwd_ws AND to c2s_ltae_attn_bwd: backward family 4
+ * of c2s_ltae_paths.  The forward then stores attn_pre and the keep flags as bits (d->keep_bits: 16*B*T*hw floats less to
  * write) and the backward reads those (as many floats less to read).  Needs d->keep_bits on both calls, the RNG mask
  * (d->keep == NULL) and the embedding output. */
 int c2s_ltae_attn_optional(const c2s_ltae_desc* d);
-/* Which kernel families c2s_ltae_attn_fwd_ws (with a workspace and attn_pre) and c2s_ltae_attn_bwd (g_emb given iff with_emb)
- * launch for this descriptor on the current device; a pure query.  *fwd: 0 = 16-pixel LDS kernel, 1 = three-pass streaming,
- * 2 = register-resident, 3 = LDS-resident 4-pixel.  *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>,
- * 2 = streaming heads + gx64, 3 = register-resident heads + gx64, 4 = the same re-deriving the keep flags from d->keep_bits
- * (attn == NULL), 5 = LDS-resident 4-pixel.  Series longer than 64 steps (every shape when the environment sets
- * C2S_LTAE_LONG=1) take the time-chunked family: *fwd = 4, *bwd = 6 (C = 64, 128 or 256; attn and attn_pre required, attn
- * never optional). */
+/* Which kernel families c2s_ltae_attn_fwd_ws (with a workspace and attn_pre) and c2s_ltae_attn_bwd (g_emb given iff
+ * with_emb; attn NULL exactly when d->keep_bits is set and d->keep is NULL) launch for this descriptor on the current
+ * device; a pure query.
+ *   *fwd: 0 = 16-pixel LDS kernel (ltae_fwd_kernel: small maps), 1 = three-pass streaming (ltae_prep + ltae_stream_fwd),
+ *         2 = register-resident (ltae_reg_fwd_kernel; the only one that may skip attn), 3 = LDS-resident 4-pixel
+ *         (ltae_lds_fwd_kernel), 4 = time-chunked (ltae_long.hip; attn_pre is its score scratch).
+ *   *bwd: 0 = 8-pixel heads + gx, 1 = streaming heads + gx<4>, 2 = streaming heads + gx64, 3 = register-resident heads +
+ *         gx64, 4 = the same re-deriving the keep flags from d->keep_bits (attn == NULL), 5 = LDS-resident 4-pixel,
+ *         6 = time-chunked.
+ * Series longer than 64 steps (every shape when the environment sets C2S_LTAE_LONG=1) take the time-chunked family: *fwd =
+ * 4, *bwd = 6 (C = 64, 128 or 256; attn and attn_pre required, attn never optional). */
 int c2s_ltae_paths(const c2s_ltae_desc* d, int with_emb, int* fwd, int* bwd);
 size_t c2s_ltae_bwd_workspace_floats(const c2s_ltae_desc* d);
-/* g_emb [B,256,hw] or NULL; g_attn [16,B,T,hw] or NULL.  Outputs (all overwritten): gx [B,T,C,hw],
+/* Families as at c2s_ltae_paths, with g_emb and attn as given here.
+ * g_emb [B,256,hw] or NULL; g_attn [16,B,T,hw] or NULL.  Outputs (all overwritten): gx [B,T,C,hw],
  * gU [16,C], gs0 [B,T,16], gWc [256,C] (embedding path only), gbc [256], ggamma [C], gbeta [C].
  * gx == NULL: the input needs no gradient.  No [B,T,C,hw] tensor is stored: the d x kernel of the family runs in a mode that
  * forms the d gamma / d beta partials only (paths 0, 3, 4; path 5 drops the d x phase of its fused kernel), or is not

@@ -258,6 +258,33 @@ def test_ltae_paths_query_without_gpu():
     assert paths(2, 39, 128, 64) == (3, 5)
     assert paths(1, 48, 128, 16) == (3, 0)
     assert paths(2, 39, 256, 16) == (0, 0)
+    assert paths(8, 122, 64, 128 * 128) == (4, 6)
+    assert paths(4, 32, 128, 256) == (3, 5)
     d = _lib.LtaeDesc(2, 9, 48, 16, 16, 256, 1e-5, 0.0, 0, None, None)      # C not a multiple of 64
     f, b = ctypes.c_int(), ctypes.c_int()
     assert L.c2s_ltae_paths(ctypes.byref(d), 1, ctypes.byref(f), ctypes.byref(b)) == -1
+
+    # the other queries are views of the same choice
+    desc = lambda B, T, C, HW: ctypes.byref(_lib.LtaeDesc(B, T, C, HW, 16, 256, 1e-5, 0.1, 0, None, None))
+    assert L.c2s_ltae_fwd_path(desc(4, 32, 128, 256)) == 3
+    valid = 0
+    for B in (1, 2, 4, 8):
+        for T in (5, 9, 32, 39, 48, 61, 64, 65, 122):
+            for C in (64, 128, 192, 256):
+                for HW in (16, 64, 256, 1024, 128 * 128, 180 * 182, 132 * 132):
+                    d = _lib.LtaeDesc(B, T, C, HW, 16, 256, 1e-5, 0.1, 0, None, None)
+                    if L.c2s_ltae_paths(ctypes.byref(d), 1, ctypes.byref(f), ctypes.byref(b)) != 0:
+                        assert L.c2s_ltae_fwd_path(ctypes.byref(d)) == -1
+                        continue
+                    valid += 1
+                    fwd = paths(B, T, C, HW)[0]
+                    assert L.c2s_ltae_fwd_path(ctypes.byref(d)) == fwd, (B, T, C, HW)
+                    assert L.c2s_ltae_uses_streaming(ctypes.byref(d)) == (fwd in (1, 2)), (B, T, C, HW)
+                    assert L.c2s_ltae_attn_optional(ctypes.byref(d)) == (paths(B, T, C, HW, keep_bits=True)[1] == 4), (B, T, C, HW)
+    assert valid == 840
+
+    # the backward workspace does not depend on the device or the family
+    for shape, floats in (((4, 32, 128, 256), 5111810), ((8, 61, 64, 128 * 128), 441425922), ((2, 39, 128, 64), 771586),
+                          ((1, 48, 128, 16), 214018), ((2, 39, 256, 16), 555394), ((1, 6, 192, 64), 607746),
+                          ((8, 122, 64, 128 * 128), 601833474), ((2, 9, 64, 132 * 132), 81052290)):
+        assert L.c2s_ltae_bwd_workspace_floats(desc(*shape)) == floats, shape
