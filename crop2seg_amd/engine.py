@@ -254,6 +254,15 @@ class Tape:
         else:
             check(lib().c2s_add_inplace(cur.data_ptr(), g.data_ptr(), g.numel(), _stream()), "add_inplace")
 
+    def grad_buffer(self, t: Tensor) -> Tuple[Tensor, int]:
+        """(gradient buffer of t, accumulate flag) for a kernel that adds in place: the buffer already on the tape with
+        flag 1, else a fresh one nobody else holds, now on the tape, with flag 0 (the kernel overwrites it)."""
+        g = self.grads.get(t.data_ptr())
+        if g is not None:
+            return g, 1
+        g = self.grads[t.data_ptr()] = torch.empty_like(t)
+        return g, 0
+
     def defer(self, fn: Callable[[], None], keep: Sequence[Tensor]) -> None:
         """Queue a launch for the side stream; a fork is issued every SIDE_BATCH launches (each fork/join is an edge of
         the captured hipGraph, and edges are not free)."""
@@ -415,16 +424,6 @@ def _pack_bf16x3(ctx: "Ctx", key: Tuple, src: Tensor, src_off: int, cin: int, co
     return whi, wlo, coutP
 
 
-def _use_winograd(K: int, S: int, pad: int, chans: Sequence[int], cout: int, H: int, W: int) -> bool:
-    """Winograd F(2x2,3x3) pays off where the 16 transform-domain GEMMs are deep and wide enough."""
-    return (WINOGRAD and CONV_MODE == "f32" and K == 3 and S == 1 and pad == 1 and sum(chans) >= 32 and cout >= 64
-            and H % 2 == 0 and W % 4 == 0 and W >= 8 and (len(chans) == 1 or chans[0] % 8 == 0))
-
-
-def _use_bf16x3(K: int, S: int, pad: int, chans: Sequence[int]) -> bool:
-    return CONV_MODE == "bf16x3" and K == 3 and S == 1 and pad == 1 and all(c % 8 == 0 for c in chans)
-
-
 # =================================================================================================
 # frame flags
 # =================================================================================================
@@ -440,27 +439,31 @@ def frame_flags(x5: Tensor, pad_value: float) -> Tensor:
 # =================================================================================================
 # convolutions
 # =================================================================================================
-# Convolution arithmetic: "f32" = exact fp32 MFMA everywhere (default); "bf16x3" = split-precision bf16 MFMA
-# (three products per fp32 product, fp32 accumulate, ~1e-5 relative) for the 3x3 stride-1 forward / data-gradient
-# launches whose channel counts are multiples of 8; everything else stays on the exact kernels.
-import os as _os
-
-CONV_MODE = _os.environ.get("C2S_CONV_MODE", "f32")
-assert CONV_MODE in ("f32", "bf16x3"), CONV_MODE
 # C2S_REDUCE_BATCH=1: the split-K slice sums of all weight gradients of a backward pass in one launch at its end (one slab
 # buffer per layer) instead of one launch per layer right behind its weight-gradient kernel.  Measured neutral on the eager
 # two-stream step (11.70 vs 11.71 ms), -0.2 ms under hipGraph capture: off by default, switched on by TrainStep.capture().
 REDUCE_BATCH = _os.environ.get("C2S_REDUCE_BATCH", "0") != "0"
+
+# The switches of the kernel choice, read by conv_plan whenever a plan is made (tests, tools and bench.py assign them).
+# Convolution arithmetic: "f32" = exact fp32 MFMA everywhere (default); "bf16x3" = split-precision bf16 MFMA
+# (three products per fp32 product, fp32 accumulate, ~1e-5 relative) for the 3x3 stride-1 forward / data-gradient
+# launches whose channel counts are multiples of 8; everything else stays on the exact kernels.
+CONV_MODE = _os.environ.get("C2S_CONV_MODE", "f32")
+assert CONV_MODE in ("f32", "bf16x3"), CONV_MODE
 # fp32 Winograd F(2x2,3x3) for the wide 3x3 layers (forward + data gradient); C2S_WINOGRAD=0 keeps the direct kernel.
 WINOGRAD = _os.environ.get("C2S_WINOGRAD", "1") != "0"
 # the 8-wave Winograd kernel with the output transform in registers (conv_winograd16.hip) for planes >= 32 wide;
 # C2S_WINO16=0 keeps the 4-wave kernel (conv_winograd.hip) everywhere
 WINO16 = _os.environ.get("C2S_WINO16", "1") != "0"
-
-
 # Winograd F(2x2,2x2) over the input parities for the 4x4 stride-2 forward convolutions (conv_s2wino.hip); C2S_S2WINO=0 keeps
 # the direct kernel
 S2WINO = _os.environ.get("C2S_S2WINO", "1") != "0"
+
+
+def _use_winograd(K: int, S: int, pad: int, chans: Sequence[int], cout: int, H: int, W: int) -> bool:
+    """Winograd F(2x2,3x3) pays off where the 16 transform-domain GEMMs are deep and wide enough."""
+    return (WINOGRAD and CONV_MODE == "f32" and K == 3 and S == 1 and pad == 1 and sum(chans) >= 32 and cout >= 64
+            and H % 2 == 0 and W % 4 == 0 and W >= 8 and (len(chans) == 1 or chans[0] % 8 == 0))
 
 
 def _wide_winograd(H: int, W: int, chans: Sequence[int]) -> bool:
@@ -468,38 +471,9 @@ def _wide_winograd(H: int, W: int, chans: Sequence[int]) -> bool:
     whole chunks in every source (ragged channel counts stay on the 4-wave kernel, whose channel index is range-checked)."""
     return WINO16 and W >= 32 and H >= 8 and sum(chans) > 24 and all(c % 8 == 0 for c in chans)
 
-# bench.py sets PROFILE = {"match": {field: value}, "events": []}: launches whose descriptor matches are bracketed
-# with HIP events on the launch stream (the stream the kernel runs on) for the live roofline measurement.
-PROFILE: Optional[dict] = None
 
-
-def _igemm(desc: ConvDesc, src0: Tensor, src1: Optional[Tensor], wpk: Tensor, bias: Optional[Tensor], out: Tensor,
-           valid: Optional[Tensor]) -> None:
-    prof = PROFILE
-    timed = prof is not None and all(getattr(desc, k) == v for k, v in prof["match"].items())
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().c2s_conv_igemm(C.byref(desc), src0.data_ptr(), _ptr(src1), wpk.data_ptr(), _ptr(bias), out.data_ptr(),
-                               _ptr(valid), _stream()), "conv_igemm")
-    if timed:
-        e1.record()
-        prof["events"].append((e0, e1))
-
-
-def _winograd(desc: ConvDesc, src0: Tensor, src1: Optional[Tensor], upk: Tensor, bias: Optional[Tensor], out: Tensor,
-              valid: Optional[Tensor], wide: bool = False) -> None:
-    prof = PROFILE
-    timed = prof is not None and all(getattr(desc, k) == v for k, v in prof["match"].items())
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    fn = lib().c2s_conv3x3_winograd16 if wide else lib().c2s_conv3x3_winograd
-    check(fn(C.byref(desc), src0.data_ptr(), _ptr(src1), upk.data_ptr(), _ptr(bias), out.data_ptr(), _ptr(valid), _stream()),
-          "conv3x3_winograd")
-    if timed:
-        e1.record()
-        prof["events"].append((e0, e1))
+def _use_bf16x3(K: int, S: int, pad: int, chans: Sequence[int]) -> bool:
+    return CONV_MODE == "bf16x3" and K == 3 and S == 1 and pad == 1 and all(c % 8 == 0 for c in chans)
 
 
 def _xpair_taps(py: int) -> List[int]:
@@ -520,24 +494,162 @@ def _parity_taps(K: int, pad: int, py: int, px: int) -> List[int]:
     return [(py + 2 * pad - 2 * ty) * K + (px + 2 * pad - 2 * tx) for ty in range(kp) for tx in range(kp)]
 
 
-def _parity_transpose(ctx: Ctx, key: Tuple, g: Tensor, Wsrc: Tensor, src_off: int, cin: int, cout: int, so: int, sc: int,
-                      K: int, pad: int, bias: Optional[Tensor], out: Tensor, accumulate: int, radj: int,
-                      valid: Optional[Tensor]) -> None:
-    """out (2H x 2W) = stride-2 transposed convolution of g (H x W) with kernel K, padding pad, as four implicit-GEMM
-    launches; radj folds the reflect-pad-2 adjoint into the 3x3 launches (data gradient of a reflect-padded down conv)."""
-    N, _, H, Wd = g.shape
-    kp = K // 2
-    for py in range(2):
-        for px in range(2):
-            wpk, CP = ctx.pack(key + ("par", py, px), Wsrc, src_off, cin, cout, so, sc, _parity_taps(K, pad, py, px))
-            d = ConvDesc(N, cin, 0, H, Wd, cout, CP, H, Wd, 2 * H, 2 * Wd, kp, kp, 1, pad // 2, pad // 2, _lib.PAD_ZEROS,
-                         2, 2, py, px, accumulate, 2 if radj else 0)
-            _igemm(d, g, None, wpk, bias, out, valid)
+def _conv_desc(*, N: int, C0: int, C1: int = 0, Hin: int, Win: int, Cout: int, CoutP: int, Hout: int, Wout: int, K: int,
+               S: int = 1, pad: int, pad_x: Optional[int] = None, pad_mode: int = _lib.PAD_ZEROS, OutH: Optional[int] = None,
+               OutW: Optional[int] = None, osy: int = 1, osx: int = 1, ooy: int = 0, oox: int = 0, accumulate: int = 0,
+               reflect_adjoint: int = 0) -> ConvDesc:
+    """ConvDesc of a square kernel; by default the output is dense (OutH x OutW = Hout x Wout, no placement stride or
+    offset), overwritten, padded alike in both directions, without the reflect adjoint."""
+    return ConvDesc(N, C0, C1, Hin, Win, Cout, CoutP, Hout, Wout, Hout if OutH is None else OutH,
+                    Wout if OutW is None else OutW, K, K, S, pad, pad if pad_x is None else pad_x, pad_mode, osy, osx, ooy, oox,
+                    accumulate, reflect_adjoint)
 
 
-def _xpair(d: ConvDesc, src: Tensor, wpk: Tensor, bias: Optional[Tensor], out: Tensor, valid: Optional[Tensor]) -> None:
-    check(lib().c2s_conv_xpair(C.byref(d), src.data_ptr(), wpk.data_ptr(), _ptr(bias), out.data_ptr(), _ptr(valid),
-                               _stream()), "conv_xpair")
+class ConvLaunch(NamedTuple):
+    """One launch of a plan: its descriptor, and its weights as Ctx.pack takes them.  `key` follows the weight's name in the
+    pack key; filter element (o, c, tap t) is weight[off + o * so + c * sc + taps[t]]."""
+    desc: ConvDesc
+    key: Tuple
+    kind: int               # PACK_KINDS (bf16x3: padded as kind 0, packed by _pack_bf16x3 into a hi / lo pair)
+    off: int
+    cin: int
+    cout: int
+    so: int
+    sc: int
+    taps: Tuple[int, ...]
+
+
+class ConvPlan(NamedTuple):
+    family: str             # key of CONV_FAMILIES
+    launches: Tuple[ConvLaunch, ...]
+
+
+# family -> (entry point, takes a second source, takes a bias, bracketed by PROFILE); after the descriptor every entry point
+# takes: source(s), packed weights (bf16x3: hi and lo), bias if any, output, frame flags, stream
+CONV_FAMILIES = {
+    "wino16": ("c2s_conv3x3_winograd16", True, True, True),             # 8-wave Winograd F(2x2,3x3)
+    "wino4": ("c2s_conv3x3_winograd", True, True, True),                # 4-wave Winograd F(2x2,3x3)
+    "bf16x3": ("c2s_conv3x3_bf16x3", True, True, False),
+    "s2wino": ("c2s_conv4x4s2_winograd", False, True, False),           # F(2x2,2x2), 4x4 stride-2 forward
+    "s2dgrad": ("c2s_conv4x4s2_dgrad_winograd", False, False, False),   # F(2x2,2x2), 4x4 stride-2 data gradient
+    "smallcin": ("c2s_conv3x3_smallcin", False, True, False),           # the first layer
+    "igemm": ("c2s_conv_igemm", True, True, True),
+    "xpair": ("c2s_conv_xpair", False, True, False),                    # transposed 4x4 stride-2 rows, one launch per row parity
+    "parity": ("c2s_conv_igemm", True, True, True),                     # PARITY_GEOMETRIES: four stride-1 sub-convolutions
+}
+
+
+def _launch(kind: int, key: Tuple, off: int, cin: int, cout: int, so: int, sc: int, taps: Sequence[int], **desc) -> ConvLaunch:
+    """One launch that reads `cin` channels (all from one source unless C0 / C1 say otherwise) and writes `cout`, padded as
+    the pack kind pads them."""
+    step = PACK_KINDS[kind][0]
+    return ConvLaunch(_conv_desc(**{"C0": cin, **desc}, Cout=cout, CoutP=(cout + step - 1) // step * step),
+                      key, kind, off, cin, cout, so, sc, tuple(taps))
+
+
+def _transposed_launches(family: str, key: Tuple, off: int, cin: int, cout: int, so: int, sc: int, K: int, pad: int, N: int,
+                         H: int, W: int, accumulate: int, radj: int) -> ConvPlan:
+    """out (2H x 2W) = stride-2 transposed convolution of an H x W plane with kernel K, padding pad: "xpair" (K = 4) one
+    launch per output-row parity, both column parities fused; "parity" four implicit-GEMM launches, where radj folds the
+    reflect-pad-2 adjoint into the 3x3 launches (data gradient of a reflect-padded down conv)."""
+    plane = dict(N=N, Hin=H, Win=W, Hout=H, Wout=W, OutH=2 * H, OutW=2 * W, osy=2, osx=2, accumulate=accumulate)
+    if family == "xpair":
+        return ConvPlan(family, tuple(
+            _launch(0, key + (py,), off, cin, cout, so, sc, _xpair_taps(py), K=2, pad=1 - py, pad_x=0, ooy=py,
+                    reflect_adjoint=radj, **plane) for py in range(2)))
+    return ConvPlan(family, tuple(
+        _launch(0, key + ("par", py, px), off, cin, cout, so, sc, _parity_taps(K, pad, py, px), K=K // 2, pad=pad // 2, ooy=py,
+                oox=px, reflect_adjoint=2 if radj else 0, **plane) for py in range(2) for px in range(2)))
+
+
+def _family_3x3(N: int, chans: Sequence[int], cout: int, H: int, W: int, K: int, S: int, pad: int):
+    """(family, pack kind, key tag) of the 3x3 stride-1 kernels besides the implicit GEMM for `chans` -> cout channels, or
+    None."""
+    if _use_winograd(K, S, pad, chans, cout, H, W):
+        wide = _wide_winograd(H, W, chans) and N <= 65536       # the 8-wave kernel's frame limit
+        return ("wino16", 2, "wino") if wide else ("wino4", 1, "wino")
+    return ("bf16x3", 0, "bx") if _use_bf16x3(K, S, pad, chans) else None
+
+
+def conv_plan(op: str, N: int, chans: Sequence[int], Cout: int, Hin: int, Win: int, K: int, S: int, pad: int, pad_mode: int,
+              si: int = 0, accumulate: int = 0) -> ConvPlan:
+    """The kernel family of one convolution and its launches: descriptors and pack requests, host integers only (no tensor,
+    no Ctx, no stream; the library is asked for its host-side *_supported predicates).  _run_conv executes a plan.
+    op "fwd": nn.Conv2d(K, S, pad, pad_mode) of N frames of Hin x Win over the channel concatenation of sources with `chans`
+    channels; "dgrad": its data gradient into source `si`, added to what that buffer holds if `accumulate`;
+    "tfwd": nn.ConvTranspose2d(K, 2, pad) from chans[0] to Cout channels, Hin x Win -> 2 Hin x 2 Win; "tdgrad": its data
+    gradient."""
+    KK, Cin = K * K, sum(chans)
+    if op == "tfwd":
+        return _transposed_launches("xpair" if K == 4 else "parity", ("fwd",), 0, Cin, Cout, KK, Cout * KK, K, pad, N, Hin, Win,
+                                    0, 0)
+    if op == "tdgrad":
+        return ConvPlan("igemm", (_launch(0, ("dgrad",), 0, Cout, Cin, Cout * KK, KK, range(KK), N=N, Hin=2 * Hin, Win=2 * Win,
+                                          Hout=Hin, Wout=Win, K=K, S=2, pad=pad, accumulate=accumulate),))
+    Ho, Wo = (Hin + 2 * pad - K) // S + 1, (Win + 2 * pad - K) // S + 1
+    if op == "fwd":
+        def fwd(family, kind, *key):
+            return ConvPlan(family, (_launch(kind, ("fwd",) + key, 0, Cin, Cout, Cin * KK, KK, range(KK), N=N,
+                                             C0=chans[0], C1=Cin - chans[0], Hin=Hin, Win=Win, Hout=Ho, Wout=Wo, K=K, S=S, pad=pad,
+                                             pad_mode=pad_mode),))
+        pick = _family_3x3(N, chans, Cout, Hin, Win, K, S, pad)
+        if pick:
+            return fwd(*pick)
+        if S2WINO and CONV_MODE == "f32" and K == 4 and S == 2 and Cin == chans[0]:
+            plan = fwd("s2wino", 3, "s2w")
+            if lib().c2s_conv4x4s2_winograd_supported(C.byref(plan.launches[0].desc)):
+                return plan
+        plan = fwd("igemm", 0)
+        first = lib().c2s_conv3x3_smallcin_supported(C.byref(plan.launches[0].desc))
+        return plan._replace(family="smallcin") if first else plan
+    assert op == "dgrad", op
+    # the gradient of the output (Cout channels, Ho x Wo) into the Cs channels of source si, which start at channel c_lo
+    Cs, c_lo = chans[si], sum(chans[:si])
+    radj = 1 if (pad_mode == _lib.PAD_REFLECT and pad > 0) else 0   # reflection adjoint folded into the kernel
+    w = (c_lo * KK, Cout, Cs, KK, Cin * KK)
+
+    def dgrad(family, kind, key, taps, **desc):
+        return ConvPlan(family, (_launch(kind, ("dgrad",) + key, *w, taps, N=N, Hin=Ho, Win=Wo, Hout=Hin, Wout=Win,
+                                         accumulate=accumulate, reflect_adjoint=radj, **desc),))
+    if S == 1:
+        taps = [(K - 1 - ky) * K + (K - 1 - kx) for ky in range(K) for kx in range(K)]
+        pick = _family_3x3(N, [Cout], Cs, Hin, Win, K, S, pad)
+        if pick:
+            return dgrad(pick[0], pick[1], (pick[2], si), taps, K=K, pad=1)
+        return dgrad("igemm", 0, (si,), taps, K=K, pad=K - 1 - pad)
+    assert S == 2 and Hin == 2 * Ho and Win == 2 * Wo, (K, S, pad, Hin, Win)
+    if (K, pad) in PARITY_GEOMETRIES:
+        return _transposed_launches("parity", ("dgrad", si), *w, K, pad, N, Ho, Wo, accumulate, radj)
+    assert K == 4 and pad == 1, (K, pad)
+    plan = dgrad("s2dgrad", 4, ("s2d", si), range(KK), K=4, S=2, pad=1)     # (cin = gy channels, cout = channels of the source)
+    if S2WINO and CONV_MODE == "f32" and lib().c2s_conv4x4s2_dgrad_winograd_supported(C.byref(plan.launches[0].desc)):
+        return plan
+    return _transposed_launches("xpair", ("dgrad", si), *w, K, pad, N, Ho, Wo, accumulate, radj)
+
+
+# bench.py sets PROFILE = {"match": {field: value}, "events": []}: launches whose descriptor matches are bracketed
+# with HIP events on the launch stream (the stream the kernel runs on) for the live roofline measurement.
+PROFILE: Optional[dict] = None
+
+
+def _run_conv(ctx: Ctx, plan: ConvPlan, wname: str, weight: Tensor, src0: Tensor, src1: Optional[Tensor],
+              bias: Optional[Tensor], out: Tensor, valid: Optional[Tensor]) -> None:
+    """Execute a plan: per launch, the packed weights of `weight` (ctx.p[wname]), then the family's entry point."""
+    entry, two_sources, has_bias, profiled = CONV_FAMILIES[plan.family]
+    for desc, key, kind, *where in plan.launches:
+        request = ((wname,) + key, weight, *where)
+        packed = _pack_bf16x3(ctx, *request)[:2] if plan.family == "bf16x3" else ctx.pack(*request, kind=kind)[:1]
+        args = [src0.data_ptr()] + ([_ptr(src1)] if two_sources else []) + [t.data_ptr() for t in packed] + \
+            ([_ptr(bias)] if has_bias else []) + [out.data_ptr(), _ptr(valid), _stream()]
+        prof = PROFILE
+        timed = profiled and prof is not None and all(getattr(desc, k) == v for k, v in prof["match"].items())
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        check(getattr(lib(), entry)(C.byref(desc), *args), entry[4:])
+        if timed:
+            e1.record()
+            prof["events"].append((e0, e1))
 
 
 def _wgrad_slices(ctx: Ctx, N: int, Hout: int, Wout: int, S: int, cin: int, cout: int) -> int:
@@ -604,35 +716,13 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
     N, C0, Hin, Win = s0.shape
     C1 = s1.shape[1] if s1 is not None else 0
     assert C0 + C1 == Cin, (wname, C0, C1, Cin)
+    chans = [C0, C1] if C1 else [C0]
     Ho = (Hin + 2 * pad - K) // S + 1
     Wo = (Win + 2 * pad - K) // S + 1
     KK = K * K
     out = torch.empty(N, Cout, Ho, Wo, device=s0.device, dtype=torch.float32)
-    if _use_winograd(K, S, pad, [C0, C1] if C1 else [C0], Cout, Hin, Win):
-        wide = _wide_winograd(Hin, Win, [C0, C1] if C1 else [C0]) and N <= 65536
-        upk, CoutP = ctx.pack((wname, "fwd", "wino"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)), kind=2 if wide else 1)
-        d = ConvDesc(N, C0, C1, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
-        _winograd(d, s0, s1, upk, ctx.p[bname] if bname else None, out, valid, wide)
-    elif _use_bf16x3(K, S, pad, [C0, C1]):
-        whi, wlo, CoutP = _pack_bf16x3(ctx, (wname, "fwd", "bx"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)))
-        d = ConvDesc(N, C0, C1, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
-        check(lib().c2s_conv3x3_bf16x3(C.byref(d), s0.data_ptr(), _ptr(s1), whi.data_ptr(), wlo.data_ptr(),
-                                       _ptr(ctx.p[bname] if bname else None), out.data_ptr(), _ptr(valid), _stream()),
-              "conv3x3_bf16x3")
-    elif (S2WINO and CONV_MODE == "f32" and K == 4 and S == 2 and C1 == 0 and lib().c2s_conv4x4s2_winograd_supported(C.byref(
-            ConvDesc(N, C0, 0, Hin, Win, Cout, (Cout + 63) // 64 * 64, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)))):
-        upk, CoutP = ctx.pack((wname, "fwd", "s2w"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)), kind=3)
-        d = ConvDesc(N, C0, 0, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
-        check(lib().c2s_conv4x4s2_winograd(C.byref(d), s0.data_ptr(), upk.data_ptr(), _ptr(ctx.p[bname] if bname else None),
-                                           out.data_ptr(), _ptr(valid), _stream()), "conv4x4s2_winograd")
-    else:
-        wpk, CoutP = ctx.pack((wname, "fwd"), W, 0, Cin, Cout, Cin * KK, KK, list(range(KK)))
-        d = ConvDesc(N, C0, C1, Hin, Win, Cout, CoutP, Ho, Wo, Ho, Wo, K, K, S, pad, pad, pad_mode, 1, 1, 0, 0, 0)
-        if lib().c2s_conv3x3_smallcin_supported(C.byref(d)):      # the first layer
-            check(lib().c2s_conv3x3_smallcin(C.byref(d), s0.data_ptr(), wpk.data_ptr(), _ptr(ctx.p[bname] if bname else None),
-                                             out.data_ptr(), _ptr(valid), _stream()), "conv3x3_smallcin")
-        else:
-            _igemm(d, s0, s1, wpk, ctx.p[bname] if bname else None, out, valid)
+    _run_conv(ctx, conv_plan("fwd", N, chans, Cout, Hin, Win, K, S, pad, pad_mode), wname, W, s0, s1,
+              ctx.p[bname] if bname else None, out, valid)
     if not ctx.mark([out], srcs, [wname, bname]):
         return out
     tape = ctx.tape
@@ -648,84 +738,29 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
             gw, acc = ctx.grad_sink(wname)
             _log("conv2d", wname, "wgrad")
             _wgrad(ctx, srcs, g, Cout, Ho, Wo, K, S, pad, pad_mode, gw, Cin * KK, KK, list(range(KK)), acc, valid)
-        if not any(need_src):
-            return
-        c_lo = 0
         for si, src in enumerate(srcs):
-            Cs = src.shape[1]
             if not need_src[si]:
-                c_lo += Cs
                 continue
             _log("conv2d", wname, "dgrad")
-            existing = tape.grad_of(src)
-            gin = existing if existing is not None else torch.empty_like(src)
-            accf = 1 if existing is not None else 0
-            radj = 1 if (pad_mode == _lib.PAD_REFLECT and pad > 0) else 0   # reflection adjoint folded into the kernel
-            if S == 1:
-                taps = [(K - 1 - ky) * K + (K - 1 - kx) for ky in range(K) for kx in range(K)]
-                if _use_winograd(K, S, pad, [Cout], Cs, Hin, Win):
-                    wide = _wide_winograd(Hin, Win, [Cout]) and N <= 65536
-                    upk, CP = ctx.pack((wname, "dgrad", "wino", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, taps,
-                                       kind=2 if wide else 1)
-                    dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Hin, Win, Hin, Win, K, K, 1, 1, 1, _lib.PAD_ZEROS, 1, 1, 0, 0,
-                                  accf, radj)
-                    _winograd(dd, g, None, upk, None, gin, valid, wide)
-                elif _use_bf16x3(K, S, pad, [Cout]):
-                    whi, wlo, CP = _pack_bf16x3(ctx, (wname, "dgrad", "bx", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, taps)
-                    dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Hin, Win, Hin, Win, K, K, 1, 1, 1, _lib.PAD_ZEROS, 1, 1, 0, 0,
-                                  accf, radj)
-                    check(lib().c2s_conv3x3_bf16x3(C.byref(dd), g.data_ptr(), None, whi.data_ptr(), wlo.data_ptr(), None,
-                                                   gin.data_ptr(), _ptr(valid), _stream()), "conv3x3_bf16x3")
-                else:
-                    wd, CP = ctx.pack((wname, "dgrad", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, taps)
-                    dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Hin, Win, Hin, Win, K, K, 1, K - 1 - pad, K - 1 - pad,
-                                  _lib.PAD_ZEROS, 1, 1, 0, 0, accf, radj)
-                    _igemm(dd, g, None, wd, None, gin, valid)
-            elif (K, pad) in PARITY_GEOMETRIES:
-                assert S == 2 and Hin == 2 * Ho and Win == 2 * Wo
-                _parity_transpose(ctx, (wname, "dgrad", si), g, W, c_lo * KK, Cout, Cs, KK, Cin * KK, K, pad, None, gin, accf,
-                                  radj, valid)
-            else:
-                assert K == 4 and S == 2 and pad == 1
-                assert Hin == 2 * Ho and Win == 2 * Wo
-                CsP = (Cs + 63) // 64 * 64
-                dw = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CsP, Hin, Win, Hin, Win, 4, 4, 2, 1, 1, _lib.PAD_ZEROS, 1, 1, 0, 0, accf, radj)
-                if S2WINO and CONV_MODE == "f32" and lib().c2s_conv4x4s2_dgrad_winograd_supported(C.byref(dw)):
-                    # (cin = gy channels, cout = input channels of this source)
-                    upk, _ = ctx.pack((wname, "dgrad", "s2d", si), W, c_lo * KK, Cout, Cs, KK, Cin * KK, list(range(KK)), kind=4)
-                    check(lib().c2s_conv4x4s2_dgrad_winograd(C.byref(dw), g.data_ptr(), upk.data_ptr(), gin.data_ptr(), _ptr(valid),
-                                                             _stream()), "conv4x4s2_dgrad_winograd")
-                else:
-                    for py in range(2):         # one launch per output-row parity, both column parities fused
-                        wd, CP = ctx.pack((wname, "dgrad", si, py), W, c_lo * KK, Cout, Cs, KK, Cin * KK, _xpair_taps(py))
-                        dd = ConvDesc(N, Cout, 0, Ho, Wo, Cs, CP, Ho, Wo, Hin, Win, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS,
-                                      2, 2, py, 0, accf, radj)
-                        _xpair(dd, g, wd, None, gin, valid)
-            if existing is None:
-                tape.grads[src.data_ptr()] = gin
-            c_lo += Cs
+            gin, accf = tape.grad_buffer(src)
+            _run_conv(ctx, conv_plan("dgrad", N, chans, Cout, Hin, Win, K, S, pad, pad_mode, si, accf), wname, W, g, None, None,
+                      gin, valid)
 
     tape.record(bwd)
     return out
 
 
 def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str, K: int = 4, pad: int = 1) -> Tensor:
-    """nn.ConvTranspose2d(k, s=2, p) (reference conv.py:384-390) for (k, p) = (4, 1) and PARITY_GEOMETRIES, as four
-    (k/2)x(k/2) parity sub-convolutions."""
+    """nn.ConvTranspose2d(k, s=2, p) (reference conv.py:384-390) for (k, p) = (4, 1) and PARITY_GEOMETRIES, as (k/2)x(k/2)
+    parity sub-convolutions."""
     Wt = ctx.p[wname]
     Cin, Cout = Wt.shape[0], Wt.shape[1]
     N, _, H, Wd = x.shape
     assert (K, pad) == (4, 1) or (K, pad) in PARITY_GEOMETRIES, (K, pad)
     KK = K * K
     out = torch.empty(N, Cout, 2 * H, 2 * Wd, device=x.device, dtype=torch.float32)
-    bias = ctx.p[bname]
-    if K == 4:
-        for py in range(2):
-            wpk, CP = ctx.pack((wname, "fwd", py), Wt, 0, Cin, Cout, 16, Cout * 16, _xpair_taps(py))
-            d = ConvDesc(N, Cin, 0, H, Wd, Cout, CP, H, Wd, 2 * H, 2 * Wd, 2, 2, 1, 1 - py, 0, _lib.PAD_ZEROS, 2, 2, py, 0, 0)
-            _xpair(d, x, wpk, bias, out, None)
-    else:
-        _parity_transpose(ctx, (wname, "fwd"), x, Wt, 0, Cin, Cout, KK, Cout * KK, K, pad, bias, out, 0, 0, None)
+    _run_conv(ctx, conv_plan("tfwd", N, [Cin], Cout, H, Wd, K, 2, pad, _lib.PAD_ZEROS), wname, Wt, x, None, ctx.p[bname], out,
+              None)
     if not ctx.mark([out], [x], [wname, bname]):
         return out
     tape = ctx.tape
@@ -744,14 +779,9 @@ def conv_transpose2d(ctx: Ctx, x: Tensor, wname: str, bname: str, K: int = 4, pa
         if not need_x:
             return
         _log("conv_transpose2d", wname, "dgrad")
-        existing = tape.grad_of(x)
-        gin = existing if existing is not None else torch.empty_like(x)
-        wd, CP = ctx.pack((wname, "dgrad"), Wt, 0, Cout, Cin, Cout * KK, KK, list(range(KK)))
-        dd = ConvDesc(N, Cout, 0, 2 * H, 2 * Wd, Cin, CP, H, Wd, H, Wd, K, K, 2, pad, pad, _lib.PAD_ZEROS, 1, 1, 0, 0,
-                      1 if existing is not None else 0)
-        _igemm(dd, g, None, wd, None, gin, None)
-        if existing is None:
-            tape.grads[x.data_ptr()] = gin
+        gin, accf = tape.grad_buffer(x)
+        _run_conv(ctx, conv_plan("tdgrad", N, [Cin], Cout, H, Wd, K, 2, pad, _lib.PAD_ZEROS, 0, accf), wname, Wt, g, None, None,
+                  gin, None)
 
     tape.record(bwd)
     return out
@@ -801,12 +831,9 @@ def depthwise_conv2d(ctx: Ctx, x: Tensor, wname: str, K: int, S: int, pad: int, 
         if not need_x:
             return
         _log("depthwise_conv2d", wname, "dgrad")
-        existing = tape.grad_of(x)                      # e.g. the residual branch of the block: accumulate in the kernel
-        gin = existing if existing is not None else torch.empty_like(x)
+        gin, accf = tape.grad_buffer(x)                 # e.g. the residual branch of the block: accumulate in the kernel
         check(lib().c2s_dwconv_dgrad(g.data_ptr(), W.data_ptr(), gin.data_ptr(), _ptr(valid), N, Cc, Hin, Win, K, S, pad,
-                                     pad_mode, 1 if existing is not None else 0, _stream()), "dwconv_dgrad")
-        if existing is None:
-            tape.grads[x.data_ptr()] = gin
+                                     pad_mode, accf, _stream()), "dwconv_dgrad")
 
     tape.record(bwd)
     return out
@@ -1019,8 +1046,7 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
         g = tape.pop_grad(out)
         if g is None:
             return
-        existing = tape.grad_of(x5) if need_x else None
-        gx = existing if existing is not None else (torch.empty_like(x5) if need_x else None)
+        gx, accx = tape.grad_buffer(x5) if need_x else (None, 0)
         if need_x:
             _log("temporal_aggregate", mode, "dgrad")
         if not need_a:
@@ -1035,17 +1061,12 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
         nws = lib().c2s_temporal_aggregate_bwd_workspace_floats(C.byref(d))
         ws = ctx.ws.get("agg", nws)
         check(lib().c2s_temporal_aggregate_bwd(C.byref(d), x5.data_ptr(), attn.data_ptr(), _ptr(valid), g.data_ptr(),
-                                               _ptr(gx), 1 if existing is not None else 0, _ptr(gattn),
+                                               _ptr(gx), accx, _ptr(gattn),
                                                ws.data_ptr(), ws.numel(), _stream()), "temporal_aggregate_bwd")
         if mode == "att_mean" and need_a:
-            cur = tape.grad_of(src_attn)
-            tgt = cur if cur is not None else torch.empty_like(src_attn)
-            check(lib().c2s_attn_head_mean_bwd(gattn.data_ptr(), tgt.data_ptr(), n_head, src_attn[0].numel(),
-                                               1 if cur is not None else 0, _stream()), "attn_head_mean_bwd")
-            if cur is None:
-                tape.grads[src_attn.data_ptr()] = tgt
-        if need_x and existing is None:
-            tape.grads[x5.data_ptr()] = gx
+            tgt, acca = tape.grad_buffer(src_attn)
+            check(lib().c2s_attn_head_mean_bwd(gattn.data_ptr(), tgt.data_ptr(), n_head, src_attn[0].numel(), acca, _stream()),
+                  "attn_head_mean_bwd")
 
     tape.record(bwd)
     return out
