@@ -7,6 +7,9 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// the same four floats at an address that is only float-aligned (a row of HW % 4 != 0 floats starts anywhere): global
+// memory takes a 16-byte access at any 4-byte boundary, but the type must say so -- a plain f32x4 promises 16
+typedef f32x4 f32x4u __attribute__((aligned(4)));
 
 void c2s_set_error(const char* fmt, ...);
 

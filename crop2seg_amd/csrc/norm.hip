@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
         // flight: 3.2 TB/s on the 537 MB layers) and stay in registers for the second pass; same summation order
         f32x4 v[SEG / 256];
 #pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) v[k] = *reinterpret_cast<const f32x4*>(xr + lane * 4 + 256 * k);
+        for (int k = 0; k < SEG / 256; ++k) v[k] = *reinterpret_cast<const f32x4u*>(xr + lane * 4 + 256 * k);
 #pragma unroll
         for (int k = 0; k < SEG / 256; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
         s = wave_sum(s);
@@ -170,10 +170,10 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
         // wave in flight)
         f32x4 v[SEG / 256], r[SEG / 256];
 #pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) v[k] = *reinterpret_cast<const f32x4*>(x + base + lane * 4 + 256 * k);
+        for (int k = 0; k < SEG / 256; ++k) v[k] = *reinterpret_cast<const f32x4u*>(x + base + lane * 4 + 256 * k);
         if (res != nullptr) {
 #pragma unroll
-            for (int k = 0; k < SEG / 256; ++k) r[k] = *reinterpret_cast<const f32x4*>(res + base + lane * 4 + 256 * k);
+            for (int k = 0; k < SEG / 256; ++k) r[k] = *reinterpret_cast<const f32x4u*>(res + base + lane * 4 + 256 * k);
         }
 #pragma unroll
         for (int k = 0; k < SEG / 256; ++k) {
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
                 if (res != nullptr) t += r[k][e];
                 o[e] = t;
             }
-            *reinterpret_cast<f32x4*>(y + base + lane * 4 + 256 * k) = o;
+            *reinterpret_cast<f32x4u*>(y + base + lane * 4 + 256 * k) = o;
         }
     } else if ((len & 3) == 0) {
         for (int i = lane * 4; i < len; i += 256) {
@@ -238,8 +238,8 @@ __global__ __launch_bounds__(256) void norm_bwd_sums_kernel(const float* __restr
         f32x4 xa[SEG / 256], ga[SEG / 256];                       // all 16 loads of the lane in flight at once
 #pragma unroll
         for (int k = 0; k < SEG / 256; ++k) {
-            xa[k] = *reinterpret_cast<const f32x4*>(x + base + lane * 4 + 256 * k);
-            ga[k] = *reinterpret_cast<const f32x4*>(g + base + lane * 4 + 256 * k);
+            xa[k] = *reinterpret_cast<const f32x4u*>(x + base + lane * 4 + 256 * k);
+            ga[k] = *reinterpret_cast<const f32x4u*>(g + base + lane * 4 + 256 * k);
         }
 #pragma unroll
         for (int k = 0; k < SEG / 256; ++k)
@@ -368,8 +368,8 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
         f32x4 xa[SEG / 256], ga[SEG / 256];                       // all 16 loads of the lane in flight at once
 #pragma unroll
         for (int k = 0; k < SEG / 256; ++k) {
-            xa[k] = *reinterpret_cast<const f32x4*>(x + base + lane * 4 + 256 * k);
-            ga[k] = *reinterpret_cast<const f32x4*>(g + base + lane * 4 + 256 * k);
+            xa[k] = *reinterpret_cast<const f32x4u*>(x + base + lane * 4 + 256 * k);
+            ga[k] = *reinterpret_cast<const f32x4u*>(g + base + lane * 4 + 256 * k);
         }
 #pragma unroll
         for (int k = 0; k < SEG / 256; ++k) {
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
                 o[e] = k1 * gg + k2 * xc + k3;
                 sdx += o[e];
             }
-            *reinterpret_cast<f32x4*>(gx + base + lane * 4 + 256 * k) = o;
+            *reinterpret_cast<f32x4u*>(gx + base + lane * 4 + 256 * k) = o;
         }
     } else if ((len & 3) == 0) {
         for (int i = lane * 4; i < len; i += 256) {

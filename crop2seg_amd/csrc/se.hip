@@ -39,11 +39,11 @@ __global__ __launch_bounds__(256) void se_row_sums_kernel(const float* __restric
     const int len = (HW - beg) < L ? (HW - beg) : L;
     const size_t base = (size_t)row * HW + beg;
     float s = 0.f;
-    if ((len & 3) == 0) {
+    if ((len & 3) == 0) {      // a full segment of a row with HW % 4 != 0 comes here at a base that is only float-aligned
         for (int i = lane * 4; i < len; i += 256) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(x + base + i);
+            const f32x4 v = *reinterpret_cast<const f32x4u*>(x + base + i);
             if (g != nullptr) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(g + base + i);
+                const f32x4 w = *reinterpret_cast<const f32x4u*>(g + base + i);
                 s += (v.x * w.x + v.y * w.y) + (v.z * w.z + v.w * w.w);
             } else {
                 s += (v.x + v.y) + (v.z + v.w);
@@ -74,17 +74,19 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ 
     }
     __syncthreads();
     if (tid < R) {
-        float v = 0.f;
-        for (int c = 0; c < C; ++c) v = fmaf(W1[(size_t)tid * C + c], sp[c], v);
-        v = fmaxf(v, 0.f);
+        // up to 1024 terms: summed in double (a sequential float sum over C = 1024 alone put the input gradient 5e-6 from
+        // the float64 result, tests/test_norm_reference_gpu.py)
+        double acc = 0.0;
+        for (int c = 0; c < C; ++c) acc = fma((double)W1[(size_t)tid * C + c], (double)sp[c], acc);
+        const float v = fmaxf((float)acc, 0.f);
         sh[tid] = v;
         hidden[(size_t)n * R + tid] = v;
     }
     __syncthreads();
     for (int c = tid; c < C; c += 256) {
-        float v = 0.f;
-        for (int k = 0; k < R; ++k) v = fmaf(W2[(size_t)c * R + k], sh[k], v);
-        scale[(size_t)n * C + c] = 1.f / (1.f + expf(-v));
+        double acc = 0.0;
+        for (int k = 0; k < R; ++k) acc = fma((double)W2[(size_t)c * R + k], (double)sh[k], acc);
+        scale[(size_t)n * C + c] = 1.f / (1.f + expf(-(float)acc));
     }
 }
 
@@ -110,9 +112,9 @@ __global__ __launch_bounds__(256) void se_apply_kernel(const float* __restrict__
     const float a = dpool != nullptr ? dpool[row] / (float)HW : 0.f;
     if ((len & 3) == 0) {
         for (int i = lane * 4; i < len; i += 256) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(x + base + i);
+            f32x4 v = *reinterpret_cast<const f32x4u*>(x + base + i);
             v.x = fmaf(v.x, s, a); v.y = fmaf(v.y, s, a); v.z = fmaf(v.z, s, a); v.w = fmaf(v.w, s, a);
-            *reinterpret_cast<f32x4*>(y + base + i) = v;
+            *reinterpret_cast<f32x4u*>(y + base + i) = v;
         }
     } else {
         for (int i = lane; i < len; i += 64) y[base + i] = fmaf(x[base + i], s, a);
@@ -141,16 +143,16 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restric
     __syncthreads();
     for (int e = tid; e < C * R; e += 256) pw2[e] = dz2[e / R] * hidden[(size_t)n * R + e % R];      // d W2 [C][R]
     if (tid < R) {
-        float v = 0.f;
-        for (int c = 0; c < C; ++c) v = fmaf(W2[(size_t)c * R + tid], dz2[c], v);
-        dz1[tid] = hidden[(size_t)n * R + tid] > 0.f ? v : 0.f;
+        double acc = 0.0;
+        for (int c = 0; c < C; ++c) acc = fma((double)W2[(size_t)c * R + tid], (double)dz2[c], acc);
+        dz1[tid] = hidden[(size_t)n * R + tid] > 0.f ? (float)acc : 0.f;
     }
     __syncthreads();
     for (int e = tid; e < R * C; e += 256) pw1[e] = dz1[e / C] * pooled[(size_t)n * C + e % C];      // d W1 [R][C]
     for (int c = tid; c < C; c += 256) {
-        float v = 0.f;
-        for (int k = 0; k < R; ++k) v = fmaf(W1[(size_t)k * C + c], dz1[k], v);
-        dpool[(size_t)n * C + c] = v;
+        double acc = 0.0;
+        for (int k = 0; k < R; ++k) acc = fma((double)W1[(size_t)k * C + c], (double)dz1[k], acc);
+        dpool[(size_t)n * C + c] = (float)acc;
     }
 }
 

@@ -962,6 +962,7 @@ def norm_act(ctx: Ctx, x: Tensor, prefix: str, kind: int, groups: int, relu: boo
             norm_bwd(ctx.ws.get("norm", nws), dgamma, dbeta, dbias)
         tape.add_grad(x, gx)
 
+    bwd.saved = {"group_stats": gstats, "row_ab": row_ab}     # what the forward left for this step (tests read it here)
     tape.record(bwd)
     return y
 
