@@ -12,8 +12,17 @@ counterpart and is not claimed.  N > 1: one process per GPU (to
 
 Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (the 64->64 3x3 convolution of the in_conv block at
 128x128 -- the 8-wave Winograd F(2x2,3x3) kernel conv_winograd16_kernel<false> --, timed with HIP events on the launch
-stream inside the timed region) and the CPU baseline (the CPU oracle --
-a restatement of the reference validated against it -- timed on this host's cores on a bounded sample).
+stream inside the timed region: part of the timed steps themselves, so it costs no run of its own).
+
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs, print the line.  Everything that takes
+a run of its own is behind --full:
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+adds the CPU baseline (`cpu_baseline`: the CPU oracle -- a restatement of the reference validated against it -- timed on
+this host's cores on a bounded sample, about half a minute; --no-cpu-baseline leaves it out again) and, with --graph, the
+extra eager steps that time the dominant kernel (a captured graph cannot carry the events, so without --full `roofline`
+is null in graph mode).
 """
 from __future__ import annotations
 
@@ -138,7 +147,10 @@ def main():
                     help="pad_collate-style batch: series lengths T_b ~ U{27..T}, frames t >= T_b zero in x and dates "
                          "(default for --model timeunet: BASELINE.json configs[2] is defined on it)")
     ap.add_argument("--regular", dest="irregular", action="store_false")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own after the timed steps: the CPU baseline and, with --graph, "
+                         "the eager steps that time the dominant kernel for the roofline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--conv-mode", default=None, choices=["f32", "bf16x3"],
                     help="convolution arithmetic: exact fp32 MFMA (default) or opt-in split-precision bf16x3")
@@ -204,8 +216,8 @@ def main():
     barrier()
     torch.cuda.synchronize()
     # HIP-event timing of the dominant kernel inside the timed region
-    # (eager launches only: a captured graph cannot carry the timing events; bench_roofline() below measures the
-    # same launches eagerly right after the timed region in graph mode)
+    # (eager launches only: a captured graph cannot carry the timing events; with --full the same launches are measured
+    # eagerly right after the timed region in graph mode)
     E.PROFILE = {"match": dict(KH=3, S=1, C0=64, C1=0, Cout=64, Hin=H, N=B * T, reflect_adjoint=0), "events": [], "ltae_events": []} if not use_graph else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -221,7 +233,7 @@ def main():
                                          "grads": step.flat_grad})
     prof = E.PROFILE
     E.PROFILE = None
-    if use_graph:
+    if use_graph and args.full:
         # roofline of the dominant kernel: the same launches, timed with HIP events on the launch stream during
         # extra eager steps (identical kernels, shapes and data as inside the graph)
         prof = {"match": dict(KH=3, S=1, C0=64, C1=0, Cout=64, Hin=H, N=B * T, reflect_adjoint=0), "events": [], "ltae_events": []}
@@ -240,6 +252,7 @@ def main():
     assert step.ws.sync_error() == 0, "a one-pass normalisation wait gave up (sync area error word set)"
 
     if rank == 0:
+        prof = prof or {"events": [], "ltae_events": []}             # graph mode without --full: nothing was timed
         ms = [a.elapsed_time(b) for a, b in prof["events"]]
         kernel_ms = sum(ms) / max(len(ms), 1)
         N = B * T
@@ -306,13 +319,13 @@ def main():
             "config": {"workload": f"{args.model} train step (fwd+CE+bwd+Adam, train mode), B={B}/GPU T={T} 10x{H}x{H}, {pad_note}, "
                                    f"weight_init random weights; {cfg_id}",
                        "global_batch": world * B, "T": T, "parallelism": f"dp{world}", "hipgraph": use_graph},
-            "roofline": roofline,
+            "roofline": roofline if ms else None,
             "loss": loss_val,
             "step_mfma_frac": (world * B * args.steps / dt / world) * step_flops / (PEAK_F32_TFLOPS * 1e12),
         }
         if ltae_roofline:
             out["roofline_ltae"] = ltae_roofline
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             threads = os.cpu_count() or 1
             try:
                 threads = len(os.sched_getaffinity(0))
