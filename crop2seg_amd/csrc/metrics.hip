@@ -189,7 +189,12 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
         const float pt = expf(logpt);
         const float om = 1.f - pt;
         // dL/dlogpt = g (1-pt)^(g-1) pt logpt - (1-pt)^g ; dlogpt/dz_k = delta_kt - p_k
-        const float coef = (gamma * powf(om, gamma - 1.f) * pt * logpt - powf(om, gamma)) * inv_n;
+        // At a saturated pixel (pt == 1.f: om == 0, logpt == 0) om^(g-1) is inf for every g < 1 and the first term inf * 0; its
+        // limit is finite (logpt ~ -om, so the term goes like -g om^g -> 0), and for g == 0 the loss is plain CE: the term is 0.
+        // The factor is taken as 0 there, so no inf is formed; elsewhere the expression is the one above.
+        const bool at_limit = gamma < 1.f && (gamma == 0.f || om <= 0.f);
+        const float om_gm1 = at_limit ? 0.f : powf(om, gamma - 1.f);
+        const float coef = (gamma * om_gm1 * pt * logpt - powf(om, gamma)) * inv_n;
         for (int k = 0; k < K; ++k) {
             const float pk = expf(lp[(size_t)k * HW] - mx) * inv_s;
             gp[(size_t)k * HW] = coef * ((k == t ? 1.f : 0.f) - pk);

@@ -531,7 +531,8 @@ int c2s_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr
  * Boundary-loss pieces (N4; utils.py:198-222,283-285; focal_loss.py:7-44):
  *   c2s_boundary_target: y_b = (get_dilated(y, K, connectivity 4).sum(1) > 1): 1 where a 4-neighbour holds another class.
  *   c2s_focal_ce: FocalCELoss(gamma, size_average=True, weight=None): mean over targets != ignore_index of
- *     -(1-pt)^gamma log pt; accumulate_loss != 0 adds it to *loss (utils.py:324 loss = loss + loss_b).
+ *     -(1-pt)^gamma log pt; accumulate_loss != 0 adds it to *loss (utils.py:324 loss = loss + loss_b).  Any gamma >= 0: at a
+ *     saturated pixel (pt == 1.f) the gradient takes its finite limit for gamma < 1, and gamma == 0 is plain cross entropy.
  *   c2s_focal_ce_ex: the module's other constructor arguments (focal_loss.py:12-45): size_average == 0: the sum; class_w[K]
  *     non-NULL: the reference multiplies a [N,1] column of gathered weights by the [N] row of focal terms (an N x N outer
  *     product, focal_loss.py:36-39), i.e. its value is mean_i(w[t_i]) * mean_j(f_j) (sum_i * sum_j without size_average) --
