@@ -1,6 +1,7 @@
 """engine.conv_plan, the one place that chooses a convolution's kernel family, checked without a GPU: the launches of
 conv2d / conv_transpose2d against the trace recorded before the plan existed (tests/conv_trace.py), the planned family of
-every row of test_conv_paths_gpu.ROWS against the table's, and the frame-count bounds of the choice."""
+every row of test_conv_paths_gpu.ROWS and of the two tables of test_conv_modes_gpu against the tables', and the frame-count
+bounds of the choice."""
 import json
 import os
 
@@ -9,6 +10,7 @@ import pytest
 import conv_trace as T
 from crop2seg_amd import _lib
 from crop2seg_amd import engine as E
+from test_conv_modes_gpu import PERSISTENT, TABLES, persistent_frames
 from test_conv_paths_gpu import ROWS
 
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_launch_trace.json")) as f:
@@ -44,6 +46,27 @@ def test_planned_family_is_the_table_s(row):
     assert {"smallcin": "igemm"}.get(fwd, fwd) == row.fwd
     dgrad = tuple(_plan("dgrad", *args, si=si, accumulate=acc).family for si, acc in enumerate(row.acc))
     assert dgrad == row.dgrad
+
+
+@pytest.mark.parametrize("mode,row", TABLES, ids=[r.id for _, r in TABLES])
+def test_planned_family_of_the_mode_rows(mode, row, monkeypatch):
+    """The first-layer and bf16x3 tables of test_conv_modes_gpu under their CONV_MODE; "smallcin" by its own name."""
+    monkeypatch.setattr(E, "CONV_MODE", mode)
+    args = (row.N, row.chans, row.Cout, row.H, row.W, row.K, row.S, row.mode)
+    assert _plan("fwd", *args).family == row.fwd
+    dgrad = tuple(_plan("dgrad", *args, si=si, accumulate=acc).family for si, acc in enumerate(row.acc))
+    assert dgrad == row.dgrad
+
+
+def test_the_persistent_row_outruns_the_grid():
+    """first-persistent on 256 compute units: more tiles than the 2 * 256 workgroups of the first-layer kernel's grid, so
+    workgroups reach a second tile; planned on that kernel."""
+    N, padded = persistent_frames(256)
+    row = PERSISTENT
+    tiles = N * (row.H // 8) * (row.W // 32)
+    assert (N, tiles) == (160, 640) and tiles > 2 * 256
+    assert padded == [1, 3, 4, 5, 6, 10, 136, 137, 138, 159]
+    assert _plan("fwd", N, row.chans, row.Cout, row.H, row.W, row.K, row.S, row.mode).family == "smallcin"
 
 
 def test_frame_count_bounds():
