@@ -44,6 +44,8 @@ struct WCfg {
     static constexpr int plane_for(int l2) { return (((TP >> l2) - 1) * S + K) * (((1 << l2) - 1) * S + K); }
     static constexpr int MAXPLANE = wg_cmax(wg_cmax(plane_for(2), plane_for(3)), wg_cmax(plane_for(4), plane_for(5))) | 1;
     static constexpr int MAXE = (32 * MAXPLANE + 255) / 256;
+    // dynamic LDS of conv_wgrad_kernel<K, S> on tiles 2^l2 positions wide: Xl [32][planeP] + Gl [64][TP+1]
+    static constexpr size_t lds_bytes(int l2) { return ((size_t)32 * (plane_for(l2) | 1) + (size_t)64 * (TP + 1)) * sizeof(float); }
 };
 
 template <int K, int S>
@@ -185,6 +187,13 @@ template <int K, int S>
 struct TCfg {
     // positions per tile: 64 keeps (accumulators + the register-staged next tile) within 256 registers = 2 waves/SIMD
     static constexpr int TP = (K == 1) ? 128 : 64;
+    // dynamic LDS of conv_wgrad_tile_kernel<K, S, LW, MODE>: Xl [CB][PLANEP] + Gl [64][TP+1], and no less than the exchange area
+    // of the position halves [2][16][64]
+    static constexpr size_t lds_bytes(int LW, int MODE) {
+        const int TW = 1 << LW, PR = TP / TW, XR = (PR - 1) * S + K, XC = (TW - 1) * S + K, CB = (MODE == 2) ? 16 : 32;
+        const size_t fl = (size_t)CB * ((XR * XC) | 1) + (size_t)64 * (TP + 1);
+        return (fl < 2 * 16 * 64 ? 2 * 16 * 64 : fl) * sizeof(float);
+    }
 };
 
 template <int K, int S, int LW, int MODE>
@@ -455,6 +464,8 @@ __device__ unsigned long long ww_stamps[1024 * 4];
 #endif
 constexpr int WW_XP = 206;     // raw input tile pitch per channel: 6 x 34 = 204 -> 206 (= 2*7 mod 64)
 constexpr int WW_GP = 130;     // gout tile pitch per channel:      4 x 32 = 128 -> 130 (= 2*1 mod 64)
+// dynamic LDS of conv_wgrad_winograd_kernel<CB>: Xl [32 CB][WW_XP] + Gl [64][WW_GP]
+constexpr size_t ww_lds_bytes(int CB) { return ((size_t)32 * CB * WW_XP + (size_t)64 * WW_GP) * sizeof(float); }
 
 typedef float f32x2w __attribute__((ext_vector_type(2)));
 
@@ -790,6 +801,8 @@ __global__ __launch_bounds__(256 * CB, CB == 1 ? 2 : 1) void conv_wgrad_winograd
 // prefetched into registers under the MFMA loop.
 constexpr int S2W_PL = 5 * 34;                      // one parity plane [5][33 -> 34]
 constexpr int S2W_XP = 4 * S2W_PL + 2;              // input pitch per channel: 682 = 2 * 341 (odd): conflict-free ds_read_b64 across channels
+// dynamic LDS of conv_wgrad_s2wino_kernel: Xl [32][S2W_XP] + Gl [64][WW_GP]
+constexpr size_t s2w_lds_bytes() { return ((size_t)32 * S2W_XP + (size_t)64 * WW_GP) * sizeof(float); }
 
 __global__ __launch_bounds__(512) void conv_wgrad_s2wino_kernel(WgradParams p) {
     constexpr int NTH = 512;
@@ -991,31 +1004,15 @@ __global__ __launch_bounds__(512) void conv_wgrad_s2wino_kernel(WgradParams p) {
         }
 }
 
-int g_wgrad_f23 = -1, g_wgrad_f22 = -1;     // -1: from the environment; 0 / 1: set by c2s_wgrad_algorithms (A/B tests)
-// F(2x2,2x2) path of the 4x4 stride-2 layers on planes that tile into 4 x 32 output pixels (C2S_S2WINO=0 keeps the direct kernel)
-bool s2wino_wgrad(const c2s_wgrad_desc* d) {
-    static const bool env_on = [] { const char* e = getenv("C2S_S2WINO"); const char* e2 = getenv("C2S_S2WINO_WGRAD");
-                                    return !(e && e[0] == '0') && !(e2 && e2[0] == '0'); }();
-    const bool enabled = g_wgrad_f22 >= 0 ? g_wgrad_f22 != 0 : env_on;
-    return enabled && d->KH == 4 && d->KW == 4 && d->S == 2 && d->pad_y == 1 && d->pad_x == 1 && d->Hin == 2 * d->Hout &&
-           d->Win == 2 * d->Wout && d->Wout % 32 == 0 && d->Hout % 4 == 0 && d->C0 + d->C1 >= 32 && d->Cout >= 32 &&
-           d->C0 % 4 == 0;
-}
-
-// Winograd path: wide 3x3 layers on planes that tile into 4 x 32 pixel pieces (C2S_WINOGRAD=0 disables it)
-bool wino_wgrad(const c2s_wgrad_desc* d) {
-    static int env_on = -1;
-    if (env_on < 0) {
-        const char* e = getenv("C2S_WINOGRAD");
-        env_on = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
-    const int enabled = g_wgrad_f23 >= 0 ? g_wgrad_f23 : env_on;
-    return enabled && d->KH == 3 && d->KW == 3 && d->S == 1 && d->pad_y == 1 && d->pad_x == 1 && d->C0 + d->C1 >= 32 &&
-           d->Cout >= 32 && d->Win == d->Wout && d->Hin == d->Hout && d->Wout % 32 == 0 && d->Hout % 4 == 0;
-}
-
-struct TapTable {
-    int off[C2S_MAX_TAPS];
+// ------------------------------------------------------------------------------------------------------------
+// Slice sums.  One job = one layer's slabs summed over the slices and scattered into the destination layout
+// dst[o*so + c*sc + taps[t]]; the batched launch walks a device table of these records (c2s_wgrad_reduce_job_fill).
+struct ReduceJob {
+    const float* slabs;
+    float* dst;
+    long so, sc;
+    int nslices, NT, Cin, Cout, CinP, CoutB, accumulate, block_start;
+    int taps[C2S_MAX_TAPS];
 };
 
 // Slice sum of one output element, shared by the per-layer and the batched kernel.  FOUR lanes per element (a launch has only
@@ -1036,77 +1033,33 @@ __device__ __forceinline__ float slice_sum4(const float* __restrict__ s, size_t 
     return acc;
 }
 
-__global__ void wgrad_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ dst, int nslices, int NT,
-                                    int Cin, int Cout, int CinP, int CoutB, long so, long sc, TapTable tt,
-                                    int accumulate) {
-    const long total = (long)NT * Cin * Cout;
-    const long t4 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+// Thread t4 of a job: lane t4 & 3 of the quad of element t4 >> 2
+__device__ __forceinline__ void reduce_job(const ReduceJob& jb, long t4) {
+    const long total = (long)jb.NT * jb.Cin * jb.Cout;
     const long e = t4 >> 2;
     const int q = (int)(t4 & 3);
     const bool live = e < total;
     const long ee = live ? e : total - 1;             // (whole quads stay converged for the shuffles)
-    const int o = (int)(ee % Cout);
-    const long tc = ee / Cout;
-    const int c = (int)(tc % Cin), t = (int)(tc / Cin);
-    const size_t stride = (size_t)NT * CinP * CoutB;
-    const float acc = slice_sum4(slabs + ((size_t)t * CinP + c) * CoutB + o, stride, nslices, q);
+    const int o = (int)(ee % jb.Cout);
+    const long tc = ee / jb.Cout;
+    const int c = (int)(tc % jb.Cin), t = (int)(tc / jb.Cin);
+    const size_t stride = (size_t)jb.NT * jb.CinP * jb.CoutB;
+    const float acc = slice_sum4(jb.slabs + ((size_t)t * jb.CinP + c) * jb.CoutB + o, stride, jb.nslices, q);
     if (live && q == 0) {
-        float* d = dst + o * so + c * sc + tt.off[t];
-        *d = accumulate ? *d + acc : acc;
+        float* d = jb.dst + o * jb.so + c * jb.sc + jb.taps[t];
+        *d = jb.accumulate ? *d + acc : acc;
     }
 }
 
-void geometry(const c2s_wgrad_desc* d, int TP, int* log2pc, int* tiles_x, int* tiles_y) {
-    int l2 = 5;
-    while (l2 > 2 && (1 << l2) > d->Wout) --l2;
-    *log2pc = l2;
-    *tiles_x = cdiv(d->Wout, 1 << l2);
-    *tiles_y = cdiv(d->Hout, TP >> l2);
-}
+__global__ void wgrad_reduce_kernel(ReduceJob jb) { reduce_job(jb, blockIdx.x * (long)blockDim.x + threadIdx.x); }
 
-template <int K, int S, int LW, int MODE>
-int launch_wgrad_tile(const c2s_wgrad_desc* d, WgradParams& p, hipStream_t st) {
-    constexpr int TP = TCfg<K, S>::TP, TW = 1 << LW, PR = TP / TW;
-    constexpr int XR = (PR - 1) * S + K, XC = (TW - 1) * S + K;
-    constexpr int CB = (MODE == 2) ? 16 : 32;
-    p.log2pc = LW;
-    p.tiles_x = d->Wout / TW;
-    p.tiles_y = d->Hout / PR;
-    p.ntiles = d->N * p.tiles_x * p.tiles_y;
-    size_t fl = (size_t)CB * ((XR * XC) | 1) + (size_t)64 * (TP + 1);
-    if (fl < 2 * 16 * 64) fl = 2 * 16 * 64;                       // exchange area of the position halves
-    c2s_ensure_init();
-    dim3 grid(p.nslices, p.CinP / 32, p.CoutB / 64);
-    hipLaunchKernelGGL((conv_wgrad_tile_kernel<K, S, LW, MODE>), grid, dim3(256), fl * sizeof(float), st, p);
-    C2S_CHECK_LAUNCH("conv_wgrad_tile");
-    return C2S_OK;
-}
-
-template <int K, int S>
-int launch_wgrad(const c2s_wgrad_desc* d, WgradParams& p, hipStream_t st) {
-    using C = WCfg<K, S>;
-    if constexpr (S == 1 || K == 4) {   // tiled path: 32- or 16-wide aligned tiles (pad (K-1)/2 kernels)
-        constexpr int TP = TCfg<K, S>::TP;
-        constexpr int MODE = (K == 4) ? 0 : 1;
-        const int pad = (K == 1) ? 0 : 1;
-        const bool geom = d->Win == d->Wout * S && d->Hin == d->Hout * S && d->pad_y == pad && d->pad_x == pad && d->Win % 4 == 0;
-        if (geom && d->Wout % 32 == 0 && d->Hout % (TP / 32) == 0) {
-            if constexpr (K == 3)
-                if (d->C0 + d->C1 <= 10) return launch_wgrad_tile<K, S, 5, 2>(d, p, st);
-            return launch_wgrad_tile<K, S, 5, MODE>(d, p, st);
-        }
-        if (geom && d->Wout == 16 && d->Hout % (TP / 16) == 0) return launch_wgrad_tile<K, S, 4, MODE>(d, p, st);
-    }
-    geometry(d, C::TP, &p.log2pc, &p.tiles_x, &p.tiles_y);
-    p.ntiles = d->N * p.tiles_x * p.tiles_y;
-    const int PC = 1 << p.log2pc, PR = C::TP >> p.log2pc;
-    const int plane = ((PR - 1) * S + K) * ((PC - 1) * S + K);
-    const size_t lds = ((size_t)32 * (plane | 1) + (size_t)64 * (C::TP + 1)) * sizeof(float);
-    c2s_ensure_init();
-    dim3 grid(p.nslices * C::TG, p.CinP / 32, p.CoutB / 64);
-    hipLaunchKernelGGL((conv_wgrad_kernel<K, S>), grid, dim3(256), lds, st, p);
-    C2S_CHECK_LAUNCH("conv_wgrad");
-    return C2S_OK;
+// all slice sums of a backward pass in ONE launch (26 launches of a few dozen workgroups each in a U-TAE step): the caller
+// keeps one slab buffer per layer, builds a table of job records once and reuses it every step (as c2s_pack_batch)
+__global__ void wgrad_reduce_batch_kernel(const ReduceJob* __restrict__ jobs, int njobs) {
+    int j = 0;
+    while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].block_start) ++j;      // a few dozen jobs: linear scan
+    const ReduceJob& jb = jobs[j];
+    reduce_job(jb, (long)(blockIdx.x - jb.block_start) * blockDim.x + threadIdx.x);
 }
 
 int check(const c2s_wgrad_desc* d) {
@@ -1117,21 +1070,138 @@ int check(const c2s_wgrad_desc* d) {
     return C2S_OK;
 }
 
+// Channel counts of the slabs [slice][tap][CinP][CoutB]: whole blocks of 32 input and 64 output channels
+struct SlabDims {
+    int CinP, CoutB;
+};
+SlabDims slab_dims(const c2s_wgrad_desc* d) { return {cdiv(d->C0 + d->C1, 32) * 32, cdiv(d->Cout, 64) * 64}; }
+
+void fill_job(ReduceJob* j, const c2s_wgrad_desc* d, const float* slabs, float* dst, long stride_o, long stride_c,
+              const int* host_tap_off, int accumulate, int block_start) {
+    const SlabDims sd = slab_dims(d);
+    const int NT = d->KH * d->KW;
+    j->slabs = slabs; j->dst = dst; j->so = stride_o; j->sc = stride_c;
+    j->nslices = d->nslices; j->NT = NT; j->Cin = d->C0 + d->C1; j->Cout = d->Cout;
+    j->CinP = sd.CinP; j->CoutB = sd.CoutB;
+    j->accumulate = accumulate; j->block_start = block_start;
+    for (int i = 0; i < C2S_MAX_TAPS; ++i) j->taps[i] = i < NT ? host_tap_off[i] : 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ dispatch
+// A/B switches of the family choice, read once per process; '0' turns off: C2S_WINOGRAD the F(2x2,3x3) kernels, C2S_S2WINO or
+// C2S_S2WINO_WGRAD the F(2x2,2x2) kernel, C2S_WGRAD_WINO_CB2 the 8-wave form of F(2x2,3x3).
+struct WgradSwitches {
+    bool winograd, s2wino, s2wino_wgrad, wino_cb2;
+};
+const WgradSwitches& wgrad_switches() {
+    static const WgradSwitches s = [] {
+        auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+        return WgradSwitches{!off("C2S_WINOGRAD"), !off("C2S_S2WINO"), !off("C2S_S2WINO_WGRAD"), !off("C2S_WGRAD_WINO_CB2")};
+    }();
+    return s;
+}
+int g_wgrad_f23 = -1, g_wgrad_f22 = -1;     // -1: from the environment; 0 / 1: set by c2s_wgrad_algorithms (A/B tests)
+
+// Kernel families; the values are those c2s_wgrad_path reports (the table in include/c2s_hip.h).
+enum WgradFamily {
+    WG_UNSUPPORTED = -1, WG_GENERIC = 0, WG_TILE32 = 1, WG_TILE16 = 2, WG_TILE_FIRST = 3, WG_WINO4 = 4, WG_WINO8 = 5, WG_S2WINO = 6
+};
+
+struct WgradPlan {
+    WgradFamily family;
+    int log2pc, tiles_x, tiles_y, ntiles;     // tiles of 2^log2pc positions a row; ntiles over all frames
+    dim3 grid;                                // (slices [x tap groups], input-channel blocks, output-channel blocks)
+    int block;
+    size_t lds;                               // dynamic LDS bytes
+};
+
+// The plan of the (K, S) instantiations.  f23 / f22 / cb2: the Winograd families and the 8-wave form are allowed.
+template <int K, int S>
+void choose(const c2s_wgrad_desc* d, bool f23, bool f22, bool cb2, WgradPlan& pl) {
+    using W = WCfg<K, S>;
+    using T = TCfg<K, S>;
+    constexpr int PAD = (K == 1) ? 0 : 1;
+    constexpr bool TILED = S == 1 || K == 4;      // instantiations of the tile kernel (pad (K-1)/2 kernels)
+    constexpr int MODE = (K == 4) ? 0 : 1;
+    const SlabDims sd = slab_dims(d);
+    const int Cin = d->C0 + d->C1;
+    // the output plane is the input plane over S: every family but the generic one.  (With the widths below Win is a multiple
+    // of 16, so the float4 rows are aligned; the `Win % 4 == 0` this test once carried was implied.)
+    const bool geom = d->Win == d->Wout * S && d->Hin == d->Hout * S && d->pad_y == PAD && d->pad_x == PAD;
+    // planes that tile into 4 x 32 output pixels, at least one full MFMA block of channels
+    const bool wino = geom && d->Wout % 32 == 0 && d->Hout % 4 == 0 && Cin >= 32 && d->Cout >= 32;
+    int tp = T::TP, cw = 32, tap_groups = 1;       // positions per tile, input channels per workgroup, workgroups per slice
+    pl.log2pc = 5;
+    pl.block = 256;
+    if (K == 3 && S == 1 && f23 && wino) {
+        const bool wide = cb2 && sd.CinP % 64 == 0;
+        pl.family = wide ? WG_WINO8 : WG_WINO4;
+        pl.lds = ww_lds_bytes(wide ? 2 : 1);
+        pl.block = wide ? 512 : 256;
+        cw = wide ? 64 : 32;
+        tp = 128;
+    } else if (K == 4 && S == 2 && f22 && wino && d->C0 % 4 == 0) {
+        pl.family = WG_S2WINO;
+        pl.lds = s2w_lds_bytes();
+        pl.block = 512;
+        tp = 128;
+    } else if (TILED && geom && d->Wout % 32 == 0 && d->Hout % (T::TP / 32) == 0) {
+        pl.family = K == 3 && Cin <= 10 ? WG_TILE_FIRST : WG_TILE32;
+        pl.lds = T::lds_bytes(5, pl.family == WG_TILE_FIRST ? 2 : MODE);
+    } else if (TILED && geom && d->Wout == 16 && d->Hout % (T::TP / 16) == 0) {
+        pl.family = WG_TILE16;
+        pl.log2pc = 4;
+        pl.lds = T::lds_bytes(4, MODE);
+    } else {                                       // any plane: tiles as wide as the plane allows, partial tiles masked
+        pl.family = WG_GENERIC;
+        while (pl.log2pc > 2 && (1 << pl.log2pc) > d->Wout) --pl.log2pc;
+        pl.lds = W::lds_bytes(pl.log2pc);
+        tp = W::TP;
+        tap_groups = W::TG;
+    }
+    pl.tiles_x = cdiv(d->Wout, 1 << pl.log2pc);    // (exact for every family but the generic one)
+    pl.tiles_y = cdiv(d->Hout, tp >> pl.log2pc);
+    pl.ntiles = d->N * pl.tiles_x * pl.tiles_y;
+    pl.grid = dim3(d->nslices * tap_groups, sd.CinP / cw, sd.CoutB / 64);
+}
+
+// The kernel c2s_conv_wgrad launches for a valid descriptor (check()) under the switches as they stand, with its launch
+// geometry.  The launch and the query take it from here.  family = WG_UNSUPPORTED (and the error message set): no kernel is
+// built for (K, S).
+WgradPlan wgrad_plan(const c2s_wgrad_desc* d) {
+    const WgradSwitches& sw = wgrad_switches();
+    const bool f23 = g_wgrad_f23 >= 0 ? g_wgrad_f23 != 0 : sw.winograd;
+    const bool f22 = g_wgrad_f22 >= 0 ? g_wgrad_f22 != 0 : sw.s2wino && sw.s2wino_wgrad;
+    WgradPlan pl = {};
+    if (d->KH == 3 && d->S == 1) choose<3, 1>(d, f23, f22, sw.wino_cb2, pl);
+    else if (d->KH == 1 && d->S == 1) choose<1, 1>(d, f23, f22, sw.wino_cb2, pl);
+    else if (d->KH == 4 && d->S == 2) choose<4, 2>(d, f23, f22, sw.wino_cb2, pl);
+    else if (d->KH == 2 && d->S == 2) choose<2, 2>(d, f23, f22, sw.wino_cb2, pl);
+    else if (d->KH == 6 && d->S == 2) choose<6, 2>(d, f23, f22, sw.wino_cb2, pl);
+    else {
+        c2s_set_error("wgrad: unsupported (K=%d,S=%d)", d->KH, d->S);
+        pl.family = WG_UNSUPPORTED;
+    }
+    return pl;
+}
+
+// Kernels that may need more than the default 64 KB of dynamic LDS: exactly the instantiations the switch of c2s_conv_wgrad
+// can launch, but conv_wgrad_winograd_kernel<1> (family 4), whose 58 KB need no raise.
 void init_hook() {
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<3, 1, 5, 2>));
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<3, 1, 5, 1>));
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<3, 1, 4, 1>));
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<1, 1, 5, 1>));
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<1, 1, 4, 1>));
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<4, 2, 5, 0>));
-    C2S_RAISE_LDS((conv_wgrad_tile_kernel<4, 2, 4, 0>));
-    C2S_RAISE_LDS((conv_wgrad_kernel<3, 1>));
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<3, 1, 5, 2>));      // family 3
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<3, 1, 5, 1>));      // family 1
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<3, 1, 4, 1>));      // family 2
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<1, 1, 5, 1>));      // family 1
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<1, 1, 4, 1>));      // family 2
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<4, 2, 5, 0>));      // family 1
+    C2S_RAISE_LDS((conv_wgrad_tile_kernel<4, 2, 4, 0>));      // family 2
+    C2S_RAISE_LDS((conv_wgrad_kernel<3, 1>));                 // family 0, all five
     C2S_RAISE_LDS((conv_wgrad_kernel<1, 1>));
     C2S_RAISE_LDS((conv_wgrad_kernel<4, 2>));
     C2S_RAISE_LDS((conv_wgrad_kernel<2, 2>));
     C2S_RAISE_LDS((conv_wgrad_kernel<6, 2>));
-    C2S_RAISE_LDS(conv_wgrad_winograd_kernel<2>);
-    C2S_RAISE_LDS(conv_wgrad_s2wino_kernel);
+    C2S_RAISE_LDS(conv_wgrad_winograd_kernel<2>);             // family 5 (84 KB)
+    C2S_RAISE_LDS(conv_wgrad_s2wino_kernel);                  // family 6
 }
 C2sInitRegistrar registrar(init_hook);
 
@@ -1149,10 +1219,19 @@ extern "C" int c2s_wgrad_algorithms(int winograd_3x3, int winograd_4x4s2) {
     return C2S_OK;
 }
 
+extern "C" int c2s_wgrad_path(const c2s_wgrad_desc* d, int* family) {
+    if (int rc = check(d)) return rc;
+    C2S_REQUIRE(family, "wgrad_path: null pointer");
+    const WgradPlan pl = wgrad_plan(d);
+    if (pl.family == WG_UNSUPPORTED) return C2S_EINVAL;
+    *family = pl.family;
+    return C2S_OK;
+}
+
 extern "C" size_t c2s_wgrad_workspace_floats(const c2s_wgrad_desc* d) {
     if (!d) return 0;
-    const size_t CinP = (size_t)cdiv(d->C0 + d->C1, 32) * 32, CoutB = (size_t)cdiv(d->Cout, 64) * 64;
-    return (size_t)d->nslices * d->KH * d->KW * CinP * CoutB;
+    const SlabDims sd = slab_dims(d);
+    return (size_t)d->nslices * d->KH * d->KW * sd.CinP * sd.CoutB;
 }
 
 extern "C" int c2s_conv_wgrad(const c2s_wgrad_desc* d, const float* src0, const float* src1, const float* gout,
@@ -1160,86 +1239,43 @@ extern "C" int c2s_conv_wgrad(const c2s_wgrad_desc* d, const float* src0, const 
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(src0 && gout && slabs && (d->C1 == 0 || src1), "wgrad: null pointer");
     C2S_REQUIRE(slab_floats >= c2s_wgrad_workspace_floats(d), "wgrad: slab workspace too small");
+    const WgradPlan pl = wgrad_plan(d);
+    if (pl.family == WG_UNSUPPORTED) return C2S_EINVAL;
+    const SlabDims sd = slab_dims(d);
     WgradParams p;
     p.src0 = src0; p.src1 = src1; p.gout = gout; p.slabs = slabs; p.valid = valid;
     p.N = d->N; p.C0 = d->C0; p.C1 = d->C1; p.Hin = d->Hin; p.Win = d->Win; p.Cout = d->Cout;
     p.Hout = d->Hout; p.Wout = d->Wout; p.pad_y = d->pad_y; p.pad_x = d->pad_x; p.pad_mode = d->pad_mode;
-    p.nslices = d->nslices;
-    p.CinP = cdiv(d->C0 + d->C1, 32) * 32;
-    p.CoutB = cdiv(d->Cout, 64) * 64;
-    hipStream_t st = (hipStream_t)stream;
-    if (wino_wgrad(d)) {
-        c2s_ensure_init();      // conv_wgrad_winograd_kernel<2> needs 84 KB of dynamic LDS: the raise lives in the init hook
-        p.tiles_x = d->Wout / 32;
-        p.tiles_y = d->Hout / 4;
-        p.ntiles = d->N * p.tiles_x * p.tiles_y;
-        p.log2pc = 5;
-        static const bool wide_ok = [] { const char* e = getenv("C2S_WGRAD_WINO_CB2"); return !(e && e[0] == '0'); }();
-        if (wide_ok && p.CinP % 64 == 0) {
-            const size_t ldsb = ((size_t)64 * WW_XP + (size_t)64 * WW_GP) * sizeof(float);
-            dim3 grid(p.nslices, p.CinP / 64, p.CoutB / 64);
-            hipLaunchKernelGGL(conv_wgrad_winograd_kernel<2>, grid, dim3(512), ldsb, st, p);
-        } else {
-            const size_t ldsb = ((size_t)32 * WW_XP + (size_t)64 * WW_GP) * sizeof(float);
-            dim3 grid(p.nslices, p.CinP / 32, p.CoutB / 64);
-            hipLaunchKernelGGL(conv_wgrad_winograd_kernel<1>, grid, dim3(256), ldsb, st, p);
-        }
-        C2S_CHECK_LAUNCH("conv_wgrad_winograd");
-        return C2S_OK;
+    p.nslices = d->nslices; p.ntiles = pl.ntiles; p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.log2pc = pl.log2pc;
+    p.CinP = sd.CinP; p.CoutB = sd.CoutB;
+    c2s_ensure_init();      // the raised dynamic-LDS limits live in the init hook
+    const int K = d->KH;    // (with S, one of the five pairs of wgrad_plan)
+    void (*kernel)(WgradParams);
+    const char* name;
+    switch (pl.family) {
+    case WG_GENERIC:
+        kernel = K == 3 ? conv_wgrad_kernel<3, 1> : K == 1 ? conv_wgrad_kernel<1, 1> : K == 4 ? conv_wgrad_kernel<4, 2>
+               : K == 2 ? conv_wgrad_kernel<2, 2> : conv_wgrad_kernel<6, 2>;
+        name = "conv_wgrad";
+        break;
+    case WG_TILE32:
+        kernel = K == 3 ? conv_wgrad_tile_kernel<3, 1, 5, 1> : K == 1 ? conv_wgrad_tile_kernel<1, 1, 5, 1> : conv_wgrad_tile_kernel<4, 2, 5, 0>;
+        name = "conv_wgrad_tile";
+        break;
+    case WG_TILE16:
+        kernel = K == 3 ? conv_wgrad_tile_kernel<3, 1, 4, 1> : K == 1 ? conv_wgrad_tile_kernel<1, 1, 4, 1> : conv_wgrad_tile_kernel<4, 2, 4, 0>;
+        name = "conv_wgrad_tile";
+        break;
+    case WG_TILE_FIRST: kernel = conv_wgrad_tile_kernel<3, 1, 5, 2>; name = "conv_wgrad_tile"; break;
+    case WG_WINO4: kernel = conv_wgrad_winograd_kernel<1>; name = "conv_wgrad_winograd"; break;
+    case WG_WINO8: kernel = conv_wgrad_winograd_kernel<2>; name = "conv_wgrad_winograd"; break;
+    case WG_S2WINO: kernel = conv_wgrad_s2wino_kernel; name = "conv_wgrad_s2wino"; break;
+    default: return C2S_EINVAL;      // WG_UNSUPPORTED, returned above
     }
-    if (s2wino_wgrad(d)) {
-        c2s_ensure_init();
-        p.tiles_x = d->Wout / 32;
-        p.tiles_y = d->Hout / 4;
-        p.ntiles = d->N * p.tiles_x * p.tiles_y;
-        p.log2pc = 5;
-        const size_t ldsb = ((size_t)32 * S2W_XP + (size_t)64 * WW_GP) * sizeof(float);
-        dim3 grid(p.nslices, p.CinP / 32, p.CoutB / 64);
-        hipLaunchKernelGGL(conv_wgrad_s2wino_kernel, grid, dim3(512), ldsb, st, p);
-        C2S_CHECK_LAUNCH("conv_wgrad_s2wino");
-        return C2S_OK;
-    }
-    if (d->KH == 3 && d->S == 1) return launch_wgrad<3, 1>(d, p, st);
-    if (d->KH == 1 && d->S == 1) return launch_wgrad<1, 1>(d, p, st);
-    if (d->KH == 4 && d->S == 2) return launch_wgrad<4, 2>(d, p, st);
-    if (d->KH == 2 && d->S == 2) return launch_wgrad<2, 2>(d, p, st);
-    if (d->KH == 6 && d->S == 2) return launch_wgrad<6, 2>(d, p, st);
-    c2s_set_error("wgrad: unsupported (K=%d,S=%d)", d->KH, d->S);
-    return C2S_EINVAL;
+    hipLaunchKernelGGL(kernel, pl.grid, dim3(pl.block), pl.lds, (hipStream_t)stream, p);
+    C2S_CHECK_LAUNCH(name);
+    return C2S_OK;
 }
-
-// ---- all slice sums of a backward pass in ONE launch (26 launches of a few dozen workgroups each in a U-TAE step): the
-// caller keeps one slab buffer per layer, builds a table of job records once and reuses it every step (as c2s_pack_batch)
-namespace {
-struct ReduceJob {
-    const float* slabs;
-    float* dst;
-    long so, sc;
-    int nslices, NT, Cin, Cout, CinP, CoutB, accumulate, block_start;
-    int taps[C2S_MAX_TAPS];
-};
-
-__global__ void wgrad_reduce_batch_kernel(const ReduceJob* __restrict__ jobs, int njobs) {
-    int j = 0;
-    while (j + 1 < njobs && (int)blockIdx.x >= jobs[j + 1].block_start) ++j;      // a few dozen jobs: linear scan
-    const ReduceJob& jb = jobs[j];
-    const long total = (long)jb.NT * jb.Cin * jb.Cout;
-    const long t4 = (long)(blockIdx.x - jb.block_start) * blockDim.x + threadIdx.x;
-    const long e = t4 >> 2;
-    const int q = (int)(t4 & 3);
-    const bool live = e < total;
-    const long ee = live ? e : total - 1;
-    const int o = (int)(ee % jb.Cout);
-    const long tc = ee / jb.Cout;
-    const int c = (int)(tc % jb.Cin), t = (int)(tc / jb.Cin);
-    const size_t stride = (size_t)jb.NT * jb.CinP * jb.CoutB;
-    const float acc = slice_sum4(jb.slabs + ((size_t)t * jb.CinP + c) * jb.CoutB + o, stride, jb.nslices, q);   // (= wgrad_reduce_kernel)
-    if (live && q == 0) {
-        float* d = jb.dst + o * jb.so + c * jb.sc + jb.taps[t];
-        *d = jb.accumulate ? *d + acc : acc;
-    }
-}
-}  // namespace
 
 extern "C" size_t c2s_wgrad_reduce_job_bytes(void) { return sizeof(ReduceJob); }
 
@@ -1252,13 +1288,7 @@ extern "C" int c2s_wgrad_reduce_job_fill(void* host_record, const c2s_wgrad_desc
                                          long stride_o, long stride_c, const int* host_tap_off, int accumulate, int block_start) {
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(host_record && slabs && dst && host_tap_off && block_start >= 0, "wgrad_reduce_job_fill: bad args");
-    ReduceJob* j = reinterpret_cast<ReduceJob*>(host_record);
-    const int NT = d->KH * d->KW, Cin = d->C0 + d->C1;
-    j->slabs = slabs; j->dst = dst; j->so = stride_o; j->sc = stride_c;
-    j->nslices = d->nslices; j->NT = NT; j->Cin = Cin; j->Cout = d->Cout;
-    j->CinP = cdiv(Cin, 32) * 32; j->CoutB = cdiv(d->Cout, 64) * 64;
-    j->accumulate = accumulate; j->block_start = block_start;
-    for (int i = 0; i < C2S_MAX_TAPS; ++i) j->taps[i] = i < NT ? host_tap_off[i] : 0;
+    fill_job(reinterpret_cast<ReduceJob*>(host_record), d, slabs, dst, stride_o, stride_c, host_tap_off, accumulate, block_start);
     return C2S_OK;
 }
 
@@ -1274,14 +1304,9 @@ extern "C" int c2s_wgrad_reduce(const c2s_wgrad_desc* d, const float* slabs, flo
                                 const int* host_tap_off, int accumulate, void* stream) {
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(slabs && dst && host_tap_off, "wgrad_reduce: null pointer");
-    const int NT = d->KH * d->KW;
-    const int Cin = d->C0 + d->C1;
-    TapTable tt;
-    for (int i = 0; i < C2S_MAX_TAPS; ++i) tt.off[i] = i < NT ? host_tap_off[i] : 0;
-    const long total = (long)NT * Cin * d->Cout;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(4 * total, 256)), dim3(256), 0, (hipStream_t)stream, slabs, dst,
-                       d->nslices, NT, Cin, d->Cout, cdiv(Cin, 32) * 32, cdiv(d->Cout, 64) * 64, stride_o, stride_c, tt,
-                       accumulate);
+    ReduceJob job;
+    fill_job(&job, d, slabs, dst, stride_o, stride_c, host_tap_off, accumulate, 0);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(4L * job.NT * job.Cin * job.Cout, 256)), dim3(256), 0, (hipStream_t)stream, job);
     C2S_CHECK_LAUNCH("wgrad_reduce");
     return C2S_OK;
 }

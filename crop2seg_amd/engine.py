@@ -678,15 +678,21 @@ def _wgrad(ctx: Ctx, srcs: Sequence[Tensor], gout: Tensor, Cout: int, Hout: int,
         _wgrad_launch(ctx, srcs, gout, Cout, Hout, Wout, K, S, pad, pad_mode, dst, so, sc, taps, accumulate, valid)
 
 
+def _wgrad_desc(ctx: Ctx, srcs: Sequence[Tensor], Cout: int, Hout: int, Wout: int, K: int, S: int, pad: int,
+                pad_mode: int) -> WgradDesc:
+    """The descriptor of a weight-gradient launch (c2s_wgrad_path answers which kernel it reaches)."""
+    N, C0, Hin, Win = srcs[0].shape
+    C1 = srcs[1].shape[1] if len(srcs) > 1 else 0
+    return WgradDesc(N, C0, C1, Hin, Win, Cout, Hout, Wout, K, K, S, pad, pad, pad_mode,
+                     _wgrad_slices(ctx, N, Hout, Wout, S, C0 + C1, Cout))
+
+
 def _wgrad_launch(ctx: Ctx, srcs: Sequence[Tensor], gout: Tensor, Cout: int, Hout: int, Wout: int, K: int, S: int, pad: int,
                   pad_mode: int, dst: Tensor, so: int, sc: int, taps: Sequence[int], accumulate: int,
                   valid: Optional[Tensor]) -> None:
     s0 = srcs[0]
     s1 = srcs[1] if len(srcs) > 1 else None
-    N, C0, Hin, Win = s0.shape
-    C1 = s1.shape[1] if s1 is not None else 0
-    d = WgradDesc(N, C0, C1, Hin, Win, Cout, Hout, Wout, K, K, S, pad, pad, pad_mode,
-                  _wgrad_slices(ctx, N, Hout, Wout, S, C0 + C1, Cout))
+    d = _wgrad_desc(ctx, srcs, Cout, Hout, Wout, K, S, pad, pad_mode)
     nfl = lib().c2s_wgrad_workspace_floats(C.byref(d))
     batched = REDUCE_BATCH and ctx.tape is not None
     # batched slice sums: one slab buffer per weight and write (they all live until the end of the backward pass); an

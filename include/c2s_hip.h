@@ -229,6 +229,19 @@ int c2s_conv_wgrad(const c2s_wgrad_desc* d, const float* src0, const float* src1
  * for the 4x4 stride-2 layers of DownConvBlock (conv.py:263-271).  1 = on, 0 = the direct split-K kernel, -1 = the default
  * (on unless C2S_WINOGRAD=0 / C2S_S2WINO=0 in the environment).  For A/B tests of two exact-fp32 evaluations. */
 int c2s_wgrad_algorithms(int winograd_3x3, int winograd_4x4s2);
+/* Which kernel family c2s_conv_wgrad launches for this descriptor, under the environment switches and c2s_wgrad_algorithms as
+ * they stand at the call; a pure host query (no device is touched).  C2S_EINVAL for a descriptor c2s_conv_wgrad refuses.
+ *   *family: 0 = generic split-K conv_wgrad_kernel<K,S> (any plane; the only one for K = 2 and K = 6),
+ *            1 = conv_wgrad_tile_kernel on 32-wide tiles (LW = 5, MODE 0 or 1: planes a multiple of 32 wide),
+ *            2 = conv_wgrad_tile_kernel on 16-wide tiles (LW = 4: planes 16 wide),
+ *            3 = conv_wgrad_tile_kernel in its first-layer form (K = 3, Cin <= 10, MODE 2: rows are (tap, cin) pairs),
+ *            4 = Winograd F(2x2,3x3), 4 waves (conv_wgrad_winograd_kernel<1>),
+ *            5 = Winograd F(2x2,3x3), 8 waves (conv_wgrad_winograd_kernel<2>: Cin rounded up to 32 is a multiple of 64, and
+ *                C2S_WGRAD_WINO_CB2=0 is not set),
+ *            6 = F(2x2,2x2) for the 4x4 stride-2 layers (conv_wgrad_s2wino_kernel).
+ * 4 - 6 need Cin >= 32, Cout >= 32 and an output plane of whole 4 x 32 pixel tiles (6 also C0 % 4 == 0); where the algorithms are
+ * switched off those layers fall to 0 - 3, which evaluate the direct form. */
+int c2s_wgrad_path(const c2s_wgrad_desc* d, int* family);
 int c2s_wgrad_reduce(const c2s_wgrad_desc* d, const float* slabs, float* dst, long stride_o, long stride_c,
                      const int* host_tap_off, int accumulate, void* stream);
 /* All slice sums of a backward pass in one launch: one slab buffer per layer, a table of job records (record size

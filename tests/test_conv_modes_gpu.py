@@ -47,7 +47,8 @@ import pytest
 import torch
 
 import conv_ref as R
-from test_conv_paths_gpu import C_FAMILY, SENTINEL, Row, _ctx, _gen, _keep, _observed_wgrad, _randn, _wgrad_kernel
+from test_conv_paths_gpu import C_FAMILY, SENTINEL, Row, _check_wgrad, _ctx, _gen, _keep, _observed_wgrad, _randn
+from test_conv_paths_gpu import EXPECTED_WGRAD as PATHS_WGRAD
 
 pytestmark = pytest.mark.gpu
 
@@ -61,44 +62,46 @@ BOUNDS = {
 }
 OBSERVED = {}           # family -> worst max |err| / (u * A), u of the family
 REACHED = {}            # row id -> set of (family, op, accumulate, reflect_adjoint)
+REACHED_WGRAD = {}      # row id -> set of weight-gradient families (c2s_wgrad_path)
 
 # Table A.  Row of test_conv_paths_gpu; an empty `dgrad` means E.conv2d(..., need_input_grad=False), as functional.py
-# calls the first layer.  All rows are 3x3 stride 1 with a bias.
+# calls the first layer.  All rows are 3x3 stride 1 with a bias.  The last field is the weight-gradient family
+# c2s_wgrad_path reports.
 FIRST_ROWS = [
-    Row("first-10", 3, (10,), 64, 32, 64, 3, 1, "reflect", (), "smallcin", ()),
-    Row("first-10-zeros", 3, (10,), 64, 32, 64, 3, 1, "zeros", (), "smallcin", ()),
+    Row("first-10", 3, (10,), 64, 32, 64, 3, 1, "reflect", (), "smallcin", (), 3),
+    Row("first-10-zeros", 3, (10,), 64, 32, 64, 3, 1, "zeros", (), "smallcin", (), 3),
     # one tile per frame (top and bottom reflection in one patch), odd channel count, blockIdx.y reaches 1
-    Row("first-9-two-blocks", 3, (9,), 128, 8, 32, 3, 1, "reflect", (), "smallcin", ()),
-    Row("first-5", 3, (5,), 64, 16, 32, 3, 1, "zeros", (), "smallcin", ()),        # NP = 5, five masked channels
-    Row("first-4", 3, (4,), 64, 16, 64, 3, 1, "reflect", (), "smallcin", ()),      # NP = 2, full
-    Row("first-1", 3, (1,), 64, 8, 32, 3, 1, "zeros", (), "smallcin", ()),         # NP = 2, three masked channels
+    Row("first-9-two-blocks", 3, (9,), 128, 8, 32, 3, 1, "reflect", (), "smallcin", (), 3),
+    Row("first-5", 3, (5,), 64, 16, 32, 3, 1, "zeros", (), "smallcin", (), 3),     # NP = 5, five masked channels
+    Row("first-4", 3, (4,), 64, 16, 64, 3, 1, "reflect", (), "smallcin", (), 3),   # NP = 2, full
+    Row("first-1", 3, (1,), 64, 8, 32, 3, 1, "zeros", (), "smallcin", (), 3),      # NP = 2, three masked channels
     # the data gradient into 10 channels, added to a prior, with the reflect adjoint: implicit GEMM
-    Row("first-10-dgrad-acc", 3, (10,), 64, 32, 32, 3, 1, "reflect", (1,), "smallcin", ("igemm",)),
+    Row("first-10-dgrad-acc", 3, (10,), 64, 32, 32, 3, 1, "reflect", (1,), "smallcin", ("igemm",), 3),
     # neighbours the predicate refuses: 11 channels; a plane that is no multiple of the 8 x 32 tile
-    Row("first-11", 3, (11,), 64, 16, 32, 3, 1, "reflect", (), "igemm", ()),
-    Row("first-10-ragged-plane", 3, (10,), 64, 20, 36, 3, 1, "reflect", (), "igemm", ()),
+    Row("first-11", 3, (11,), 64, 16, 32, 3, 1, "reflect", (), "igemm", (), 1),
+    Row("first-10-ragged-plane", 3, (10,), 64, 20, 36, 3, 1, "reflect", (), "igemm", (), 0),
 ]
 
 # Table B.  The weight gradient of every row stays on the exact fp32 kernels.
 BF16X3_ROWS = [
-    Row("bx", 3, (64,), 64, 64, 64, 3, 1, "reflect", (0,), "bf16x3", ("bf16x3",)),
-    Row("bx-acc", 3, (64,), 64, 64, 64, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),             # ADJ + accumulate
-    Row("bx-5frames-acc", 5, (64,), 64, 16, 16, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),     # FC = 16, two padded frames
+    Row("bx", 3, (64,), 64, 64, 64, 3, 1, "reflect", (0,), "bf16x3", ("bf16x3",), 5),
+    Row("bx-acc", 3, (64,), 64, 64, 64, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 5),          # ADJ + accumulate
+    Row("bx-5frames-acc", 5, (64,), 64, 16, 16, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 2),  # FC = 16, two padded frames
     # forward CoutP = 96 (MF = 1, three blocks); data gradient into 32 channels; partial tiles both ways
-    Row("bx-ragged-acc", 3, (32,), 72, 12, 40, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),
+    Row("bx-ragged-acc", 3, (32,), 72, 12, 40, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 0),
     # CoutP = 64: MF = 2 with 24 padded output channels; data gradient from 40 channels (5 chunks)
-    Row("bx-cout40-acc", 3, (64,), 40, 24, 40, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),
-    Row("bx-two-sources-acc-skip", 3, (32, 64), 64, 32, 64, 3, 1, "reflect", (0, 1), "bf16x3", ("bf16x3", "bf16x3")),
-    Row("bx-8wide-acc", 3, (128,), 128, 8, 8, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),       # FC = 8
-    Row("bx-4x4-acc", 3, (128,), 128, 4, 4, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),         # FC = 4: all border
-    Row("bx-2x2-acc", 3, (64,), 64, 2, 2, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",)),           # ay_hi < ay_lo
-    Row("bx-zeros-acc", 3, (40,), 64, 8, 32, 3, 1, "zeros", (1,), "bf16x3", ("bf16x3",)),          # no adjoint
-    Row("bx-cout15", 3, (32,), 15, 32, 32, 3, 1, "reflect", (1,), "bf16x3", ("igemm",)),           # Cout % 8 != 0: igemm dgrad
+    Row("bx-cout40-acc", 3, (64,), 40, 24, 40, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 0),
+    Row("bx-two-sources-acc-skip", 3, (32, 64), 64, 32, 64, 3, 1, "reflect", (0, 1), "bf16x3", ("bf16x3", "bf16x3"), 4),
+    Row("bx-8wide-acc", 3, (128,), 128, 8, 8, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 0),    # FC = 8
+    Row("bx-4x4-acc", 3, (128,), 128, 4, 4, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 0),      # FC = 4: all border
+    Row("bx-2x2-acc", 3, (64,), 64, 2, 2, 3, 1, "reflect", (1,), "bf16x3", ("bf16x3",), 0),        # ay_hi < ay_lo
+    Row("bx-zeros-acc", 3, (40,), 64, 8, 32, 3, 1, "zeros", (1,), "bf16x3", ("bf16x3",), 5),       # no adjoint
+    Row("bx-cout15", 3, (32,), 15, 32, 32, 3, 1, "reflect", (1,), "bf16x3", ("igemm",), 1),        # Cout % 8 != 0: igemm dgrad
 ]
 
 TABLES = [("f32", r) for r in FIRST_ROWS] + [("bf16x3", r) for r in BF16X3_ROWS]
 
-PERSISTENT = Row("first-persistent", 0, (10,), 64, 32, 32, 3, 1, "reflect", (), "smallcin", ())   # N: persistent_frames(cus)
+PERSISTENT = Row("first-persistent", 0, (10,), 64, 32, 32, 3, 1, "reflect", (), "smallcin", (), 3)   # N: persistent_frames(cus)
 
 
 def persistent_frames(cus):
@@ -181,7 +184,7 @@ def _run_row(mode, row, monkeypatch, keep=None):
     assert fwd[0] == (row.fwd, "fwd", None, 0, 0), f"{row.id}: forward launch {fwd[0]}, the table says {row.fwd}"
     want = [(k, "dgrad", si, a, radj) for si, (k, a) in enumerate(zip(row.dgrad, row.acc))]
     assert dgrad == want, f"{row.id}: data-gradient launches {dgrad}, the table says {want}"
-    assert wk == _wgrad_kernel(K, S, Cin, row.Cout, H, W, row.chans[0]), f"{row.id}: weight gradient on {wk}"
+    REACHED_WGRAD[row.id] = {_check_wgrad(row.id, ctx, srcs, row.Cout, H, W, K, S, pad, pm, wk, row.wgrad)}
     REACHED[row.id] = {(c[0], c[1], c[3], c[4]) for c in calls} | {(wk, "wgrad", 0, 0)}
 
     # the values
@@ -245,12 +248,13 @@ EXPECTED = {
     ("igemm", "dgrad", 1, 1),
     ("wgrad_direct", "wgrad", 0, 0), ("wgrad_f23", "wgrad", 0, 0),
 }
+EXPECTED_WGRAD = {0, 1, 2, 3, 4, 5}      # (6, the 4x4 stride-2 form, is reached by test_conv_paths_gpu.py)
 
 
 def test_reached_paths_are_the_table(monkeypatch):
-    """Every (family, op, accumulate, reflect_adjoint) the tables reached, against the expected set: a dispatch change that
-    moves a row to another kernel fails its row, one that drops a path altogether fails here.  Rows not run yet in this
-    session (-k selections) run here."""
+    """Every (family, op, accumulate, reflect_adjoint) and every weight-gradient family the tables reached, against the
+    expected sets: a dispatch change that moves a row to another kernel fails its row, one that drops a path altogether fails
+    here.  Rows not run yet in this session (-k selections) run here."""
     for mode, row in TABLES:
         if row.id not in REACHED:
             _run_row(mode, row, monkeypatch)
@@ -259,3 +263,6 @@ def test_reached_paths_are_the_table(monkeypatch):
     reached = set().union(*REACHED.values())
     print("\nworst |err| / (u * A) per kernel family: " + "  ".join(f"{k} {v:.2f}" for k, v in sorted(OBSERVED.items())))
     assert reached == EXPECTED, f"missing {sorted(EXPECTED - reached)}, unexpected {sorted(reached - EXPECTED)}"
+    families = set().union(*REACHED_WGRAD.values())
+    assert families == EXPECTED_WGRAD, f"weight-gradient families reached: {sorted(families)}, expected {sorted(EXPECTED_WGRAD)}"
+    assert EXPECTED_WGRAD | PATHS_WGRAD == set(range(7)), "the two tables together reach every weight-gradient family"

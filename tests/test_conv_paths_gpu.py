@@ -9,7 +9,9 @@ accumulate = 0 there, and padded frames hold finite numbers.  Here:
   the sentinel 1234.5 on the padded frames, which must still be bit-identical after the backward pass;
 - every result meets |got - ref64| <= c * u * A element by element (u = 2^-24, A = the same map on absolute values) and
   the Frobenius bars of test_ops_gpu.py (2e-6 forward, 5e-6 gradients);
-- every row asserts the kernels it reached, and test_reached_paths_are_the_table asserts the whole set.
+- every row asserts the kernels it reached, and test_reached_paths_are_the_table asserts the whole set.  The weight-gradient
+  kernel is the family c2s_wgrad_path reports (the table in include/c2s_hip.h) against the row's literal, and the class of
+  that family (WGRAD_CLASS) against the one observed from bit-identity with the forced runs.
 
 Error constants c per kernel family: about 4x the worst ratio max |err| / (u * A) observed over the rows of the family on
 an MI355X (printed with -s), capped at 1024; an indexing or accumulation bug lands near 1/u ~ 1e7.  Observed worst ratios:
@@ -21,6 +23,7 @@ The rows can fail: with the 8-wave Winograd epilogue changed to skip the accumul
 part of the project), the five rows that accumulate through that kernel fail here while every convolution test of
 test_ops_gpu.py still passes.
 """
+import ctypes
 import math
 import zlib
 from typing import NamedTuple, Tuple
@@ -39,6 +42,9 @@ C_FAMILY = {
 }
 OBSERVED = {}           # family -> worst ratio over the rows that ran
 REACHED = {}            # row id -> set of (kernel, accumulate, reflect_adjoint)
+REACHED_WGRAD = {}      # row id -> set of weight-gradient families (c2s_wgrad_path)
+# class of a c2s_wgrad_path family: which algorithm it evaluates, hence how it rounds (keys of C_FAMILY)
+WGRAD_CLASS = ("wgrad_direct",) * 4 + ("wgrad_f23",) * 2 + ("wgrad_f22",)
 
 
 def _engine():
@@ -78,19 +84,29 @@ def _note(family, ratio):
     OBSERVED[family] = max(OBSERVED.get(family, 0.0), ratio)
 
 
-def _wgrad_kernel(K, S, cin, cout, Hout, Wout, c0, f23=True, f22=True):
-    """conv_wgrad.hip's choice (wino_wgrad / s2wino_wgrad) for the launch, restated."""
-    if f23 and K == 3 and S == 1 and cin >= 32 and cout >= 32 and Wout % 32 == 0 and Hout % 4 == 0:
-        return "wgrad_f23"
-    if f22 and K == 4 and S == 2 and Wout % 32 == 0 and Hout % 4 == 0 and cin >= 32 and cout >= 32 and c0 % 4 == 0:
-        return "wgrad_f22"
-    return "wgrad_direct"
+def wgrad_family(ctx, srcs, Cout, Ho, Wo, K, S, pad, pm):
+    """The family c2s_wgrad_path reports for the launch engine._wgrad_launch makes of these arguments, under the switches as
+    they stand.  `ctx` needs its CU count only, `srcs` their shapes: no device is touched."""
+    E, _ = _engine()
+    fam = ctypes.c_int(-1)
+    rc = E.lib().c2s_wgrad_path(ctypes.byref(E._wgrad_desc(ctx, srcs, Cout, Ho, Wo, K, S, pad, pm)), ctypes.byref(fam))
+    assert rc == 0, E.lib().c2s_last_error()
+    return fam.value
+
+
+def _check_wgrad(name, ctx, srcs, Cout, Ho, Wo, K, S, pad, pm, observed, expected):
+    """The reported family is the literal one, and its class is the one observed."""
+    fam = wgrad_family(ctx, srcs, Cout, Ho, Wo, K, S, pad, pm)
+    assert WGRAD_CLASS[fam] == observed, f"{name}: c2s_wgrad_path reports family {fam}, the weight gradient ran on {observed}"
+    assert fam == expected, f"{name}: weight gradient on family {fam}, the table says {expected}"
+    return fam
 
 
 def _observed_wgrad(ctx, srcs, gout, Cout, Ho, Wo, K, S, pad, pm, so, sc, taps, valid, got):
-    """The weight-gradient kernel that produced `got`, observed.  The library does not report its choice, but the split-K
-    kernels and their fixed-order slice sum are deterministic and the algorithms round differently: `got` is bit-identical to
-    the forced run of the algorithm that ran, and to that one only (c2s_wgrad_algorithms, reset to -1 in finally)."""
+    """The weight-gradient algorithm that produced `got`, observed, to hold against the library's report (_check_wgrad).  The
+    split-K kernels and their fixed-order slice sum are deterministic and the algorithms round differently: `got` is
+    bit-identical to the forced run of the algorithm that ran, and to that one only (c2s_wgrad_algorithms, reset to -1 in
+    finally)."""
     E, _ = _engine()
     runs = {}
     try:
@@ -145,42 +161,43 @@ class Row(NamedTuple):
     acc: Tuple[int, ...]          # per source: prior gradient on the tape
     fwd: str                      # forward kernel it must reach
     dgrad: Tuple[str, ...]        # data-gradient kernel per source
+    wgrad: int                    # weight-gradient family (c2s_wgrad_path)
 
 
 ROWS = [
     # 8-wave Winograd (conv_winograd16.hip) forward + data gradient with the reflect adjoint
-    Row("wino16", 3, (64,), 64, 64, 64, 3, 1, "reflect", (0,), "wino16", ("wino16",)),
-    Row("wino16-acc", 3, (64,), 64, 64, 64, 3, 1, "reflect", (1,), "wino16", ("wino16",)),
-    Row("wino16-5frames-acc", 5, (64,), 64, 32, 64, 3, 1, "reflect", (1,), "wino16", ("wino16",)),
+    Row("wino16", 3, (64,), 64, 64, 64, 3, 1, "reflect", (0,), "wino16", ("wino16",), 5),
+    Row("wino16-acc", 3, (64,), 64, 64, 64, 3, 1, "reflect", (1,), "wino16", ("wino16",), 5),
+    Row("wino16-5frames-acc", 5, (64,), 64, 32, 64, 3, 1, "reflect", (1,), "wino16", ("wino16",), 5),
     # ragged: partial tiles both ways; the data gradient into 32 channels runs on the implicit GEMM
-    Row("wino16-ragged", 3, (32,), 72, 12, 40, 3, 1, "reflect", (0,), "wino16", ("igemm",)),
-    Row("wino16-ragged-acc", 3, (32,), 72, 12, 40, 3, 1, "reflect", (1,), "wino16", ("igemm",)),
+    Row("wino16-ragged", 3, (32,), 72, 12, 40, 3, 1, "reflect", (0,), "wino16", ("igemm",), 0),
+    Row("wino16-ragged-acc", 3, (32,), 72, 12, 40, 3, 1, "reflect", (1,), "wino16", ("igemm",), 0),
     # ... and the 8-wave data gradient into 72 channels (a half-empty second block of 64) on partial tiles
-    Row("wino16-ragged-dgrad-acc", 3, (72,), 64, 12, 40, 3, 1, "reflect", (1,), "wino16", ("wino16",)),
+    Row("wino16-ragged-dgrad-acc", 3, (72,), 64, 12, 40, 3, 1, "reflect", (1,), "wino16", ("wino16",), 0),
     # 4-wave Winograd (conv_winograd.hip): 16 x 16 planes, ragged channel counts
-    Row("wino4", 3, (128,), 128, 16, 16, 3, 1, "reflect", (0,), "wino4", ("wino4",)),
-    Row("wino4-acc", 3, (128,), 128, 16, 16, 3, 1, "reflect", (1,), "wino4", ("wino4",)),
-    Row("wino4-ragged-acc", 3, (36,), 64, 16, 32, 3, 1, "reflect", (1,), "wino4", ("igemm",)),
-    Row("wino4-ragged-dgrad-acc", 3, (64,), 36, 16, 32, 3, 1, "reflect", (1,), "igemm", ("wino4",)),
+    Row("wino4", 3, (128,), 128, 16, 16, 3, 1, "reflect", (0,), "wino4", ("wino4",), 2),
+    Row("wino4-acc", 3, (128,), 128, 16, 16, 3, 1, "reflect", (1,), "wino4", ("wino4",), 2),
+    Row("wino4-ragged-acc", 3, (36,), 64, 16, 32, 3, 1, "reflect", (1,), "wino4", ("igemm",), 5),
+    Row("wino4-ragged-dgrad-acc", 3, (64,), 36, 16, 32, 3, 1, "reflect", (1,), "igemm", ("wino4",), 5),
     # two sources [up, skip] (UpConvBlock conv1), the prior on the second source only
-    Row("two-sources-acc-skip", 3, (32, 64), 64, 32, 64, 3, 1, "reflect", (0, 1), "wino16", ("igemm", "wino16")),
+    Row("two-sources-acc-skip", 3, (32, 64), 64, 32, 64, 3, 1, "reflect", (0, 1), "wino16", ("igemm", "wino16"), 4),
     # implicit GEMM 3x3 (conv_igemm.hip): Cout < 64, 4 x 4 maps, 32-channel decoder layers
-    Row("igemm-cout32", 3, (64,), 32, 32, 32, 3, 1, "reflect", (0,), "igemm", ("wino16",)),
-    Row("igemm-cout32-acc", 3, (64,), 32, 32, 32, 3, 1, "reflect", (1,), "igemm", ("wino16",)),
-    Row("igemm-32ch", 3, (32,), 32, 32, 32, 3, 1, "reflect", (0,), "igemm", ("igemm",)),
-    Row("igemm-32ch-acc", 3, (32,), 32, 32, 32, 3, 1, "reflect", (1,), "igemm", ("igemm",)),
-    Row("igemm-4x4", 3, (128,), 128, 4, 4, 3, 1, "reflect", (0,), "igemm", ("igemm",)),
-    Row("igemm-4x4-acc", 3, (128,), 128, 4, 4, 3, 1, "reflect", (1,), "igemm", ("igemm",)),
+    Row("igemm-cout32", 3, (64,), 32, 32, 32, 3, 1, "reflect", (0,), "igemm", ("wino16",), 5),
+    Row("igemm-cout32-acc", 3, (64,), 32, 32, 32, 3, 1, "reflect", (1,), "igemm", ("wino16",), 5),
+    Row("igemm-32ch", 3, (32,), 32, 32, 32, 3, 1, "reflect", (0,), "igemm", ("igemm",), 4),
+    Row("igemm-32ch-acc", 3, (32,), 32, 32, 32, 3, 1, "reflect", (1,), "igemm", ("igemm",), 4),
+    Row("igemm-4x4", 3, (128,), 128, 4, 4, 3, 1, "reflect", (0,), "igemm", ("igemm",), 0),
+    Row("igemm-4x4-acc", 3, (128,), 128, 4, 4, 3, 1, "reflect", (1,), "igemm", ("igemm",), 0),
     # implicit GEMM 1x1
-    Row("igemm-1x1-acc", 3, (64,), 32, 32, 32, 1, 1, "zeros", (1,), "igemm", ("igemm",)),
+    Row("igemm-1x1-acc", 3, (64,), 32, 32, 32, 1, 1, "zeros", (1,), "igemm", ("igemm",), 1),
     # 4x4 stride 2: F(2x2,2x2) forward (conv_s2wino.hip) + data gradient (conv_s2dgrad.hip)
-    Row("s2", 3, (64,), 64, 128, 128, 4, 2, "reflect", (0,), "s2wino", ("s2dgrad",)),
-    Row("s2-acc", 3, (64,), 64, 128, 128, 4, 2, "reflect", (1,), "s2wino", ("s2dgrad",)),
-    Row("s2-ragged", 3, (8,), 72, 24, 80, 4, 2, "reflect", (0,), "s2wino", ("s2dgrad",)),
-    Row("s2-ragged-acc", 3, (8,), 72, 24, 80, 4, 2, "reflect", (1,), "s2wino", ("s2dgrad",)),
+    Row("s2", 3, (64,), 64, 128, 128, 4, 2, "reflect", (0,), "s2wino", ("s2dgrad",), 6),
+    Row("s2-acc", 3, (64,), 64, 128, 128, 4, 2, "reflect", (1,), "s2wino", ("s2dgrad",), 6),
+    Row("s2-ragged", 3, (8,), 72, 24, 80, 4, 2, "reflect", (0,), "s2wino", ("s2dgrad",), 0),
+    Row("s2-ragged-acc", 3, (8,), 72, 24, 80, 4, 2, "reflect", (1,), "s2wino", ("s2dgrad",), 0),
     # gy narrower than 32: implicit GEMM forward, transposed-row fallback of the data gradient (conv_xpair.hip)
-    Row("xpair", 3, (64,), 64, 32, 32, 4, 2, "reflect", (0,), "igemm", ("xpair",)),
-    Row("xpair-acc", 3, (64,), 64, 32, 32, 4, 2, "reflect", (1,), "igemm", ("xpair",)),
+    Row("xpair", 3, (64,), 64, 32, 32, 4, 2, "reflect", (0,), "igemm", ("xpair",), 2),
+    Row("xpair-acc", 3, (64,), 64, 32, 32, 4, 2, "reflect", (1,), "igemm", ("xpair",), 2),
 ]
 
 
@@ -220,7 +237,7 @@ def _run_row(row: Row):
     wk = _observed_wgrad(ctx, srcs, gd, row.Cout, Ho, Wo, K, S, pad, pm, Cin * K * K, K * K, list(range(K * K)), vd,
                          ctx.g["w"])
     assert (fwd, dgrad) == (row.fwd, row.dgrad), f"{row.id}: reached {fwd} / {dgrad}, the table says {row.fwd} / {row.dgrad}"
-    assert wk == _wgrad_kernel(K, S, Cin, row.Cout, Ho, Wo, row.chans[0]), f"{row.id}: weight gradient on {wk}"
+    REACHED_WGRAD[row.id] = {_check_wgrad(row.id, ctx, srcs, row.Cout, Ho, Wo, K, S, pad, pm, wk, row.wgrad)}
     REACHED[row.id] = {(k, a, radj) for k, a in zip(dgrad, row.acc)} | {(wk, 0, 0)}
 
     got_gx = torch.cat([ctx.tape.grads[s.data_ptr()].cpu() for s in srcs], 1)
@@ -250,6 +267,7 @@ def test_conv2d_path(row):
 # transposed and depthwise convolutions: the "existing gradient" branch
 # =================================================================================================
 TRANSPOSE_SHAPES = [(2, 128, 64, 4, 4), (2, 64, 32, 16, 16), (1, 32, 32, 64, 64)]     # no frame flags on this op
+TRANSPOSE_WGRAD = {TRANSPOSE_SHAPES[0]: 0, TRANSPOSE_SHAPES[1]: 2, TRANSPOSE_SHAPES[2]: 6}     # weight-gradient family
 
 
 def _run_transpose(shape):
@@ -273,7 +291,8 @@ def _run_transpose(shape):
     assert ("w", "dgrad") in ctx._packed and ("w", "fwd", 0) in ctx._packed
     # dW = conv4x4s2 weight gradient with (input = gout, gout = x), as engine.conv_transpose2d launches it
     wk = _observed_wgrad(ctx, [gd], xd, Cin, H, W, 4, 2, 1, L.PAD_ZEROS, Cout * 16, 16, list(range(16)), None, ctx.g["w"])
-    assert wk == _wgrad_kernel(4, 2, Cout, Cin, H, W, Cout), f"transpose{shape}: weight gradient on {wk}"
+    REACHED_WGRAD[f"transpose{shape}"] = {_check_wgrad(f"transpose{shape}", ctx, [gd], Cin, H, W, 4, 2, 1, L.PAD_ZEROS, wk,
+                                                       TRANSPOSE_WGRAD[shape])}
     REACHED[f"transpose{shape}"] = {("igemm", 1, 0), (wk, 0, 0)}
     c = {"fwd": C_FAMILY["xpair"], "dgrad": C_FAMILY["igemm"], "wgrad": C_FAMILY[wk]}
     ratios = R.check_conv(out.cpu(), ctx.tape.grads[xd.data_ptr()].cpu(), ctx.g["w"].cpu(), x, w, b, gout, keep, 2, 1,
@@ -334,6 +353,7 @@ WGRAD_TWICE = [
     (3, 1, 3, 64, 64, 32, 32),          # F(2x2,3x3) and direct
     (4, 2, 3, 64, 64, 64, 64),          # F(2x2,2x2) and direct
 ]
+WGRAD_TWICE_FAMILY = {(3, 1): {True: 5, False: 1}, (4, 2): {True: 6, False: 1}}      # (K, S) -> forced fast / forced direct
 
 
 def _two_layer_refs(x1, x2, w, gout1, gout2, keep, K, S, pad):
@@ -355,7 +375,9 @@ def _wgrad_twice(K, S, N, Cc, Cout, H, W, fast):
     try:
         E.lib().c2s_wgrad_algorithms(int(fast) if K == 3 else -1, int(fast) if K == 4 else -1)
         v = keep.int().cuda()
-        y1 = E.conv2d(ctx, [x1.cuda()], "w", None, K, S, pad, L.PAD_REFLECT, v, need_input_grad=False)
+        x1d = x1.cuda()
+        fam = wgrad_family(ctx, [x1d], Cout, Ho, Wo, K, S, pad, L.PAD_REFLECT)
+        y1 = E.conv2d(ctx, [x1d], "w", None, K, S, pad, L.PAD_REFLECT, v, need_input_grad=False)
         y2 = E.conv2d(ctx, [x2.cuda()], "w", None, K, S, pad, L.PAD_REFLECT, v, need_input_grad=False)
         ctx.tape.grads[y1.data_ptr()] = g1.cuda()
         ctx.tape.grads[y2.data_ptr()] = g2.cuda()
@@ -363,20 +385,22 @@ def _wgrad_twice(K, S, N, Cc, Cout, H, W, fast):
         torch.cuda.synchronize()
     finally:
         E.lib().c2s_wgrad_algorithms(-1, -1)
-    wk = _wgrad_kernel(K, S, Cc, Cout, Ho, Wo, Cc, f23=fast, f22=fast)
+    assert fam == WGRAD_TWICE_FAMILY[K, S][fast], f"forced {'fast' if fast else 'direct'}: weight gradient on family {fam}"
+    wk = WGRAD_CLASS[fam]
     assert (wk != "wgrad_direct") == fast
     ref, A = _two_layer_refs(x1, x2, w, g1, g2, keep, K, S, pad)
     ratio = R.assert_within(f"weight gradient written twice ({wk})", ctx.g["w"], ref, A, C_FAMILY[wk], R.FROB_GRAD)
     _note(wk, ratio)
     print(f"\nwgrad twice {wk}: {ratio:.2f}")
-    return wk, ctx.g["w"].cpu()
+    return wk, fam, ctx.g["w"].cpu()
 
 
 @pytest.mark.parametrize("K,S,N,Cc,Cout,H,W", WGRAD_TWICE)
 def test_weight_gradient_written_twice(K, S, N, Cc, Cout, H, W):
-    wk_fast, fast = _wgrad_twice(K, S, N, Cc, Cout, H, W, True)
-    wk_direct, direct = _wgrad_twice(K, S, N, Cc, Cout, H, W, False)
+    wk_fast, fam_fast, fast = _wgrad_twice(K, S, N, Cc, Cout, H, W, True)
+    wk_direct, fam_direct, direct = _wgrad_twice(K, S, N, Cc, Cout, H, W, False)
     assert not torch.equal(fast, direct), "the forced weight-gradient algorithms must be different kernels"
+    REACHED_WGRAD[f"twice{K}{S}"] = {fam_fast, fam_direct}
     REACHED[f"twice{K}{S}"] = {(wk_fast, 0, 0), (wk_fast, 1, 0), (wk_direct, 0, 0), (wk_direct, 1, 0)}
 
 
@@ -451,12 +475,13 @@ EXPECTED = {
     ("wgrad_direct", 0, 0), ("wgrad_direct", 1, 0), ("wgrad_f23", 0, 0), ("wgrad_f23", 1, 0),
     ("wgrad_f22", 0, 0), ("wgrad_f22", 1, 0), ("dw_wgrad", 0, 0),
 }
+EXPECTED_WGRAD = {0, 1, 2, 4, 5, 6}      # (3, the first-layer form, is reached by test_conv_modes_gpu.py: seven in all)
 
 
 def test_reached_paths_are_the_table(monkeypatch):
-    """Every (kernel, accumulate, reflect_adjoint) the table reached, against the expected set: a dispatch change that
-    moves a row to another kernel fails its row, one that drops a path altogether fails here.  Rows not run yet in this
-    session (-k selections) run here."""
+    """Every (kernel, accumulate, reflect_adjoint) and every weight-gradient family the table reached, against the expected
+    sets: a dispatch change that moves a row to another kernel fails its row, one that drops a path altogether fails here.
+    Rows not run yet in this session (-k selections) run here."""
     for row in ROWS:
         if row.id not in REACHED:
             _run_row(row)
@@ -474,3 +499,5 @@ def test_reached_paths_are_the_table(monkeypatch):
     reached = set().union(*REACHED.values())
     print("\nworst |err| / (u * A) per kernel family: " + "  ".join(f"{k} {v:.2f}" for k, v in sorted(OBSERVED.items())))
     assert reached == EXPECTED, f"missing {sorted(EXPECTED - reached)}, unexpected {sorted(reached - EXPECTED)}"
+    families = set().union(*REACHED_WGRAD.values())
+    assert families == EXPECTED_WGRAD, f"weight-gradient families reached: {sorted(families)}, expected {sorted(EXPECTED_WGRAD)}"
