@@ -94,6 +94,17 @@ def clip_runs(runs: List[Tuple[int, int]], lo: int, hi: int) -> List[Tuple[int, 
     return [(max(b, lo), min(e, hi)) for b, e in runs if min(e, hi) > max(b, lo)]
 
 
+def early_cut(names: List[str], written, flags: List[bool]) -> int:
+    """First index of the early bucket of the two-bucket gradient exchange: the longest suffix of `names` whose gradients are
+    final when the backward pass enters the per-frame encoder, i.e. every slot in it is in `written` or frozen (flags False:
+    never written).  An unwritten trainable slot ends the walk, whatever lies in front of it.  0 (the encoder has nothing left
+    to write) and len(names) (nothing final yet) both mean: no early bucket."""
+    i = len(names)
+    while i > 0 and (names[i - 1] in written or not flags[i - 1]):
+        i -= 1
+    return i
+
+
 class TrainStep:
     """One optimiser step of the reference's training loop (src/learning/utils.py:314-328) with everything on
     the HIP engine and no autograd graph:
@@ -193,9 +204,7 @@ class TrainStep:
             # step) still runs; the encoder's own gradients follow after the join.
             def early_exchange():
                 tape.flush_side()                        # the weight-gradient launches queued so far
-                i = len(self.names)                      # the suffix of final gradients, frozen slots (never written) included
-                while i > 0 and (self.names[i - 1] in ctx._gwritten or not flags[i - 1]):
-                    i -= 1
+                i = early_cut(self.names, ctx._gwritten, flags)   # the suffix of final gradients, frozen slots included
                 if i == 0 or i == len(self.names):
                     return
                 off = self.offsets[i]
