@@ -156,6 +156,11 @@ SIGNATURES = {
     "c2s_collate_series_ndvi": (I, [P, I, P, P, P, P, P, I, I, I, I, I, C.POINTER(I), C.POINTER(F), C.POINTER(F), F, I, I, P]),
     "c2s_softmax_stitch": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),
     "c2s_adam_flat": (I, [P, P, P, P, L, F, F, F, F, I, P, F, P]),
+    "c2s_grad_sumsq_workspace_doubles": (SZ, []),
+    "c2s_grad_sumsq": (I, [P, P, P, I, L, P, SZ, P, P]),
+    "c2s_step_decide": (I, [P, F, F, I, P, P, I, P, P]),
+    "c2s_adam_slots": (I, [P, P, P, P, P, P, P, I, L, F, F, F, F, P, P]),
+    "c2s_restore_if_skipped": (I, [P, P, L, P, P]),
     "c2s_fill": (I, [P, L, F, P]),
     "c2s_add_inplace": (I, [P, P, L, P]),
 }

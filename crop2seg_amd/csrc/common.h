@@ -55,6 +55,22 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// One element of torch.optim.Adam (train.py:454, torch defaults): shared by adam_kernel (misc.hip) and adam_slots_kernel
+// (guard.hip) so that the two cannot drift apart.  bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step) (adam_bias).
+__device__ __forceinline__ void adam_bias(float b1, float b2, int st, float& bc1, float& bc2s) {
+    bc1 = 1.f - powf(b1, (float)st);
+    bc2s = sqrtf(1.f - powf(b2, (float)st));
+}
+__device__ __forceinline__ void adam_element(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, long i, float lr, float b1, float b2, float eps,
+                                             float bc1, float bc2s, float gscale) {
+    const float gg = g[i] * gscale;
+    const float mm = b1 * m[i] + (1.f - b1) * gg;
+    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
+    m[i] = mm; v[i] = vv;
+    const float denom = sqrtf(vv) / bc2s + eps;
+    p[i] -= (lr / bc1) * (mm / denom);
+}
 // taps of the largest packed kernel (the 6x6 stride-2 convolutions): tap tables of the weight packs and slice sums
 constexpr int C2S_MAX_TAPS = 36;
 

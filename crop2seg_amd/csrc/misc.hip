@@ -477,16 +477,10 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
                             const int* __restrict__ step_dev, float gscale) {
     // the step count may live on the device so that a captured graph advances it on replay
     const int st = step_dev != nullptr ? *step_dev : step;
-    const float bc1 = 1.f - powf(b1, (float)st);
-    const float bc2s = sqrtf(1.f - powf(b2, (float)st));
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gg = g[i] * gscale;
-        const float mm = b1 * m[i] + (1.f - b1) * gg;
-        const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm; v[i] = vv;
-        const float denom = sqrtf(vv) / bc2s + eps;
-        p[i] -= (lr / bc1) * (mm / denom);
-    }
+    float bc1, bc2s;
+    adam_bias(b1, b2, st, bc1, bc2s);
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        adam_element(p, g, m, v, i, lr, b1, b2, eps, bc1, bc2s, gscale);     // common.h: shared with guard.hip
 }
 
 __global__ void fill_kernel(float* p, long n, float v) {

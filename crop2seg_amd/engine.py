@@ -189,7 +189,10 @@ class Workspace:
         """Raise if a one-pass normalisation wait gave up since the last check (host synchronisation -- call where the
         caller synchronises anyway).  The groups that gave up wrote NaN, so the step that hit it is lost; recovery: the area
         is re-zeroed and the process falls back to the two-pass normalisation kernels (`engine.ONEPASS_NORM = False`),
-        which need no residency assumption, so the caller may catch the error and carry on with the next batch."""
+        which need no residency assumption.  Whether the caller may catch the error and repeat the step depends on what the
+        lost step did to the optimiser state: under TrainStep(skip_nonfinite=True) the device skipped it and nothing changed;
+        without that guard (or in a loop of the caller's own that ran an optimiser on the NaN gradient) the parameters, Adam
+        moments and BatchNorm running statistics are NaN by now and the last checkpoint has to be restored."""
         if self.sync_error() == 0:
             return
         global ONEPASS_NORM
@@ -199,7 +202,9 @@ class Workspace:
         raise RuntimeError(
             "crop2seg_amd: a one-pass normalisation wait gave up (the workgroups of a group were not co-resident: "
             "shared or masked GPU, profiler serialisation?).  The affected outputs are NaN.  The sync area has been "
-            "reset and this process now uses the two-pass normalisation kernels; repeat the step.")
+            "reset and this process now uses the two-pass normalisation kernels.  Repeat the step if it was a forward pass or "
+            "a TrainStep(skip_nonfinite=True) step (the device skipped the update); otherwise the NaN has reached the "
+            "parameters, the Adam moments and the BatchNorm running statistics: restore the last checkpoint.")
 
     def get(self, name: str, nfloats: int) -> Tensor:
         b = self.bufs.get(name)
@@ -1376,3 +1381,49 @@ def adam_flat(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float =
               b2: float = 0.999, eps: float = 1e-8, grad_scale: float = 1.0, step_dev: Optional[Tensor] = None) -> None:
     check(lib().c2s_adam_flat(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, b1, b2, eps, step,
                               _ptr(step_dev), grad_scale, _stream()), "adam")
+
+
+# Guarded optimiser step (csrc/guard.hip; the layout of the status block: include/c2s_hip.h).  All stream-ordered; `status` is
+# the float64[4] tensor of guard_status(), `slots` int64 [n, 2] (offset, length), `mask` / `slot_steps` int32 [n].
+GUARD_STATUS_BYTES = 32
+
+
+def guard_status(device) -> Tensor:
+    """A zeroed status block; `guard_views` names its fields."""
+    return torch.zeros(GUARD_STATUS_BYTES // 8, device=device, dtype=torch.float64)
+
+
+def guard_views(status: Tensor) -> Dict[str, Tensor]:
+    """0-dim views of the status block's fields (no copy, no synchronisation until a value is read)."""
+    f, i = status.view(torch.float32), status.view(torch.int32)
+    return {"sumsq": status[0], "ok": i[2], "scale": f[3], "norm": f[4], "coef": f[5]}
+
+
+def grad_sumsq(g: Tensor, slots: Tensor, mask: Tensor, ws: Workspace, status: Tensor) -> None:
+    """status.sumsq = sum of squares of the trainable slots of `g`, in float64 and in a fixed order."""
+    n = lib().c2s_grad_sumsq_workspace_doubles()
+    w = ws.get("grad_sumsq", 2 * n)                      # n doubles (the allocator's blocks are 8-byte aligned)
+    check(lib().c2s_grad_sumsq(g.data_ptr(), slots.data_ptr(), mask.data_ptr(), mask.numel(), g.numel(), w.data_ptr(), n,
+                               status.data_ptr(), _stream()), "grad_sumsq")
+
+
+def step_decide(status: Tensor, max_grad_norm: Optional[float], grad_scale: float, skip_nonfinite: bool, mask: Tensor,
+                slot_steps: Tensor, skip_count: Tensor) -> None:
+    """Clip coefficient and skip decision from status.sumsq; advances `slot_steps` of the trainable slots or `skip_count`."""
+    check(lib().c2s_step_decide(status.data_ptr(), 0.0 if max_grad_norm is None else float(max_grad_norm), float(grad_scale),
+                                int(bool(skip_nonfinite)), mask.data_ptr(), slot_steps.data_ptr(), mask.numel(),
+                                skip_count.data_ptr(), _stream()), "step_decide")
+
+
+def adam_slots(p: Tensor, g: Tensor, m: Tensor, v: Tensor, slots: Tensor, mask: Tensor, slot_steps: Tensor, status: Tensor,
+               lr: float = 1e-3, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8) -> None:
+    """`adam_flat` over every trainable slot in one launch: per-slot step counts, gradient scale and go-ahead from `status`."""
+    check(lib().c2s_adam_slots(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), slots.data_ptr(), mask.data_ptr(),
+                               slot_steps.data_ptr(), mask.numel(), p.numel(), lr, b1, b2, eps, status.data_ptr(), _stream()),
+          "adam_slots")
+
+
+def restore_if_skipped(dst: Tensor, saved: Tensor, status: Tensor) -> None:
+    """dst = saved where the step was skipped (status.ok == 0); untouched otherwise."""
+    check(lib().c2s_restore_if_skipped(dst.data_ptr(), saved.data_ptr(), dst.numel(), status.data_ptr(), _stream()),
+          "restore_if_skipped")

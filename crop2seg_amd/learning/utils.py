@@ -105,6 +105,17 @@ def early_cut(names: List[str], written, flags: List[bool]) -> int:
     return i
 
 
+def slot_table(offsets: List[int], total: int, flags: List[bool]) -> Tuple[List[Tuple[int, int]], List[int]]:
+    """The table the guarded step's kernels walk (csrc/guard.hip): (offset, padded length) of every slot of the flat buffers --
+    slot i is [offsets[i], offsets[i + 1]), the last one ends at `total` -- and the mask of trainable slots (1 / 0)."""
+    if len(offsets) != len(flags):
+        raise ValueError("slot_table: one flag per slot")
+    ends = list(offsets[1:]) + [total]
+    if any(e < b for b, e in zip(offsets, ends)) or (offsets and offsets[0] < 0):
+        raise ValueError("slot_table: offsets must ascend and end within `total`")
+    return [(b, e - b) for b, e in zip(offsets, ends)], [1 if f else 0 for f in flags]
+
+
 class TrainStep:
     """One optimiser step of the reference's training loop (src/learning/utils.py:314-328) with everything on
     the HIP engine and no autograd graph:
@@ -118,12 +129,33 @@ class TrainStep:
     Fine-tuning: a parameter with requires_grad False (read at every eager step; fixed by capture()) gets no gradient, no
     launch of its own and no update.  The flat layout keeps every parameter; Adam and the gradient exchange cover the runs
     of trainable slots, and, as in torch.optim.Adam, a parameter's step count advances only on the steps where it trained.
+
+    Guarded step (`max_grad_norm` and / or `skip_nonfinite`; with both at their defaults the step launches exactly what it
+    launched without them).  The L2 norm of the gradient -- over the trainable slots, after the data-parallel sum and its
+    1/world scale, so every rank decides alike -- is taken on the device, and one decision launch follows:
+      max_grad_norm: torch.nn.utils.clip_grad_norm_(norm_type=2): coef = min(1, max_grad_norm / (norm + 1e-6)) is folded
+        into the scale Adam applies; `flat_grad` keeps the unclipped sum.
+      skip_nonfinite: if the norm is not finite the step changes nothing, as when torch.optim.Adam.step() is not called:
+        parameters, both moments and the per-parameter step counts stay, and the model's floating-point buffers (BatchNorm
+        running_mean / running_var, re-pointed at views of one flat tensor) are put back to their values from before this
+        step's forward pass.  The integer buffers are not rolled back: `num_batches_tracked` may advance on a skipped step.
+      Without skip_nonfinite a non-finite step is applied as before; skip_nonfinite alone uses coef = 1.
+    Adam then runs as one launch over all slots with per-slot step counts kept on the device (a skip that falls while a
+    parameter is frozen does not count against it).  Nothing inside a step, eager or replayed, synchronises with the host; the
+    readers do: `last_grad_norm` / `last_clip_coef` (device scalars of the last decided step), `skipped_steps()`,
+    `sync_steps()`.  Until `sync_steps()` the host's `param_steps` / `step_count` count a skipped step as taken.
     """
 
     def __init__(self, model, num_classes: int = 15, ignore_index: int = -1, lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, process_group=None,
-                 distributed: bool = False, label_smoothing: float = 0.0, boundary_gamma: float = 2.0):
+                 distributed: bool = False, label_smoothing: float = 0.0, boundary_gamma: float = 2.0,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         self.model = model
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"TrainStep: max_grad_norm must be positive or None, got {max_grad_norm!r}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
         self.label_smoothing = float(label_smoothing)       # train.py:172,466-468
         self.boundary_gamma = float(boundary_gamma)         # FocalCELoss(gamma=2.0), src/learning/utils.py:259
         self.num_classes = num_classes
@@ -160,12 +192,80 @@ class TrainStep:
         self.class_w = cw
         self.step_count = 0
         self.ws = E.Workspace(dev)
+        if self.guarded:
+            self._init_guard(dev)
         self.dp = None
         if distributed:
             from .ddp import FlatDataParallel
             self.dp = FlatDataParallel(process_group)
             # identical initial weights AND BatchNorm buffers on every rank
             self.dp.sync_parameters(self.flat_param, [b for _, b in model.named_buffers()])
+
+    # ------------------------------------------------------------------------------------------------ guarded step
+    def _init_guard(self, dev) -> None:
+        """Device state of the guarded step: slot table, mask, per-slot step counts, status block, skip counter; with
+        skip_nonfinite also the model's floating-point buffers as views of one flat tensor, and its copy."""
+        table, _ = slot_table(self.offsets, self.total, [True] * len(self.offsets))
+        self._slots_dev = torch.tensor(table, device=dev, dtype=torch.int64)
+        self._mask_dev = torch.zeros(len(table), device=dev, dtype=torch.int32)
+        self._mask_flags: Optional[List[bool]] = None            # the flags `_mask_dev` holds
+        self.slot_steps_dev = torch.tensor(self.param_steps, device=dev, dtype=torch.int32)
+        self._status = E.guard_status(dev)
+        self._skip_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+        views = E.guard_views(self._status)
+        self.last_grad_norm, self.last_clip_coef = views["norm"], views["coef"]
+        self._attempts = 0
+        self.flat_buf = self._buf_saved = None
+        if self.skip_nonfinite:
+            fbufs = [b for _, b in self.model.named_buffers() if b.is_floating_point()]
+            n = sum((b.numel() + 3) // 4 * 4 for b in fbufs)
+            self.flat_buf = torch.zeros(n, device=dev, dtype=torch.float32)
+            self._buf_saved = torch.zeros(n, device=dev, dtype=torch.float32)
+            o = 0
+            for b in fbufs:
+                if b.dtype != torch.float32:
+                    raise ValueError("TrainStep(skip_nonfinite=True): floating-point buffers must be float32")
+                view = self.flat_buf[o:o + b.numel()].view_as(b)
+                view.copy_(b.data)
+                b.data = view                           # the module's buffers now alias the flat tensor
+                o += (b.numel() + 3) // 4 * 4
+
+    def _set_mask(self, flags: List[bool]) -> None:
+        """Upload the mask of trainable slots when the flags have changed (stream-ordered copy; never under capture)."""
+        if flags != self._mask_flags:
+            _, mask = slot_table(self.offsets, self.total, flags)
+            self._mask_dev.copy_(torch.tensor(mask, dtype=torch.int32))
+            self._mask_flags = list(flags)
+
+    def _save_buffers(self) -> None:
+        if self.flat_buf is not None and self.flat_buf.numel():
+            self._buf_saved.copy_(self.flat_buf)
+
+    def _guarded_update(self, scale: float) -> None:
+        """norm -> decision -> Adam over all slots -> roll-back of the buffers; the mask is on the device already."""
+        E.grad_sumsq(self.flat_grad, self._slots_dev, self._mask_dev, self.ws, self._status)
+        E.step_decide(self._status, self.max_grad_norm, scale, self.skip_nonfinite, self._mask_dev, self.slot_steps_dev,
+                      self._skip_dev)
+        E.adam_slots(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self._slots_dev, self._mask_dev,
+                     self.slot_steps_dev, self._status, self.lr, self.betas[0], self.betas[1], self.eps)
+        if self.flat_buf is not None and self.flat_buf.numel():
+            E.restore_if_skipped(self.flat_buf, self._buf_saved, self._status)
+
+    def _need_guard(self) -> None:
+        if not self.guarded:
+            raise RuntimeError("TrainStep: built without max_grad_norm / skip_nonfinite, there is no guarded step to read")
+
+    def skipped_steps(self) -> int:
+        """Steps skipped so far because their gradient was not finite (reads a device counter: host synchronisation)."""
+        self._need_guard()
+        return int(self._skip_dev)
+
+    def sync_steps(self) -> None:
+        """Bring the host's `param_steps` / `step_count` in line with the device's counts (host synchronisation): they count
+        a skipped step as taken until this is called."""
+        self._need_guard()
+        self.param_steps = [int(s) for s in self.slot_steps_dev.tolist()]
+        self.step_count = self._attempts - int(self._skip_dev)
 
     # ------------------------------------------------------------------------------------------------
     def trainable_flags(self) -> List[bool]:
@@ -249,7 +349,10 @@ class TrainStep:
         """Host-synchronising health check (every display_step; `StepMeters.watch(step)` calls it from `get_miou_acc()` /
         `loss_mean()`): raises if a one-pass normalisation wait gave up (engine.Workspace.check_sync: the area is reset and
         the process continues on the two-pass kernels).  A captured graph has the one-pass launches baked in, so it is
-        dropped and has to be captured again."""
+        dropped and has to be captured again.  The step that hit the failed wait produced NaN: with skip_nonfinite=True it
+        changed nothing (the device skipped it: `skipped_steps()`), so the caller may catch the error and repeat the step; without
+        it the NaN has gone through Adam into the parameters, the moments and the BatchNorm running statistics, and the
+        way back is the last checkpoint."""
         try:
             self.ws.check_sync()
         except RuntimeError:
@@ -274,6 +377,9 @@ class TrainStep:
         flags = self.trainable_flags()
         if not any(flags):
             raise ValueError("TrainStep: no parameter requires grad")
+        if self.guarded and apply_update:
+            self._set_mask(flags)
+            self._save_buffers()                         # what a skipped step puts back
         loss, logits = self._forward_backward(x.contiguous(), dates.contiguous(), y, drop, overlap_exchange=True, flags=flags)
         xruns = self._xruns(flags)
         scale = 1.0
@@ -292,6 +398,10 @@ class TrainStep:
         if apply_update:
             self.step_count += 1
             self.param_steps = [s + 1 if f else s for s, f in zip(self.param_steps, flags)]
+            if self.guarded:
+                self._attempts += 1
+                self._guarded_update(scale)
+                return loss, logits
             for b, e, st in self._adam_runs(flags):
                 E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], st, self.lr,
                             self.betas[0], self.betas[1], self.eps, grad_scale=scale)
@@ -312,8 +422,11 @@ class TrainStep:
         if not any(flags):
             raise ValueError("TrainStep: no parameter requires grad")
         self.static_x, self.static_dates, self.static_y = x.clone().contiguous(), dates.clone().contiguous(), y.clone()
-        runs = self._adam_runs(flags)                   # one device step counter per Adam launch
-        self.step_dev = torch.tensor([st for _, _, st in runs], device=dev, dtype=torch.int32)
+        if self.guarded:
+            self._set_mask(flags)                       # the guarded step keeps its step counts per slot (slot_steps_dev)
+        else:
+            runs = self._adam_runs(flags)               # one device step counter per Adam launch
+            self.step_dev = torch.tensor([st for _, _, st in runs], device=dev, dtype=torch.int32)
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         drop = self._fresh_dropout()
         drop.seed_dev = self.seed_dev
@@ -338,16 +451,21 @@ class TrainStep:
             # (hipEventQuery), which the default global mode forbids while ANY thread captures
             with torch.cuda.graph(self.graph_fb, capture_error_mode="thread_local"):
                 self.seed_dev.add_(1)
+                if self.guarded:
+                    self._save_buffers()
                 self.static_loss, self.static_logits = self._forward_backward(self.static_x, self.static_dates, self.static_y, drop,
                                                                               flags=flags)
         finally:
             E.REDUCE_BATCH = batch0
         self.graph_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_opt, capture_error_mode="thread_local"):
-            self.step_dev.add_(1)
-            for k, (b, e, _) in enumerate(runs):
-                E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], 0, self.lr,
-                            self.betas[0], self.betas[1], self.eps, grad_scale=scale, step_dev=self.step_dev[k:k + 1])
+            if self.guarded:                            # after the exchange that sits between the two graphs
+                self._guarded_update(scale)
+            else:
+                self.step_dev.add_(1)
+                for k, (b, e, _) in enumerate(runs):
+                    E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], 0, self.lr,
+                                self.betas[0], self.betas[1], self.eps, grad_scale=scale, step_dev=self.step_dev[k:k + 1])
         self._cap_flags = flags
 
     @torch.no_grad()
@@ -367,5 +485,7 @@ class TrainStep:
             self.dp.reduce_gradients(self.flat_grad, runs=self._xruns(flags))     # between the two graphs, on the same stream
         self.graph_opt.replay()
         self.step_count += 1
+        if self.guarded:
+            self._attempts += 1
         self.param_steps = [s + 1 if f else s for s, f in zip(self.param_steps, flags)]
         return self.static_loss, self.static_logits

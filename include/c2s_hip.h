@@ -531,6 +531,48 @@ int c2s_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr
                   int step, const int* step_dev, float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Guarded optimiser step (csrc/guard.hip): gradient-norm clipping and the skip of a non-finite step, decided and applied
+ * on the device.  The reference's loop has neither (train.py:454 is a plain Adam.step()); the semantics are torch's:
+ * clipping as torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) -- total = ||g||_2 over the trainable parameters,
+ * coef = min(1, max_norm / (total + 1e-6)), every gradient multiplied by coef -- and a skipped step as a step on which
+ * torch.optim.Adam.step() is not called: parameters, moments and the per-parameter step counts stay as they are.
+ *
+ * Slot table: long[nslots][2] = (offset, length) in floats, offsets ascending, slots disjoint (TrainStep: one slot per
+ * parameter, the length padded to a multiple of 4).  What lies between the end of a slot and the next offset is padding.
+ * mask: int[nslots], non-zero = trainable.  Elements of masked-out slots and of the padding are neither read nor written.
+ * slots, mask, slot_steps, skip_count, workspace and status are DEVICE pointers; nothing is read back, allocated or
+ * synchronised, so every call is legal inside a hipGraph capture.
+ *
+ * Status block (C2S_GUARD_STATUS_BYTES, 8-byte aligned):
+ *     byte 0  double sumsq   sum of squares of the trainable elements            (c2s_grad_sumsq)
+ *     byte 8  int    ok      1: apply the step, 0: skip it                       (c2s_step_decide)
+ *     byte 12 float  scale   grad_scale * coef, the scale Adam applies           (c2s_step_decide)
+ *     byte 16 float  norm    grad_scale * sqrt(sumsq)                            (c2s_step_decide)
+ *     byte 20 float  coef    the clip coefficient                                (c2s_step_decide)
+ *
+ *   c2s_grad_sumsq: sumsq in double (the square of a finite float never overflows it), in a fixed order: a grid that depends on
+ *     `total` alone, one partial per workgroup (lane order, wave butterfly, LDS), the partials summed in index order by a second
+ *     launch -- bitwise reproducible.  An inf or NaN in a trainable element makes sumsq non-finite.  workspace: see the query.
+ *   c2s_step_decide: one launch.  ok = !skip_nonfinite || isfinite(sumsq); norm and coef in double, rounded once to float;
+ *     max_grad_norm <= 0: no clipping (coef = 1).  ok: slot_steps[s] += 1 for every trainable slot; otherwise skip_count[0] += 1.
+ *   c2s_adam_slots: c2s_adam_flat (train.py:454) over every trainable slot in ONE launch instead of one per run of slots:
+ *     the step count is the slot's own slot_steps[s] (>= 1), the gradient scale is status.scale; returns at once when
+ *     status.ok == 0.  Per element the arithmetic is adam_kernel's (one shared device function).
+ *   c2s_restore_if_skipped: dst[i] = status.ok ? dst[i] : saved[i] (the model's floating-point buffers, copied aside before
+ *     the forward pass).
+ * ------------------------------------------------------------------------------------------------ */
+#define C2S_GUARD_STATUS_BYTES 32
+size_t c2s_grad_sumsq_workspace_doubles(void);
+int c2s_grad_sumsq(const float* g, const long* slots, const int* mask, int nslots, long total, double* workspace,
+                   size_t ws_doubles, void* status, void* stream);
+int c2s_step_decide(void* status, float max_grad_norm, float grad_scale, int skip_nonfinite, const int* mask,
+                    int* slot_steps, int nslots, int* skip_count, void* stream);
+int c2s_adam_slots(float* p, const float* g, float* m, float* v, const long* slots, const int* mask,
+                   const int* slot_steps, int nslots, long total, float lr, float b1, float b2, float eps,
+                   const void* status, void* stream);
+int c2s_restore_if_skipped(float* dst, const float* saved, long n, const void* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Metrics tail of iterate() (src/learning/utils.py:332-336,377-380; src/learning/miou.py:55-117).
  *   c2s_metrics_update: one pass over logits [B,K,HW] and target int64 [B,HW]:
  *       pred      = argmax_k logits (first maximum, = torch.argmax)
