@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libc2s_hip.so")
-SOURCES = ["pack.hip", "conv_igemm.hip", "conv_bf16x3.hip", "conv_xpair.hip", "conv_first.hip", "conv_winograd.hip", "conv_winograd16.hip", "conv_s2wino.hip", "conv_s2dgrad.hip", "conv_wgrad.hip", "norm.hip", "se.hip", "ltae.hip", "ltae_long.hip", "ltae_pe.hip", "aggregate.hip", "misc.hip", "guard.hip", "metrics.hip", "io.hip"]
+SOURCES = ["pack.hip", "conv_igemm.hip", "conv_bf16x3.hip", "conv_xpair.hip", "conv_first.hip", "conv_winograd.hip", "conv_winograd16.hip", "conv_s2wino.hip", "conv_s2dgrad.hip", "conv_wgrad.hip", "norm.hip", "se.hip", "ltae.hip", "ltae_long.hip", "ltae_pe.hip", "aggregate.hip", "misc.hip", "guard.hip", "metrics.hip", "parcels.hip", "io.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value", "-D__HIP_PLATFORM_AMD__"]
 
@@ -32,6 +32,7 @@ def _stale(target: str, deps) -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     cc = hipcc()
     headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ltae_drop.h"), os.path.join(CSRC, "ltae_long.h"),
+               os.path.join(CSRC, "parcels_uf.h"),
                os.path.join(os.path.dirname(HERE), "include", "c2s_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:

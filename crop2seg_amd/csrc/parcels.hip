@@ -1,0 +1,339 @@
+// Parcel homogenisation of predictions (the raster restatement of src/helpers/postprocess.py:377-604).
+//
+// Reference call sites (paths under the reference root):
+//   src/helpers/postprocess.py:540-551  top-2 of the class probabilities; super = not (boundary | strong second boundary | class 0)
+//   src/helpers/postprocess.py:532-536,554-560  scipy.ndimage.label with the plus element; components under 13 pixels removed
+//   src/helpers/postprocess.py:449-456,580  per parcel: the class of the largest area; background only above a 0.75 share
+//   src/learning/utils.py:341-361,383   iterate(): the homogenised prediction feeds the IoU meter
+//
+// A parcel is a set of pixels with one integer id and an area is a pixel count, so everything after the seeds rule is
+// integer work: bit-exact and independent of scheduling.  All rasters are [B,H,W]; images are independent.  Every pass is
+// one thread per pixel over a few bytes per pixel (latency- and atomic-bound, not bandwidth-bound); entry points only
+// enqueue on the stream: no allocation, no read-back, no synchronisation.
+#include <limits.h>
+#include "common.h"
+#include "parcels_uf.h"
+
+namespace {
+
+constexpr int MAXK = 32;        // classes, as in metrics.hip
+constexpr int PC_SCAN = 256;    // pixels one workgroup of the numbering scan covers (one per lane)
+constexpr long PC_MAX_PIXELS = INT_MAX - 4096L * 256;       // a grid-stride step past the last pixel still fits an int
+
+inline int grid_for(long n, int cap = 4096) {
+    long b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// base[key] += number of active lanes of the wave that hold `key`: one atomic per distinct key and wave.  Called by whole
+// waves (the callers' loops have wave-uniform trip counts).
+__device__ __forceinline__ void wave_count_add(int* __restrict__ base, int key, bool on) {
+    unsigned long long todo = __ballot(on);
+    const int lane = threadIdx.x & 63;
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int k0 = __shfl(key, leader, 64);
+        const unsigned long long same = __ballot(on && key == k0);
+        if (lane == leader) atomicAdd(base + k0, (int)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+// inclusive prefix sum of v over the 256 lanes of the workgroup; total = the sum.  sw: 4 ints of LDS.
+__device__ __forceinline__ int block_scan_incl(int v, int* sw, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    __syncthreads();                            // the previous use of sw is over
+    if (lane == 63) sw[w] = x;
+    __syncthreads();
+    int off = 0;
+    for (int j = 0; j < w; ++j) off += sw[j];
+    total = sw[0] + sw[1] + sw[2] + sw[3];
+    return x + off;
+}
+
+// ---------------------------------------------------------------- (a) seeds (postprocess.py:540-551)
+// top-1 / top-2 as metrics_update_kernel finds them: first maximum, lowest index on ties.  With from_logits the softmax
+// runs here (max-subtracted, fp32, as softmax_stitch_kernel).
+__global__ __launch_bounds__(256) void parcel_seeds_kernel(const float* __restrict__ scores, const float* __restrict__ bscores,
+                                                           unsigned char* __restrict__ mask, int64_t* __restrict__ t1_out,
+                                                           int B, int K, int HW, int from_logits, int boundary_code,
+                                                           float thr) {
+    const long total = (long)B * HW;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int pix = (int)(e % HW), b = (int)(e / HW);
+        const float* sp = scores + (size_t)b * K * HW + pix;
+        float v1 = sp[0], v2 = -INFINITY;
+        int i1 = 0, i2 = -1;
+        for (int k = 1; k < K; ++k) {
+            const float v = sp[(size_t)k * HW];
+            if (v > v1 || (v != v && v1 == v1)) {
+                v2 = v1; i2 = i1; v1 = v; i1 = k;
+            } else if (i2 < 0 || v > v2 || (v != v && v2 == v2)) {
+                v2 = v; i2 = k;
+            }
+        }
+        float p2 = v2;
+        if (from_logits) {
+            float s = 0.f;
+            for (int k = 0; k < K; ++k) s += expf(sp[(size_t)k * HW] - v1);
+            p2 = expf(v2 - v1) / s;
+        }
+        bool boundary;
+        if (bscores) {                                      // the separate 2-class head
+            const float* bp = bscores + (size_t)b * 2 * HW + pix;
+            float p0 = bp[0], p1 = bp[HW];
+            if (from_logits) {
+                const float m = fmaxf(p0, p1);
+                const float e0 = expf(p0 - m), e1 = expf(p1 - m);
+                p0 = e0 / (e0 + e1);
+                p1 = e1 / (e0 + e1);
+            }
+            boundary = p1 >= p0 || p1 > thr;
+        } else {
+            boundary = i1 == boundary_code || (i2 == boundary_code && p2 > thr);
+        }
+        mask[e] = (boundary || i1 == 0) ? 0 : 1;
+        if (t1_out) t1_out[e] = i1;
+    }
+}
+
+// ---------------------------------------------------------------- (b) connected components, 4-connectivity
+__global__ __launch_bounds__(256) void cc_init_kernel(int* __restrict__ parent, int* __restrict__ size, int n) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) { parent[i] = i; size[i] = 0; }
+}
+
+__global__ __launch_bounds__(256) void cc_unite_kernel(int* __restrict__ parent, const unsigned char* __restrict__ mask, int n,
+                                                       int H, int W, int* __restrict__ error) {
+    const int cap = H * W;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
+        if (mask[i] && !puf_unite_pixel(parent, mask, i, H, W, cap)) atomicOr(error, 1);
+}
+
+// parent[i] = the root; size[root] = pixels of the component
+__global__ __launch_bounds__(256) void cc_flatten_kernel(int* __restrict__ parent, int* __restrict__ size,
+                                                         const unsigned char* __restrict__ mask, int n, int H, int W,
+                                                         int* __restrict__ error) {
+    const int cap = H * W;
+    for (int base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {      // wave-uniform: wave_count_add
+        const int i = base + threadIdx.x;
+        const bool on = i < n && mask[i];
+        int r = 0;
+        if (on) {
+            r = puf_find(parent, i, cap);
+            if (r < 0) { atomicOr(error, 1); r = i; }
+            parent[i] = r;
+        }
+        wave_count_add(size, r, on);
+    }
+}
+
+__device__ __forceinline__ bool cc_survivor(const int* __restrict__ parent, const int* __restrict__ size,
+                                            const unsigned char* __restrict__ mask, int i, int min_size) {
+    return mask[i] && parent[i] == i && size[i] >= min_size;
+}
+
+// grid (blocks per image, B): sums[b][block] = surviving roots among the block's PC_SCAN pixels
+__global__ __launch_bounds__(PC_SCAN) void cc_count_kernel(const int* __restrict__ parent, const int* __restrict__ size,
+                                                           const unsigned char* __restrict__ mask, int HW, int min_size,
+                                                           int* __restrict__ sums) {
+    __shared__ int sw[4];
+    const int p = blockIdx.x * PC_SCAN + threadIdx.x;
+    const int i = blockIdx.y * HW + p;
+    int total;
+    block_scan_incl(p < HW && cc_survivor(parent, size, mask, i, min_size) ? 1 : 0, sw, total);
+    if (threadIdx.x == 0) sums[blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// one workgroup per image: sums[b][*] -> their exclusive prefix sums, count[b] = the image's components
+__global__ __launch_bounds__(256) void cc_scan_sums_kernel(int* __restrict__ sums, int nblk, int* __restrict__ count) {
+    __shared__ int sw[4];
+    int* s = sums + (size_t)blockIdx.x * nblk;
+    int carry = 0;
+    for (int base = 0; base < nblk; base += 256) {
+        const int j = base + threadIdx.x;
+        const int v = j < nblk ? s[j] : 0;
+        int total;
+        const int incl = block_scan_incl(v, sw, total);
+        if (j < nblk) s[j] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) count[blockIdx.x] = carry;
+}
+
+// size[root] = the dense id of a surviving root (1..n in raster order of the roots = of the components' first pixels), 0
+// for a removed one
+__global__ __launch_bounds__(PC_SCAN) void cc_number_kernel(const int* __restrict__ parent, int* __restrict__ size,
+                                                            const unsigned char* __restrict__ mask, int HW, int min_size,
+                                                            const int* __restrict__ sums) {
+    __shared__ int sw[4];
+    const int p = blockIdx.x * PC_SCAN + threadIdx.x;
+    const int i = blockIdx.y * HW + p;
+    const bool in = p < HW;
+    const bool root = in && mask[i] && parent[i] == i;
+    const bool on = root && size[i] >= min_size;
+    int total;
+    const int incl = block_scan_incl(on ? 1 : 0, sw, total);
+    if (root) size[i] = on ? sums[blockIdx.y * gridDim.x + blockIdx.x] + incl : 0;
+}
+
+__global__ __launch_bounds__(256) void cc_write_kernel(const int* __restrict__ parent, const int* __restrict__ ids,
+                                                       const unsigned char* __restrict__ mask, int* __restrict__ labels, int n) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) labels[i] = mask[i] ? ids[parent[i]] : 0;
+}
+
+// ---------------------------------------------------------------- (c) the vote (postprocess.py:449-456,580)
+__global__ __launch_bounds__(256) void vote_zero_kernel(int* __restrict__ hist, int n) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) hist[i] = 0;
+}
+
+// hist[b][label-1][pred] += 1; error[0] += labels outside [0, cap], error[1] += classes outside [0, K)
+__global__ __launch_bounds__(256) void vote_hist_kernel(const int64_t* __restrict__ pred, const int* __restrict__ labels,
+                                                        int* __restrict__ hist, int n, int HW, int K, int cap,
+                                                        int* __restrict__ error) {
+    for (int base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {      // wave-uniform: wave_count_add
+        const int i = base + threadIdx.x;
+        bool on = false, bad_label = false, bad_class = false;
+        int key = 0;
+        if (i < n) {
+            const int l = labels[i];
+            const long long c = pred[i];
+            bad_label = l < 0 || l > cap;
+            bad_class = c < 0 || c >= K;
+            on = l > 0 && !bad_label && !bad_class;
+            if (on) key = ((i / HW) * cap + (l - 1)) * K + (int)c;
+        }
+        wave_count_add(hist, key, on);
+        wave_count_add(error, 0, bad_label);
+        wave_count_add(error, 1, bad_class);
+    }
+}
+
+// one thread per parcel: the candidate class of the largest count, lower class on ties, 0 without a candidate
+__global__ __launch_bounds__(256) void vote_winner_kernel(const int* __restrict__ hist, int* __restrict__ parcel_class,
+                                                          int nparcels, int K, float bg_share) {
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < nparcels; p += gridDim.x * 256) {
+        const int* h = hist + (size_t)p * K;
+        long total = 0;
+        for (int k = 0; k < K; ++k) total += h[k];
+        int best = 0, win = 0;
+        if (bg_share >= 0.f && h[0] > 0 && (double)h[0] > (double)bg_share * (double)total) best = h[0];
+        for (int k = 1; k < K; ++k)
+            if (h[k] > best) { best = h[k]; win = k; }
+        parcel_class[p] = win;
+    }
+}
+
+__global__ __launch_bounds__(256) void vote_write_kernel(const int64_t* __restrict__ pred, const int* __restrict__ labels,
+                                                         const int* __restrict__ parcel_class, int64_t* __restrict__ out, int n,
+                                                         int HW, int K, int cap, int outside) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int l = labels[i];
+        const long long c = pred[i];
+        if (l < 0 || l > cap || c < 0 || c >= K) continue;             // counted by vote_hist_kernel: nothing is written
+        out[i] = l > 0 ? (long long)parcel_class[(i / HW) * cap + (l - 1)] : (outside ? c : 0);
+    }
+}
+
+inline long cc_pixels(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    const long n = (long)B * H * W;
+    return n <= PC_MAX_PIXELS && B <= 65535 ? n : 0;        // int indices; grid.y = B
+}
+
+}  // namespace
+
+extern "C" int c2s_parcel_seeds(const float* scores, const float* boundary_scores, unsigned char* mask, long long* t1, int B,
+                                int K, int H, int W, int from_logits, int boundary_code, float second_threshold,
+                                void* stream) {
+    C2S_REQUIRE(scores && mask, "parcel_seeds: null pointer");
+    C2S_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W <= INT_MAX, "parcel_seeds: bad shape");
+    C2S_REQUIRE(K >= 2 && K <= MAXK, "parcel_seeds: 2 <= K <= 32 classes");
+    C2S_REQUIRE(from_logits == 0 || from_logits == 1, "parcel_seeds: from_logits is 0 or 1");
+    C2S_REQUIRE(!(second_threshold != second_threshold), "parcel_seeds: second_threshold is NaN");
+    hipLaunchKernelGGL(parcel_seeds_kernel, dim3(grid_for((long)B * H * W)), dim3(256), 0, (hipStream_t)stream, scores,
+                       boundary_scores, mask, (int64_t*)t1, B, K, H * W, from_logits, boundary_code, second_threshold);
+    C2S_CHECK_LAUNCH("parcel_seeds");
+    return C2S_OK;
+}
+
+// parent int[n] | size / id int[n] | block sums int[B * blocks per image]
+extern "C" size_t c2s_label_components_workspace_bytes(int B, int H, int W) {
+    const long n = cc_pixels(B, H, W);
+    if (n == 0) return 0;
+    const long nblk = ((long)H * W + PC_SCAN - 1) / PC_SCAN;
+    return (size_t)(2 * n + B * nblk) * sizeof(int);
+}
+
+extern "C" int c2s_label_components(const unsigned char* mask, int* labels, int* count, int B, int H, int W, int min_size,
+                                    void* workspace, size_t ws_bytes, int* error, void* stream) {
+    C2S_REQUIRE(mask && labels && count && workspace && error, "label_components: null pointer");
+    const long nl = cc_pixels(B, H, W);
+    C2S_REQUIRE(nl > 0, "label_components: bad shape (B * H * W <= %ld, B <= 65535)", PC_MAX_PIXELS);
+    C2S_REQUIRE(min_size >= 1, "label_components: min_size %d < 1", min_size);
+    C2S_REQUIRE((uintptr_t)workspace % 16 == 0, "label_components: workspace not 16-byte aligned");
+    const size_t need = c2s_label_components_workspace_bytes(B, H, W);
+    C2S_REQUIRE(ws_bytes >= need, "label_components: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    const int n = (int)nl, HW = H * W, nblk = (HW + PC_SCAN - 1) / PC_SCAN;
+    int* parent = (int*)workspace;
+    int* size = parent + n;
+    int* sums = size + n;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g(grid_for(n)), t(256), gs(nblk, B);
+    hipLaunchKernelGGL(cc_init_kernel, g, t, 0, st, parent, size, n);
+    C2S_CHECK_LAUNCH("cc_init");
+    hipLaunchKernelGGL(cc_unite_kernel, g, t, 0, st, parent, mask, n, H, W, error);
+    C2S_CHECK_LAUNCH("cc_unite");
+    hipLaunchKernelGGL(cc_flatten_kernel, g, t, 0, st, parent, size, mask, n, H, W, error);
+    C2S_CHECK_LAUNCH("cc_flatten");
+    hipLaunchKernelGGL(cc_count_kernel, gs, dim3(PC_SCAN), 0, st, parent, size, mask, HW, min_size, sums);
+    C2S_CHECK_LAUNCH("cc_count");
+    hipLaunchKernelGGL(cc_scan_sums_kernel, dim3(B), t, 0, st, sums, nblk, count);
+    C2S_CHECK_LAUNCH("cc_scan_sums");
+    hipLaunchKernelGGL(cc_number_kernel, gs, dim3(PC_SCAN), 0, st, parent, size, mask, HW, min_size, sums);
+    C2S_CHECK_LAUNCH("cc_number");
+    hipLaunchKernelGGL(cc_write_kernel, g, t, 0, st, parent, size, mask, labels, n);
+    C2S_CHECK_LAUNCH("cc_write");
+    return C2S_OK;
+}
+
+// the histogram int[B][cap][K]
+extern "C" size_t c2s_parcel_vote_workspace_bytes(int B, int cap, int K) {
+    if (B <= 0 || cap <= 0 || K <= 0) return 0;
+    const long n = (long)B * cap * K;
+    return n <= INT_MAX ? (size_t)n * sizeof(int) : 0;
+}
+
+extern "C" int c2s_parcel_vote(const long long* pred, const int* labels, long long* out, int* parcel_class, int B, int H, int W,
+                               int K, int cap, float bg_share, int outside, void* workspace, size_t ws_bytes, int* error,
+                               void* stream) {
+    C2S_REQUIRE(pred && labels && out && parcel_class && workspace && error, "parcel_vote: null pointer");
+    C2S_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W <= PC_MAX_PIXELS, "parcel_vote: bad shape (B * H * W <= %ld)", PC_MAX_PIXELS);
+    C2S_REQUIRE(K >= 2 && K <= MAXK, "parcel_vote: 2 <= K <= 32 classes");
+    C2S_REQUIRE(cap >= 1, "parcel_vote: cap %d < 1", cap);
+    C2S_REQUIRE(outside == 0 || outside == 1, "parcel_vote: outside is 0 (zero) or 1 (keep)");
+    C2S_REQUIRE(!(bg_share != bg_share), "parcel_vote: bg_share is NaN");
+    const size_t need = c2s_parcel_vote_workspace_bytes(B, cap, K);
+    C2S_REQUIRE(need > 0, "parcel_vote: B * cap * K = %ld entries are more than int indices reach", (long)B * cap * K);
+    C2S_REQUIRE((uintptr_t)workspace % 16 == 0, "parcel_vote: workspace not 16-byte aligned");
+    C2S_REQUIRE(ws_bytes >= need, "parcel_vote: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    const int n = B * H * W, HW = H * W, nh = B * cap * K;
+    int* hist = (int*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g(grid_for(n)), t(256);
+    hipLaunchKernelGGL(vote_zero_kernel, dim3(grid_for(nh)), t, 0, st, hist, nh);
+    C2S_CHECK_LAUNCH("vote_zero");
+    hipLaunchKernelGGL(vote_hist_kernel, g, t, 0, st, (const int64_t*)pred, labels, hist, n, HW, K, cap, error);
+    C2S_CHECK_LAUNCH("vote_hist");
+    hipLaunchKernelGGL(vote_winner_kernel, dim3(grid_for((long)B * cap)), t, 0, st, hist, parcel_class, B * cap, K, bg_share);
+    C2S_CHECK_LAUNCH("vote_winner");
+    hipLaunchKernelGGL(vote_write_kernel, g, t, 0, st, (const int64_t*)pred, labels, parcel_class, (int64_t*)out, n, HW, K, cap,
+                       outside);
+    C2S_CHECK_LAUNCH("vote_write");
+    return C2S_OK;
+}

@@ -23,11 +23,18 @@ Tensor = torch.Tensor
 
 
 @torch.no_grad()
-def predict_tile(model, x: Tensor, dates: Tensor, grid: int = 10, crop: int = 1098, batch_size: int = 10) -> Tuple[Tensor, Tensor]:
+def predict_tile(model, x: Tensor, dates: Tensor, grid: int = 10, crop: int = 1098, batch_size: int = 10,
+                 parcels: Optional[Tensor] = None, boundary_homogenize: bool = False, boundary_code: int = 15):
     """x [grid*grid, T, C, h1, w1] (patches in row-major tile order, as the reference's test loader yields them), dates
-    [grid*grid, T] -> (proba [K, crop, crop] f32, top1 [crop, crop] int64) on the device."""
+    [grid*grid, T] -> (proba [K, crop, crop] f32, top1 [crop, crop] int64) on the device.
+    With `parcels` ([crop, crop] parcel ids of the tile, 0 = no parcel) or `boundary_homogenize` a third element follows: the
+    tile raster homogenised per parcel ([crop, crop] int64), as the web app does (crop2seg.py:335-371): by the given
+    parcels (postprocess.homogenize), or by the parcels that the boundary class `boundary_code` of the stitched
+    probabilities outlines (postprocess.homogenize_boundaries)."""
     if not x.is_cuda:
         raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
+    if parcels is not None and boundary_homogenize:
+        raise ValueError("predict_tile: give `parcels` or `boundary_homogenize`, not both")
     n = x.shape[0]
     assert n == grid * grid and dates.shape[0] == n
     h1, w1 = x.shape[-2:]
@@ -52,4 +59,10 @@ def predict_tile(model, x: Tensor, dates: Tensor, grid: int = 10, crop: int = 10
     finally:
         model.train(was_training)
     model.check_health()                 # one host synchronisation per tile: a failed normalisation wait must not reach a map
+    if parcels is not None:
+        from .postprocess import homogenize
+        return proba, top1, homogenize(top1, parcels, proba.shape[0])
+    if boundary_homogenize:
+        from .postprocess import homogenize_boundaries
+        return proba, top1, homogenize_boundaries(proba, boundary_code=boundary_code, from_logits=False)
     return proba, top1

@@ -198,20 +198,32 @@ class StepMeters:
     def get_miou_acc_boundary(self) -> Tuple[float, float]:
         return self.iou_boundary.get_miou_acc()
 
-    def update(self, out: Tensor, y: Tensor, loss: Optional[Tensor] = None, want_pred: bool = False):
+    def update(self, out: Tensor, y: Tensor, loss: Optional[Tensor] = None, want_pred: bool = False,
+               parcels: Optional[Tensor] = None):
         """out [B,K,H,W] f32 logits, y [B,H,W] int64, loss: 1-element device tensor.  Returns (pred, pred_top2) int64
-        [B,H,W] when want_pred, else None."""
+        [B,H,W] when want_pred, else None.
+        parcels [B,H,W] (a rasterised parcel id map, 0 = no parcel): the top-1 prediction is homogenised per parcel before
+        the IoU meter sees it, as iterate() does under --get_affine (utils.py:341-361,383; postprocess.homogenize); the top-2
+        and the loss meter are fed as without it, and `pred` is then the homogenised prediction."""
         _require_hip(out, "out")
         B, K = out.shape[:2]
         assert K == self.num_classes and out.dtype == torch.float32
         out = out.contiguous()
         y = self.region_target(y.to(torch.int64).contiguous())
         HW = out[0, 0].numel()
+        if parcels is not None:
+            want_pred = True
         pred = torch.empty_like(y) if want_pred else None
         pred2 = torch.empty_like(y) if want_pred else None
-        check(lib().c2s_metrics_update(out.data_ptr(), y.data_ptr(), self.iou.conf_metric.conf.data_ptr(),
+        conf = self.iou.conf_metric.conf if parcels is None else torch.zeros_like(self.iou.conf_metric.conf)
+        check(lib().c2s_metrics_update(out.data_ptr(), y.data_ptr(), conf.data_ptr(),
                                        self.iou_top2.conf_metric.conf.data_ptr(), pred.data_ptr() if want_pred else None,
                                        pred2.data_ptr() if want_pred else None, B, K, HW, _stream()), "metrics_update")
+        if parcels is not None:
+            from ..postprocess import homogenize
+            pred = homogenize(pred, parcels, K)
+            check(lib().c2s_confusion_add(pred.data_ptr(), y.data_ptr(), self.iou.conf_metric.conf.data_ptr(), y.numel(), K,
+                                          _stream()), "confusion_add")
         if loss is not None:
             _require_hip(loss, "loss")
             lf = loss.detach().to(torch.float32).reshape(-1)

@@ -627,6 +627,58 @@ int c2s_smooth_ce_ex(const float* logits, const long long* target, const float* 
                      int reduction, int accumulate_loss, float* workspace, size_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Parcel homogenisation of predictions: the raster restatement of src/helpers/postprocess.py:377-604 (homogenize,
+ * homogenize_boundaries), called by iterate() under --get_affine (src/learning/utils.py:341-361,383) and by the web app
+ * (crop2seg.py:335-371).  A parcel is a set of pixels with one integer id, an area is a pixel count; the vector side
+ * (shapefiles, CRS, polygonisation) stays with the caller.  All rasters are [B,H,W] and the images of a
+ * batch are independent: nothing connects the last column of a row to the first of the next, nor image b to image b + 1.
+ * Every entry point only enqueues on the stream: no allocation, no read-back, no synchronisation.  Integer work throughout:
+ * results are bit-exact and do not depend on scheduling.  B * H * W <= 2^31 - 1 - 2^20.
+ *
+ *   c2s_parcel_seeds: the `super` mask of postprocess.py:540-551.  scores [B,K,H,W] f32 (2 <= K <= 32): probabilities, or
+ *     logits with from_logits = 1 (the softmax over K then runs inside, fp32).  Per pixel t1 / t2 = the top-1 / top-2 class
+ *     (ties to the lower class index, as c2s_metrics_update) and p2 = the top-2 probability:
+ *         seed = !(t1 == boundary_code || (t2 == boundary_code && p2 > second_threshold) || t1 == 0)
+ *     boundary_scores [B,2,H,W] non-NULL (this project's separate 2-class boundary head; logits under from_logits = 1): the
+ *     pixel is boundary when its class-1 probability is >= its class-0 probability or > second_threshold, and
+ *         seed = !(boundary || t1 == 0)                                       (boundary_code is ignored)
+ *     mask u8 [B,H,W] receives 0 / 1; t1 int64 [B,H,W] (may be NULL) the top-1 class.
+ *   c2s_label_components: scipy.ndimage.label with the plus-shaped element (postprocess.py:532-536,554: 4-connectivity) on
+ *     a u8 mask (non-zero = set), then the removal of components under min_size pixels (>= 1; :556-560 uses 13; EVERY
+ *     component is tested, the reference's range(ncomp) misses the last).  labels int32 [B,H,W]: 0 off the mask and in
+ *     removed components, survivors numbered 1..count[b] per image in raster order of their first pixel -- with
+ *     min_size = 1 exactly scipy's numbering.  count int32 [B].  Union-find over the pixels: every pixel is united with its
+ *     left and upper neighbour (find by following parents, the larger root linked under the smaller with atomicMin), so
+ *     the root of a component is its smallest pixel index; one pass flattens and counts sizes, a scan over "surviving root"
+ *     numbers them.  Every loop that follows parents or retries a link is capped at H * W steps (a parent never exceeds its
+ *     pixel's index, so the cap is reached only on damaged memory): a hit sets error[0] |= 1 and the loop ends.
+ *     workspace: 16-byte aligned, see the query (0 for a shape the call refuses).
+ *   c2s_parcel_vote: the per-parcel vote of postprocess.py:449-456 / :580 by pixel count.  pred int64 [B,H,W], labels int32
+ *     [B,H,W] (0 = no parcel, ids 1..cap), 2 <= K <= 32:
+ *         hist[b][label-1][pred] += 1;
+ *         per parcel: class k > 0 is a candidate when its count is > 0; class 0 only when bg_share >= 0 and
+ *         (double)count0 > (double)bg_share * (double)total (strict, the `> 0.75` of :453-454; bg_share < 0 restates the
+ *         boundary variant's raster_val > 0); the largest count wins, ties go to the lower class, no candidate gives 0;
+ *         out[b,y,x] = winner[label]; where the label is 0: 0 (rasterize(fill=0)) with outside = 0, pred with outside = 1.
+ *     parcel_class int32 [B,cap] receives the winners (0 for ids no pixel carries); the histogram int32 [B,cap,K] is the
+ *     workspace (16-byte aligned, see the query) and stays readable.  out may be pred itself.  Pixels whose label lies
+ *     outside [0,cap] or whose class lies outside [0,K) take no part and out is not written there; error[0] += the
+ *     former, error[1] += the latter (device ints, never reset by the call).  For labels that come from
+ *     c2s_label_components, cap = H * W / min_size + 1 always suffices.
+ *   Deviations from the reference (it cannot be run where geopandas / rasterio are missing; stated, not measured): :580
+ *   takes the class of the largest single same-class patch inside a component, here the largest per-class pixel count wins
+ *   (homogenize's own aggregation, :449); ties are unordered there, the lower class wins here.
+ * ------------------------------------------------------------------------------------------------ */
+int c2s_parcel_seeds(const float* scores, const float* boundary_scores, unsigned char* mask, long long* t1, int B, int K,
+                     int H, int W, int from_logits, int boundary_code, float second_threshold, void* stream);
+size_t c2s_label_components_workspace_bytes(int B, int H, int W);
+int c2s_label_components(const unsigned char* mask, int* labels, int* count, int B, int H, int W, int min_size,
+                         void* workspace, size_t ws_bytes, int* error, void* stream);
+size_t c2s_parcel_vote_workspace_bytes(int B, int cap, int K);
+int c2s_parcel_vote(const long long* pred, const int* labels, long long* out, int* parcel_class, int B, int H, int W, int K,
+                    int cap, float bg_share, int outside, void* workspace, size_t ws_bytes, int* error, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Batch movers on either side of the path.
  *   c2s_collate_series: dataset tail + pad_collate in one pass (s2_ts_cz_crop.py:366-374,393-398; src/utils.py:14-32;
  *     train.py:291).  src = the B series of a batch back to back, [sum_b T_b][Cs][HW] in the storage type of the .npy
