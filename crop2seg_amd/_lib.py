@@ -64,6 +64,7 @@ SIGNATURES = {
     "c2s_pack_job_blocks": (I, [I, I, I, I]),
     "c2s_pack_batch": (I, [P, I, I, P]),
     "c2s_conv_igemm": (I, [C.POINTER(ConvDesc), P, P, P, P, P, P, P]),
+    "c2s_conv_igemm_split": (I, [C.POINTER(ConvDesc), I]),
     "c2s_conv_xpair": (I, [C.POINTER(ConvDesc), P, P, P, P, P, P]),
     "c2s_conv3x3_smallcin_supported": (I, [C.POINTER(ConvDesc)]),
     "c2s_conv3x3_smallcin": (I, [C.POINTER(ConvDesc), P, P, P, P, P, P]),

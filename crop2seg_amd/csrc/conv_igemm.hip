@@ -11,6 +11,17 @@
 // the gather offsets of a thread's staging elements are computed once per tile (reflection included)
 // and kept in registers, so the per-chunk staging is load + ds_write only.
 //
+//
+// Split tiles (SP = 2, 4; MF = 1) for launches too small to fill the GPU (the decoder and head run on N = batch frames:
+// a 32-channel 3x3 layer at 64x64, N = 4 is 64 workgroups on 256 CUs, each wave walking the whole K loop with two MFMAs
+// per k-step).  SP = 2: the tile is 4 position fragments, a wave owns ONE; SP = 4: 2 fragments, a workgroup of 2 waves.
+// The grid grows SP-fold and a wave issues half the MFMAs; its operand reads run two k-steps ahead, since one MFMA no
+// longer covers an LDS round trip.  Every output element is still the same chain of MFMAs over the same k-steps in the
+// same order, so the result is BIT-IDENTICAL to the unsplit tile's: the choice may depend on the frame count without
+// making a sample's result depend on its batch (tests pin that bit for bit).  (Splitting the K loop over the waves of a
+// tile, the first form of this, was faster again on the smallest launches but rounds differently at every split, which
+// breaks exactly that: DESIGN 8.)  c2s_conv_igemm_split is the rule that picks SP.
+//
 // Reference call sites replaced: nn.Conv2d / nn.ConvTranspose2d in src/backbones/conv.py:70-80,
 // 263-271,378-390 and their convolution_backward-input.
 #include "common.h"
@@ -36,30 +47,36 @@ struct ConvParams {
 };
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
-constexpr int plane_for(int K, int S, int log2fc) {
-    return ((8 * (32 >> log2fc) - 1) * S + K) * (((1 << log2fc) - 1) * S + K);
+constexpr int plane_for(int K, int S, int log2fc, int NF) {      // NF = position fragments of the tile (8 / SP)
+    return ((NF * (32 >> log2fc) - 1) * S + K) * (((1 << log2fc) - 1) * S + K);
 }
-constexpr int max_plane(int K, int S) {
-    return cmax(cmax(plane_for(K, S, 2), plane_for(K, S, 3)), cmax(plane_for(K, S, 4), plane_for(K, S, 5)));
+constexpr int max_plane(int K, int S, int NF) {
+    return cmax(cmax(plane_for(K, S, 2, NF), plane_for(K, S, 3, NF)), cmax(plane_for(K, S, 4, NF), plane_for(K, S, 5, NF)));
 }
 
-template <int K, int S>
+template <int K, int S, int SP = 1>
 struct Cfg {
     // channels per LDS chunk: enough MFMA k-steps per barrier pair (>= 16) without growing the prefetch registers
     static constexpr int CK = K == 1 ? 16 : (K == 2 ? 8 : (K >= 4 ? 2 : 4));
     static constexpr int NT = K * K;
-    static constexpr int MAXE = (CK * max_plane(K, S) + 255) / 256;
+    static constexpr int NTHR = SP == 4 ? 128 : 256;             // threads of a workgroup
+    static constexpr int MAXE = (CK * max_plane(K, S, 8 / SP) + NTHR - 1) / NTHR;
 };
 
-template <int K, int S, int MF, bool ADJ>
-__global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
-    constexpr int CK = Cfg<K, S>::CK;
-    constexpr int NT = Cfg<K, S>::NT;
-    constexpr int MAXE = Cfg<K, S>::MAXE;
+template <int K, int S, int MF, bool ADJ, int SP = 1>
+__global__ __launch_bounds__((Cfg<K, S, SP>::NTHR)) void conv_igemm_kernel(ConvParams p) {
+    static_assert(SP == 1 || ((SP == 2 || SP == 4) && MF == 1), "the split tiles exist for 32-channel tiles");
+    constexpr int CK = Cfg<K, S, SP>::CK;
+    constexpr int NT = Cfg<K, S, SP>::NT;
+    constexpr int MAXE = Cfg<K, S, SP>::MAXE;
+    constexpr int NTHR = Cfg<K, S, SP>::NTHR;
+    constexpr int NF = 8 / SP;                   // position fragments of the tile
+    constexpr int NQ = SP == 1 ? 2 : 1;          // fragments (accumulators per channel fragment) of a wave
+    constexpr int LA = SP == 1 ? 1 : 2;          // k-steps the operand reads run ahead of the MFMAs
     constexpr int COT = 32 * MF;
     constexpr int WV = COT / 4;                  // float4 per (tap, channel) weight row
     constexpr int NWV = NT * CK * WV;            // float4 items of the weight slab
-    constexpr int WPT = (NWV + 255) / 256;
+    constexpr int WPT = (NWV + NTHR - 1) / NTHR;
     constexpr int NS = NT * (CK / 2);            // MFMA k-steps per chunk
     extern __shared__ float lds[];
 
@@ -78,7 +95,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     if (p.valid != nullptr && p.valid[n] == 0) return;
 
     const int FC = 1 << p.log2fc, FR = 32 >> p.log2fc;
-    const int tile_h = 8 * FR, tile_w = FC;
+    const int tile_h = NF * FR, tile_w = FC;
     const int rows = (tile_h - 1) * S + K, cols = (tile_w - 1) * S + K;
     const int plane = rows * cols;
     float* Xl = lds;                 // [2][ [CK][plane] | [NT][CK][COT] ]
@@ -99,7 +116,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     const int total = CK * plane;
 #pragma unroll
     for (int i = 0; i < MAXE; ++i) {
-        const int e = tid + i * 256;
+        const int e = tid + i * NTHR;
         int off = -1;
         if (e < total) {
             const int c = e / plane;
@@ -124,20 +141,20 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lk = lane >> 5;
     const int fy = li >> p.log2fc, fx = li & (FC - 1);
-    int boff[2];
+    int boff[NQ];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int f = 2 * wave + q;
+    for (int q = 0; q < NQ; ++q) {
+        const int f = NQ * wave + q;
         boff[q] = lk * plane + ((f * FR + fy) * S) * cols + fx * S;
     }
     const int aoff = lk * COT + li;
 
     // reflect adjoint: per-lane masks of the border positions this lane owns
-    float mxlo[2] = {0.f, 0.f}, mxhi[2] = {0.f, 0.f}, mylo[2] = {0.f, 0.f}, myhi[2] = {0.f, 0.f};
+    float mxlo[NQ] = {}, mxhi[NQ] = {}, mylo[NQ] = {}, myhi[NQ] = {};
     if constexpr (ADJ) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int f = 2 * wave + q;
+        for (int q = 0; q < NQ; ++q) {
+            const int f = NQ * wave + q;
             const int oy = oy0 + f * FR + fy, ox = ox0 + fx;
             mxlo[q] = ox == p.ax_lo ? 1.f : 0.f;
             mxhi[q] = ox == p.ax_hi ? 1.f : 0.f;
@@ -146,11 +163,11 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
         }
     }
 
-    f32x16 acc[MF][2];
+    f32x16 acc[MF][NQ];
 #pragma unroll
     for (int m = 0; m < MF; ++m)
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
+        for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][q][r] = 0.f;
 
@@ -180,7 +197,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
         }
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
-            const int e = tid + i * 256;
+            const int e = tid + i * NTHR;
             const int o4 = e % WV, tc = e / WV;
             const int c = tc % CK, t = tc / CK;
             const bool ok = e < NWV && cb + c < Cin;
@@ -193,24 +210,24 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
         float* Wd = Wl + buf * BUF;
 #pragma unroll
         for (int i = 0; i < MAXE; ++i) {
-            const int e = tid + i * 256;
+            const int e = tid + i * NTHR;
             if (e < total) Xd[e] = xr[i];
         }
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
-            const int e = tid + i * 256;
+            const int e = tid + i * NTHR;
             if (e < NWV) *reinterpret_cast<f32x4*>(Wd + (size_t)e * 4) = wr[i];
         }
     };
 
     // operands of k-step s = (tap t, channel pair cp)
-    auto load_ops = [&](const float* Xl, const float* Wl, int s_, float (&a)[MF], float (&b)[2]) {
+    auto load_ops = [&](const float* Xl, const float* Wl, int s_, float (&a)[MF], float (&b)[NQ]) {
         const int t = s_ / (CK / 2), cp = s_ % (CK / 2);
         const int ky = t / K, kx = t % K;
 #pragma unroll
         for (int m = 0; m < MF; ++m) a[m] = Wl[(t * CK + 2 * cp) * COT + aoff + m * 32];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < NQ; ++q) {
             const int ad = boff[q] + 2 * cp * plane + ky * cols + kx;
             float v = Xl[ad];
             if constexpr (ADJ) {
@@ -247,19 +264,20 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     for (int cb = 0; cb < Cin; cb += CK, cur ^= 1) {
         const float* Xc = Xl + cur * BUF;
         const float* Wc = Wl + cur * BUF;
-        float a[2][MF], b[2][2];
-        load_ops(Xc, Wc, 0, a[0], b[0]);
+        float a[LA + 1][MF], b[LA + 1][NQ];
+#pragma unroll
+        for (int s_ = 0; s_ < LA; ++s_) load_ops(Xc, Wc, s_, a[s_], b[s_]);
 #pragma unroll
         for (int s_ = 0; s_ < NS; ++s_) {
-            // operands one k-step ahead; the scheduling barriers keep hipcc from sinking the ds_reads below the
+            // operands LA k-steps ahead; the scheduling barriers keep hipcc from sinking the ds_reads below the
             // MFMAs that hide them (it would then wait on them right away) or hoisting a whole chunk's reads
-            if (s_ + 1 < NS) load_ops(Xc, Wc, s_ + 1, a[(s_ + 1) & 1], b[(s_ + 1) & 1]);
+            if (s_ + LA < NS) load_ops(Xc, Wc, s_ + LA, a[(s_ + LA) % (LA + 1)], b[(s_ + LA) % (LA + 1)]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int m = 0; m < MF; ++m)
 #pragma unroll
-                for (int q = 0; q < 2; ++q)
-                    acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ & 1][m], b[s_ & 1][q], acc[m][q], 0, 0, 0);
+                for (int q = 0; q < NQ; ++q)
+                    acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ % (LA + 1)][m], b[s_ % (LA + 1)][q], acc[m][q], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (s_ == COMMIT_AT && cb + CK < Cin) {
                 commit(cur ^ 1);
@@ -274,8 +292,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     const size_t outHW = (size_t)p.OutH * p.OutW;
     float* on = p.out + (size_t)n * p.Cout * outHW;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int f = 2 * wave + q;
+    for (int q = 0; q < NQ; ++q) {
+        const int f = NQ * wave + q;
         const int oy = oy0 + f * FR + fy, ox = ox0 + fx;
         if (oy >= p.Hout || ox >= p.Wout) continue;
         const size_t sp = (size_t)(oy * p.osy + p.ooy) * p.OutW + (ox * p.osx + p.oox);
@@ -310,15 +328,15 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     }
 }
 
-template <int K, int S, int MF, bool ADJ>
+template <int K, int S, int MF, bool ADJ, int SP = 1>
 int launch_conv(const ConvParams& p, int N, int tiles, hipStream_t st) {
-    constexpr int CK = Cfg<K, S>::CK;
-    constexpr int NT = Cfg<K, S>::NT;
+    constexpr int CK = Cfg<K, S, SP>::CK;
+    constexpr int NT = Cfg<K, S, SP>::NT;
     const int FC = 1 << p.log2fc, FR = 32 >> p.log2fc;
-    const int rows = (8 * FR - 1) * S + K, cols = (FC - 1) * S + K;
+    const int rows = ((8 / SP) * FR - 1) * S + K, cols = (FC - 1) * S + K;
     const size_t lds = 2 * ((((size_t)CK * rows * cols + 3) & ~(size_t)3) + (size_t)NT * CK * 32 * MF) * sizeof(float);
     dim3 grid(tiles, p.CoutP / (32 * MF), N);
-    hipLaunchKernelGGL((conv_igemm_kernel<K, S, MF, ADJ>), grid, dim3(256), lds, st, p);
+    hipLaunchKernelGGL((conv_igemm_kernel<K, S, MF, ADJ, SP>), grid, dim3(Cfg<K, S, SP>::NTHR), lds, st, p);
     C2S_CHECK_LAUNCH("conv_igemm");
     return C2S_OK;
 }
@@ -333,10 +351,43 @@ void init_hook() {
     C2S_RAISE_LDS((conv_igemm_kernel<3, 1, 2, true>));
     C2S_RAISE_LDS((conv_igemm_kernel<2, 1, 1, true>));
     C2S_RAISE_LDS((conv_igemm_kernel<2, 1, 2, true>));
+#define C2S_RAISE_SP(K_, S_, A_)                              \
+    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, A_, 2>));     \
+    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, A_, 4>));
+    C2S_RAISE_SP(3, 1, false) C2S_RAISE_SP(3, 1, true) C2S_RAISE_SP(1, 1, false) C2S_RAISE_SP(2, 1, false)
+    C2S_RAISE_SP(2, 1, true) C2S_RAISE_SP(4, 2, false) C2S_RAISE_SP(2, 2, false) C2S_RAISE_SP(6, 2, false)
+#undef C2S_RAISE_SP
 }
 C2sInitRegistrar registrar(init_hook);
 
+// log2 of the fragment width and the workgroups of a launch at split sp (32-channel tiles)
+int frag_log2(const c2s_conv_desc* d) {
+    int l2 = 5;
+    while (l2 > 2 && (1 << l2) > d->Wout) --l2;
+    return l2;
+}
+long split_wgs(const c2s_conv_desc* d, int sp) {
+    const int l2 = frag_log2(d);
+    return (long)cdiv(d->Wout, 1 << l2) * cdiv(d->Hout, (8 / sp) * (32 >> l2)) * d->N * (d->CoutP / 32);
+}
+// C2S_IGEMM_SPLIT=1|2|4 forces the split (A/B runs, tests); anything else: the rule
+int forced_split() {
+    const char* e = getenv("C2S_IGEMM_SPLIT");
+    if (e == nullptr || e[0] == 0 || e[1] != 0) return 0;
+    return e[0] == '1' ? 1 : (e[0] == '2' ? 2 : (e[0] == '4' ? 4 : 0));
+}
+
 }  // namespace
+
+// The split of a launch (1, 2 or 4), host arithmetic only.  1 where the 256-position tiles already put two workgroups
+// on every CU (every large launch); otherwise the smallest split that does, else 4.  Never decreases as N shrinks; the
+// result of a launch does not depend on it (bit-identical tiles), only its duration does.
+extern "C" int c2s_conv_igemm_split(const c2s_conv_desc* d, int cus) {
+    if (d == nullptr || d->N <= 0 || d->C0 <= 0 || d->C1 < 0 || d->CoutP < 32 || d->Hout <= 0 || d->Wout <= 0 || d->KH <= 0) return 1;
+    if (cus <= 0) cus = c2s_cus();
+    if (split_wgs(d, 1) >= 2L * cus) return 1;
+    return split_wgs(d, 2) >= 2L * cus ? 2 : 4;
+}
 
 extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const float* src1, const float* wpk,
                               const float* bias, float* out, const int* valid, void* stream) {
@@ -391,20 +442,25 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
             if (d->pad_x == 0) p.ax_lo = 0; else p.ax_hi = d->Wout - 1;
         }
     }
-    int l2 = 5;
-    while (l2 > 2 && (1 << l2) > d->Wout) --l2;
+    const int l2 = frag_log2(d);
     p.log2fc = l2;
     const int FC = 1 << l2, FR = 32 >> l2;
     p.tiles_x = cdiv(d->Wout, FC);
-    const int tiles = p.tiles_x * cdiv(d->Hout, 8 * FR);
     hipStream_t st = (hipStream_t)stream;
     // 64-channel tiles halve the LDS reads per MFMA, but on small planes (16x16 and below) they leave the grid short of
     // two workgroups per CU: fall back to 32-channel tiles there
     const int cus = c2s_cus();
-    const bool wide = d->CoutP % 64 == 0 && (long)tiles * d->N * (d->CoutP / 64) >= 2L * cus;
-#define C2S_DISPATCH(K_, S_, A_)                                        \
-    if (d->KH == K_ && d->S == S_ && (p.adj != 0) == A_)                \
-        return wide ? launch_conv<K_, S_, 2, A_>(p, d->N, tiles, st) : launch_conv<K_, S_, 1, A_>(p, d->N, tiles, st);
+    // launches that still leave CUs empty run on smaller tiles with one fragment per wave (c2s_conv_igemm_split)
+    const int forced = forced_split();
+    const int sp = forced ? forced : c2s_conv_igemm_split(d, cus);
+    const int tiles = p.tiles_x * cdiv(d->Hout, (8 / sp) * FR);
+    const bool wide = sp == 1 && d->CoutP % 64 == 0 && (long)tiles * d->N * (d->CoutP / 64) >= 2L * cus;
+#define C2S_DISPATCH(K_, S_, A_)                                                   \
+    if (d->KH == K_ && d->S == S_ && (p.adj != 0) == A_) {                         \
+        if (sp == 2) return launch_conv<K_, S_, 1, A_, 2>(p, d->N, tiles, st);     \
+        if (sp == 4) return launch_conv<K_, S_, 1, A_, 4>(p, d->N, tiles, st);     \
+        return wide ? launch_conv<K_, S_, 2, A_>(p, d->N, tiles, st) : launch_conv<K_, S_, 1, A_>(p, d->N, tiles, st); \
+    }
     C2S_DISPATCH(3, 1, false)
     C2S_DISPATCH(3, 1, true)
     C2S_DISPATCH(1, 1, false)

@@ -99,6 +99,15 @@ typedef struct c2s_conv_desc {
 
 int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const float* src1, const float* wpk,
                    const float* bias, float* out, const int* valid, void* stream);
+/* The tile split c2s_conv_igemm gives this launch: 1, 2 or 4 (host arithmetic only, no device call; cus <= 0: the compute
+ * units of the current device, 256 without one).  A launch whose 256-position x 32-channel tiles put fewer than two
+ * workgroups on every CU (the decoder and head layers, N = batch frames) runs on tiles of 256 / split positions with one
+ * 32-position fragment per wave (split 4: workgroups of two waves): split-fold the workgroups, half the MFMAs per
+ * wave.  Every output element keeps its chain of MFMAs, so the result is bit-identical at every split; only the
+ * duration depends on it.  1 when the launch fills the GPU without it; otherwise the smallest split that reaches two
+ * workgroups per CU, else 4.  C2S_IGEMM_SPLIT=1|2|4 in the environment (read at every call) forces the split in
+ * c2s_conv_igemm, for A/B runs; the query reports the rule. */
+int c2s_conv_igemm_split(const c2s_conv_desc* d, int cus);
 
 /* ------------------------------------------------------------------------------------------------
  * 3x3 stride-1 pad-1 convolution of a few input channels (<= 10: the Sentinel-2 bands of the first layer), same
