@@ -99,6 +99,7 @@ SIGNATURES = {
     "c2s_dwconv_fwd": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "c2s_dwconv_dgrad": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "c2s_dwconv_wgrad": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "c2s_dwconv_paths": (I, [I, I, I, I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
     "c2s_norm_workspace_floats": (SZ, [C.POINTER(NormDesc)]),
     "c2s_norm_fwd": (I, [C.POINTER(NormDesc), P, P, P, P, P, P, P, P, P, P, I, P, SZ, P, F, P]),
     "c2s_norm_bwd": (I, [C.POINTER(NormDesc), P, P, P, P, P, I, P, P, P, P, P, SZ, P, P]),

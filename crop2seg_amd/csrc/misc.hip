@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ i
     const int plane = blockIdx.y, c = plane % C, n = plane / C;
     if (valid != nullptr && valid[n] == 0) return;
     const int Ho = (Hin + 2 * pad - K) / S + 1, Wo = (Win + 2 * pad - K) / S + 1;
-    const int W4 = Wo / PX;                                          // PX = 4 needs Wo % 4 == 0 (host dispatch)
+    const int W4 = Wo / PX;                                          // PX = 4 needs Wo % 4 == 0, Win % 4 == 0 (dw_span4)
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= Ho * W4) return;
     const int oy = e / W4, ox0 = (e - oy * W4) * PX;
@@ -177,19 +177,25 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ i
 // data gradient, gather form: input pixel j receives from the padded positions that reflect onto it
 // (j itself; -j if 1 <= j <= pad; 2(n-1) - j if n-1-pad <= j <= n-2) through every tap whose output index is integral and
 // in range.  Per dimension that is a short list of (output index, tap) pairs -- at most 3 for 3x3/s1 plus one mirrored,
-// at most 2 + 2 for 4x4/s2, 3 + 1 for 6x6/s2 (pad 2), 1 for 2x2/s2 -- built once per thread without branches in the accumulation loop (invalid slots point at output 0
-// with weight 0); the 2-D gradient is the product of the two lists.  Four adjacent pixels of a row per thread (float4
-// store; the row list is shared).
+// 3 + 2 for 3x3/s1 on a dimension of 3 (its middle index is the image of both padded positions, -1 and 3), at most
+// 2 + 2 for 4x4/s2, 3 + 1 for 6x6/s2 (pad 2), 1 for 2x2/s2: DW_SLOTS<K> slots -- built once per thread without branches in
+// the accumulation loop (invalid slots point at output 0 with weight 0); the 2-D gradient is the product of the two lists.
+// One pixel per thread (the 4-pixel variant of the kernel is the stencil below and never gets here).
+template <int K>
+constexpr int DW_SLOTS = K == 3 ? 5 : 4;
+
 template <int K, int S>
-__device__ __forceinline__ void dw_pairs(int j, int n_in, int n_out, int pad, bool rf, int (&o)[4], int (&k)[4]) {
+__device__ __forceinline__ void dw_pairs(int j, int n_in, int n_out, int pad, bool rf, int (&o)[DW_SLOTS<K>],
+                                         int (&k)[DW_SLOTS<K>]) {
+    constexpr int NS = DW_SLOTS<K>;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { o[i] = 0; k[i] = -1; }
+    for (int i = 0; i < NS; ++i) { o[i] = 0; k[i] = -1; }
     int cnt = 0;
 #pragma unroll
     for (int kk = 0; kk < K; ++kk) {
         const int t = j + pad - kk;
         const bool ok = t >= 0 && (t % S) == 0 && t / S < n_out;
-        if (ok && cnt < 4) { o[cnt] = t / S; k[cnt] = kk; ++cnt; }
+        if (ok && cnt < NS) { o[cnt] = t / S; k[cnt] = kk; ++cnt; }
     }
     // mirrored sources: -j on the low side, 2(n-1) - j on the high side (both on planes of at most 2 * pad + 1)
     const bool lo = rf && j >= 1 && j <= pad, hi = rf && j >= n_in - 1 - pad && j <= n_in - 2;
@@ -201,7 +207,7 @@ __device__ __forceinline__ void dw_pairs(int j, int n_in, int n_out, int pad, bo
         for (int kk = 0; kk < K; ++kk) {
             const int t = qm + pad - kk;
             const bool ok = t >= 0 && (t % S) == 0 && t / S < n_out;
-            if (ok && cnt < 4) { o[cnt] = t / S; k[cnt] = kk; ++cnt; }
+            if (ok && cnt < NS) { o[cnt] = t / S; k[cnt] = kk; ++cnt; }
         }
     }
 }
@@ -215,7 +221,7 @@ __global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__
     if (threadIdx.x < K * K) ws[threadIdx.x] = w[(size_t)c * K * K + threadIdx.x];
     if (threadIdx.x == K * K) ws[K * K] = 0.f;                      // weight of an empty slot
     __syncthreads();
-    const int W4 = Win / PX;                                          // PX = 4 needs Win % 4 == 0 (host dispatch)
+    const int W4 = Win / PX;                                          // PX = 4 needs Win % 4 == 0 (dw_stencil4)
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= Hin * W4) return;
     const int jy = e / W4, jx0 = (e - jy * W4) * PX;
@@ -293,18 +299,19 @@ __global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__
         *reinterpret_cast<f32x4*>(gp_in) = r;
         return;
     }
-    int oy[4], ky[4];
+    constexpr int NS = DW_SLOTS<K>;
+    int oy[NS], ky[NS];
     dw_pairs<K, S>(jy, Hin, Ho, pad, rf, oy, ky);
     float res[PX];
 #pragma unroll
     for (int u = 0; u < PX; ++u) {
-        int ox[4], kx[4];
+        int ox[NS], kx[NS];
         dw_pairs<K, S>(jx0 + u, Win, Wo, pad, rf, ox, kx);
         float acc = 0.f;
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
+        for (int a = 0; a < NS; ++a) {
 #pragma unroll
-            for (int bb = 0; bb < 4; ++bb) {
+            for (int bb = 0; bb < NS; ++bb) {
                 const int wi = (ky[a] >= 0 && kx[bb] >= 0) ? ky[a] * K + kx[bb] : K * K;
                 acc = fmaf(ws[wi], gp[oy[a] * Wo + ox[bb]], acc);
             }
@@ -324,7 +331,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_kernel(const float* __restrict__
     __shared__ float red[4][K * K];
     const int n = blockIdx.x / C;
     const int Ho = (Hin + 2 * pad - K) / S + 1, Wo = (Win + 2 * pad - K) / S + 1;
-    const int W4 = Wo / PX;                                          // PX = 4 needs Wo % 4 == 0 (host dispatch)
+    const int W4 = Wo / PX;                                          // PX = 4 needs Wo % 4 == 0, Win % 4 == 0 (dw_span4)
     float acc[K * K];
 #pragma unroll
     for (int k = 0; k < K * K; ++k) acc[k] = 0.f;
@@ -517,6 +524,31 @@ static int dw_check(int N, int C, int Hin, int Win, int K, int S, int pad, int p
     return C2S_OK;
 }
 
+// Pixels per thread of the three exports (the table at c2s_dwconv_paths in include/c2s_hip.h).  The launchers and the query
+// call these two predicates, nothing else decides.
+// forward and weight gradient: dw_load_span<K,S,4> reads aligned float4s of the input row -- pad == 1, Win % 4 == 0 -- and the
+// thread writes / reads one float4 of the output row -- Wo % 4 == 0.  (For 3x3/s1 Wo == Win; for 4x4/s2 an odd Win can have
+// Wo % 4 == 0, e.g. 9 -> 4: one output per thread.)
+static bool dw_span4(int Win, int K, int S, int pad) {
+    if (K == 2 || K == 6) return false;                             // the 4-wide span loader assumes pad 1
+    const int Wo = (Win + 2 * pad - K) / S + 1;
+    return Wo % 4 == 0 && Win % 4 == 0;
+}
+// data gradient: the border stencil of dw_dgrad_kernel<K,S,4> is written for Win % 4 == 0, Win >= 8, Hin >= 4 (rows 1 and
+// Hin - 2, each with its one reflected slot, are different rows) and, for 4x4/s2, an even Hin (Ho = Hin / 2)
+static bool dw_stencil4(int Hin, int Win, int K) {
+    if (K == 2 || K == 6) return false;                             // the 4-wide stencil is written for pad 1: the gather form
+    return Win % 4 == 0 && Win >= 8 && Hin >= 4 && (K == 3 || Hin % 2 == 0);
+}
+
+extern "C" int c2s_dwconv_paths(int Hin, int Win, int K, int S, int pad, int pad_mode, int* fwd, int* dgrad, int* wgrad) {
+    if (int rc = dw_check(1, 1, Hin, Win, K, S, pad, pad_mode)) return rc;
+    C2S_REQUIRE(fwd && dgrad && wgrad, "dwconv_paths: null pointer");
+    *fwd = *wgrad = dw_span4(Win, K, S, pad) ? 4 : 1;
+    *dgrad = dw_stencil4(Hin, Win, K) ? 4 : 1;
+    return C2S_OK;
+}
+
 extern "C" int c2s_dwconv_fwd(const float* in, const float* w, float* out, const int* valid, int N, int C, int Hin,
                               int Win, int K, int S, int pad, int pad_mode, void* stream) {
     if (int rc = dw_check(N, C, Hin, Win, K, S, pad, pad_mode)) return rc;
@@ -524,11 +556,11 @@ extern "C" int c2s_dwconv_fwd(const float* in, const float* w, float* out, const
     const int Ho = (Hin + 2 * pad - K) / S + 1, Wo = (Win + 2 * pad - K) / S + 1;
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
     hipStream_t st = (hipStream_t)stream;
-    if (K == 2 || K == 6) {         // the 4-wide span loader assumes pad 1: one output per thread
+    if (K == 2 || K == 6) {         // one output per thread (dw_span4 is false)
         const dim3 grid(cdiv(Ho * Wo, 256), N * C);
         if (K == 2) hipLaunchKernelGGL((dw_fwd_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
         else hipLaunchKernelGGL((dw_fwd_kernel<6, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
-    } else if (Wo % 4 == 0) {
+    } else if (dw_span4(Win, K, S, pad)) {
         const dim3 grid(cdiv(Ho * (Wo / 4), 256), N * C);
         if (K == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 1, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
         else hipLaunchKernelGGL((dw_fwd_kernel<4, 2, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
@@ -547,11 +579,11 @@ extern "C" int c2s_dwconv_dgrad(const float* gout, const float* w, float* gin, c
     C2S_REQUIRE(gout && w && gin, "dwconv_dgrad: null pointer");
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
     hipStream_t st = (hipStream_t)stream;
-    if (K == 2 || K == 6) {         // the 4-wide stencil is written for pad 1: the gather form
+    if (K == 2 || K == 6) {         // the gather form (dw_stencil4 is false)
         const dim3 grid(cdiv(Hin * Win, 256), N * C);
         if (K == 2) hipLaunchKernelGGL((dw_dgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
         else hipLaunchKernelGGL((dw_dgrad_kernel<6, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
-    } else if (Win % 4 == 0 && Win >= 8 && Hin >= 4 && (K == 3 || Hin % 2 == 0)) {
+    } else if (dw_stencil4(Hin, Win, K)) {
         const dim3 grid(cdiv(Hin * (Win / 4), 256), N * C);
         if (K == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
         else hipLaunchKernelGGL((dw_dgrad_kernel<4, 2, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
@@ -570,12 +602,11 @@ extern "C" int c2s_dwconv_wgrad(const float* in, const float* gout, float* parti
     C2S_REQUIRE(in && gout && partial && gw, "dwconv_wgrad: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
-    const int Wo = (Win + 2 * pad - K) / S + 1;
     const dim3 grid(N * C);
     if (K == 2 || K == 6) {
         if (K == 2) hipLaunchKernelGGL((dw_wgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
         else hipLaunchKernelGGL((dw_wgrad_kernel<6, 2, 1>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
-    } else if (Wo % 4 == 0) {
+    } else if (dw_span4(Win, K, S, pad)) {
         if (K == 3) hipLaunchKernelGGL((dw_wgrad_kernel<3, 1, 4>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
         else hipLaunchKernelGGL((dw_wgrad_kernel<4, 2, 4>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);
     } else {

@@ -275,6 +275,17 @@ int c2s_dwconv_dgrad(const float* gout, const float* w, float* gin, const int* v
 /* gw[C,K,K] = sum_n ...; `partial` is scratch of N*C*K*K floats */
 int c2s_dwconv_wgrad(const float* in, const float* gout, float* partial, float* gw, const int* valid, int N, int C,
                      int Hin, int Win, int K, int S, int pad, int pad_mode, void* stream);
+/* Pixels per thread (1 or 4) of the kernel each of the three exports launches on an Hin x Win plane; a pure host query (no
+ * device is touched) that calls the predicates the launchers call.  Returns what the exports return for these arguments:
+ * C2S_EINVAL for a (K,S,pad) outside (3,1,1), (4,2,1), (2,2,0), (6,2,2) and for reflect padding on a plane of Hin <= pad or
+ * Win <= pad (or below 2), with the outputs untouched.  With Wo = (Win + 2 pad - K) / S + 1:
+ *   *fwd, *wgrad: 4 if (K,S,pad) is (3,1,1) or (4,2,1) and Wo % 4 == 0 and Win % 4 == 0   (one float4 of the output row, aligned
+ *                   float4s of the input row), else 1.  An odd Win of 4x4/s2 with Wo % 4 == 0 (9 -> 4) runs on 1.
+ *   *dgrad:       4 if (K,S,pad) is (3,1,1) or (4,2,1) and Win % 4 == 0 and Win >= 8 and Hin >= 4 and (K == 3 or Hin even)
+ *                   (the border stencil), else 1 (the gather form, whose pair lists hold 5 entries per dimension for 3x3/s1:
+ *                   reflect padding on a dimension of 3 folds both padded positions onto its middle index).
+ * (2,2,0) and (6,2,2) always run on 1.  The padding mode does not enter the choice. */
+int c2s_dwconv_paths(int Hin, int Win, int K, int S, int pad, int pad_mode, int* fwd, int* dgrad, int* wgrad);
 
 /* ------------------------------------------------------------------------------------------------
  * Normalisation + ReLU (+ residual), GroupNorm and train/eval BatchNorm share one set of kernels:
