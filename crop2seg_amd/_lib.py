@@ -117,12 +117,17 @@ SIGNATURES = {
     "c2s_ltae_fold_fwd": (I, [P] * 9 + [I, I, P]),
     "c2s_ltae_fold_bwd": (I, [P] * 16 + [I, I, I, P, SZ, P]),
     "c2s_ltae_fold_bwd_workspace_floats": (SZ, []),
+    "c2s_positional_table_ex": (I, [P, P, L, C.c_float, I, P]),
+    "c2s_ltae_fold_fwd_ex": (I, [P] * 9 + [I, I, I, I, I, P]),
+    "c2s_ltae_fold_bwd_ex": (I, [P] * 16 + [I, I, I, I, I, I, P, SZ, P]),
+    "c2s_ltae_fold_bwd_workspace_floats_ex": (SZ, [I, I]),
     "c2s_ltae_pe_table": (I, [I, P, P, F, P, P, P, P, P, I, P]),
     "c2s_ltae_pe_abs_add": (I, [P, P, P, P, P, I, P]),
     "c2s_ltae_pe_abs_bwd": (I, [P, P, P, P, I, P]),
     "c2s_ltae_pe_fwd": (I, [P, P, P, P, P, I, I, I, I, P]),
     "c2s_ltae_pe_gattn": (I, [P, P, P, P, I, I, I, P]),
     "c2s_ltae_pe_bwd": (I, [I] + [P] * 15 + [I, I, I, P]),
+    "c2s_ltae_pe_bwd_ex": (I, [I] + [P] * 15 + [I, I, I, I, P]),
     "c2s_ltae_fwd_workspace_floats": (SZ, [C.POINTER(LtaeDesc)]),
     "c2s_ltae_attn_fwd_ws": (I, [C.POINTER(LtaeDesc)] + [P] * 13 + [P, SZ, P]),
     "c2s_ltae_uses_streaming": (I, [C.POINTER(LtaeDesc)]),

@@ -396,6 +396,9 @@ class _Backbone(nn.Module):
         if H % 8 or W % 8 or H < 16 or W < 16:
             raise ValueError("H and W must be multiples of 8 and >= 16")
         B, T = input.shape[:2]
+        if T > 64 and (self.spec.n_head, self.spec.d_model) != (16, 256):
+            raise NotImplementedError("crop2seg_amd: series longer than 64 time steps are built for n_head=16, d_model=256; got "
+                                      f"n_head={self.spec.n_head}, d_model={self.spec.d_model} at T={T}")
         if T > 64:      # the time-chunked L-TAE kernels (csrc/ltae_long.hip)
             c_ltae = self.spec.encoder_widths[0] if self.spec.model == "timeunet" else self.spec.encoder_widths[-1]
             if c_ltae not in (64, 128, 256):
@@ -473,10 +476,24 @@ def _common_init(self, model, input_dim, encoder_widths, decoder_widths, out_con
             f"{bad or dict(conv_type=conv_type, agg_mode=agg_mode)}")
     # Limits compiled into the kernels (include/c2s_hip.h, INTEGRATION.md "Shape limits"): raise HERE, naming the limit, not as a
     # C-ABI error code from the first forward.  The reference builds any combination (train.py:35-43, tae.py:355-449).
-    if (n_head, d_model, d_k) != (16, 256, 4):
+    # The kernels and the C ABI (engine.ltae_attention, c2s_ltae_desc, the c2s_ltae_fold_*_ex entry points) take n_head in
+    # {8, 16} and d_k in 1..32; the model classes keep refusing both away from the reference's defaults, as they always have
+    # (tests/test_abi.py::test_offdefault_flags_fail_loudly holds them to that), and open d_model alone.
+    if n_head != 16 or d_k != 4:
         raise NotImplementedError(
-            f"crop2seg_amd: the L-TAE kernels are built for n_head=16, d_model=256, d_k=4 (the reference's defaults, train.py:40-43); "
-            f"got n_head={n_head}, d_model={d_model}, d_k={d_k}")
+            f"crop2seg_amd: the model classes are built for n_head=16, d_k=4 (the reference's defaults, train.py:40-43), with "
+            f"d_model in {{128, 256, 512}}; got n_head={n_head}, d_k={d_k}")
+    if d_model is None or d_model % n_head or d_model // n_head not in (8, 16, 32):
+        raise NotImplementedError(
+            f"crop2seg_amd: the L-TAE kernels are built for d_model / n_head in {{8, 16, 32}} (d_model 128, 256 or 512); "
+            f"got d_model={d_model} with n_head={n_head}")
+    # Any other pair than the reference's default (train.py:40-41) runs the 16-pixel / 8-pixel kernel family (csrc/ltae.hip) at
+    # every map size, with the default sinusoid table only.
+    default_heads = (n_head, d_model) == (16, 256)
+    if not default_heads and (use_doy or use_abs_rel_enc or add_linear):
+        raise NotImplementedError(
+            "crop2seg_amd: the learnable positional encoders (use_doy / use_abs_rel_enc / add_linear) are built for n_head=16, "
+            f"d_model=256; got n_head={n_head}, d_model={d_model}")
     if (str_conv_k, str_conv_s, str_conv_p) not in STR_CONV_GEOMETRIES:
         raise NotImplementedError(
             f"crop2seg_amd: the strided / transposed convolutions are built for str_conv_k=4, str_conv_s=2, str_conv_p=1 (the "
@@ -487,6 +504,17 @@ def _common_init(self, model, input_dim, encoder_widths, decoder_widths, out_con
         raise NotImplementedError(
             "crop2seg_amd: the L-TAE kernels take a multiple of 64 input channels, at most 256 (encoder_widths[-1]; "
             f"encoder_widths[0] for TimeUNet_v1); got encoder_widths={list(encoder_widths)}")
+    if not default_heads:
+        if c_ltae % n_head or c_ltae // n_head > 16:
+            raise NotImplementedError(
+                f"crop2seg_amd: the L-TAE normalises groups of at most 16 channels: its {c_ltae} input channels (encoder_widths="
+                f"{list(encoder_widths)}) over n_head={n_head} groups give {c_ltae / n_head:g}")
+        agg_widths = [c_ltae] if model == "timeunet" else list(encoder_widths)
+        wrong = [w for w in agg_widths if w % n_head or w // n_head not in (1, 2, 4, 8, 16)]
+        if wrong:
+            raise NotImplementedError(
+                f"crop2seg_amd: the temporal aggregation takes widths with width / n_head in {{1, 2, 4, 8, 16}}; got widths {wrong} "
+                f"of encoder_widths={list(encoder_widths)} with n_head={n_head}")
     if encoder:
         return_maps = True                      # utae.py:129-130
     if decoder_widths is None:

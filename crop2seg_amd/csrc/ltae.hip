@@ -85,14 +85,20 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned grid) {
 //   3 softmax : (pixel, head)                   loop t over LDS; writes attn / attn_pre
 //   4 z       : slot = channel(s)               loop t; 16 head accumulators x 4 pixels -> LDS (CH channels at a time)
 //   5 emb     : (pixel, head)                   loop c over LDS; Wc rows from L1/L2
+// NH heads of width DV (the file-scope 16 x 16 is the default instantiation and the only one the other families know):
+// with NH = 8 the threads of the (pixel, head) and (group, t mod 4) mappings whose head / group index is >= NH idle through
+// those phases (every thread still reaches every barrier); a wave owns NH/4 heads in phase 5, whose 16 MFMA columns are the
+// head width: DV = 8 feeds zeros to columns 8..15, DV = 32 takes two column blocks.
+template <int NH = 16, int DV = 16>
 __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
+    static_assert((NH == 8 || NH == 16) && (DV == 8 || DV == 16 || DV == 32), "ltae_fwd_kernel: unsupported head layout");
     extern __shared__ float lds[];
     const int C = p.C, T = p.T, HW = p.HW;
     const int CH = C > 64 ? 64 : C;             // channels per z/emb pass
     float* ABl = lds;                           // [C][2][16]   per-(channel,pixel) scale, shift of the GroupNorm
-    float* Sl = ABl + C * 32;                   // [T][16][16]  scores -> attention (post-dropout)
-    float* ASl = Sl + T * 256;                  // [16][16]     sum_t attention
-    float* Zl = ASl + 256;                      // [16][CH][16] z = sum_t attn * xhat   (also the stats scratch)
+    float* Sl = ABl + C * 32;                   // [T][NH][16]  scores -> attention (post-dropout)
+    float* ASl = Sl + T * NH * 16;              // [NH][16]     sum_t attention
+    float* Zl = ASl + NH * 16;                  // [NH][CH][16] z = sum_t attn * xhat   (also the stats scratch)
     const int tid = threadIdx.x;
     const int q = tid & 3, slot = tid >> 2;      // streaming mapping
     const int px = tid & 15, hh = tid >> 4;      // per-pixel mapping
@@ -109,7 +115,7 @@ __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
 
     // ---- phase 1: GroupNorm statistics (padded frames included, tae.py:461): 4 partials per group, each a Chan merge of
     // exact two-pass moments of the cpg values of one time step (error independent of the data, see the streaming kernel)
-    {
+    if (NH >= 16 || (slot & 15) < NH) {
         const int g = slot & 15, tq = slot >> 4;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         f32x4 mean = zero, m2 = zero;
@@ -143,7 +149,7 @@ __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
         *reinterpret_cast<f32x4*>(Zl + ((g * 4 + tq) * 2 + 1) * 16 + 4 * q) = m2;
     }
     __syncthreads();
-    {
+    if (NH >= 16 || hh < NH) {
         const int g = hh;       // (pixel, group)
         float cnt = 0.f, mean = 0.f, m2 = 0.f;
 #pragma unroll
@@ -192,31 +198,31 @@ __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
         const bool padded = p.valid != nullptr && p.valid[b * T + t] == 0;
 #pragma unroll
         for (int h = 0; h < NH; ++h)
-            *reinterpret_cast<f32x4*>(Sl + (t * 16 + h) * 16 + 4 * q) = padded ? (f32x4){-1e6f, -1e6f, -1e6f, -1e6f} : sc[h];   // tae.py:831
+            *reinterpret_cast<f32x4*>(Sl + (t * NH + h) * 16 + 4 * q) = padded ? (f32x4){-1e6f, -1e6f, -1e6f, -1e6f} : sc[h];   // tae.py:831
     }
     __syncthreads();
 
     // ---- phase 3: softmax over T for (pixel, head), dropout
-    {
+    if (NH >= 16 || hh < NH) {
         float mx = -3.0e38f;
-        for (int t = 0; t < T; ++t) mx = fmaxf(mx, Sl[(t * 16 + hh) * 16 + px]);
+        for (int t = 0; t < T; ++t) mx = fmaxf(mx, Sl[(t * NH + hh) * 16 + px]);
         float den = 0.f;
         for (int t = 0; t < T; ++t) {
-            const float e = __expf(Sl[(t * 16 + hh) * 16 + px] - mx);
-            Sl[(t * 16 + hh) * 16 + px] = e;
+            const float e = __expf(Sl[(t * NH + hh) * 16 + px] - mx);
+            Sl[(t * NH + hh) * 16 + px] = e;
             den += e;
         }
         const float inv_den = 1.f / den;
         float asum = 0.f;
         for (int t = 0; t < T; ++t) {
-            const float a = Sl[(t * 16 + hh) * 16 + px] * inv_den;
+            const float a = Sl[(t * NH + hh) * 16 + px] * inv_den;
             const float ad = a * keep_scale(p, hh, Ptot, pidx, t);
             const size_t o = ((size_t)(hh * p.B + b) * T + t) * HW + pix;
             if (act) {
                 if (p.attn_pre != nullptr) p.attn_pre[o] = a;
                 p.attn[o] = ad;
             }
-            Sl[(t * 16 + hh) * 16 + px] = ad;
+            Sl[(t * NH + hh) * 16 + px] = ad;
             asum += ad;
         }
         ASl[hh * 16 + px] = asum;
@@ -225,11 +231,15 @@ __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
     __syncthreads();
 
     // ---- phases 4+5, CH channels at a time.  Phase 5 runs on the 16x16x4 MFMA (rows = pixel, columns = j, k = channel,
-    // then k = time step for the positional term): wave w owns heads 4w..4w+3, one accumulator each.
+    // then k = time step for the positional term): wave w owns heads HPW*w..HPW*w+HPW-1, one accumulator per column block.
+    constexpr int HPW = NH / 4, NB = (DV + 15) / 16;
     const int l15 = tid & 15, l4 = (tid & 63) >> 4, wv = tid >> 6;
-    f32x4 eacc[4];
+    const bool jv = DV >= 16 || l15 < DV;        // column j = 16*nb + l15 exists
+    f32x4 eacc[HPW][NB];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) eacc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < HPW; ++i)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) eacc[i][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < C; c0 += CH) {
         // 4: z[h] = sum_t attn[h,t] * x[t,c] for channel c = c0 + slot (4 pixels per thread)
         for (int c = c0 + slot; c < c0 + CH; c += 64) {
@@ -240,7 +250,7 @@ __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
             for (int t = 0; t < T; ++t) {
                 const f32x4 xv = *reinterpret_cast<const f32x4*>(xq + (size_t)(t * C + c) * HW);
 #pragma unroll
-                for (int h = 0; h < NH; ++h) z[h] += *reinterpret_cast<const f32x4*>(Sl + (t * 16 + h) * 16 + 4 * q) * xv;
+                for (int h = 0; h < NH; ++h) z[h] += *reinterpret_cast<const f32x4*>(Sl + (t * NH + h) * 16 + 4 * q) * xv;
             }
             const f32x4 a = *reinterpret_cast<const f32x4*>(ABl + (c * 2 + 0) * 16 + 4 * q);
             const f32x4 bb = *reinterpret_cast<const f32x4*>(ABl + (c * 2 + 1) * 16 + 4 * q);
@@ -252,32 +262,48 @@ __global__ __launch_bounds__(256) void ltae_fwd_kernel(LtaeParams p) {
         __syncthreads();
         // 5: emb[px][16h+j] += sum_c z[h][c][px] Wc[16h+j][c]; k-step (m, i) lane-quarter l4 <-> channel 16m + 4*l4 + i
 #pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) {
-            const int h = wv * 4 + i4;
+        for (int i4 = 0; i4 < HPW; ++i4) {
+            const int h = wv * HPW + i4;
             for (int m = 0; m < CH / 16; ++m) {
-                const f32x4 wq = *reinterpret_cast<const f32x4*>(p.Wc + (size_t)(h * DV + l15) * C + c0 + 16 * m + 4 * l4);
+                f32x4 wq[NB];
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    eacc[i4] = __builtin_amdgcn_mfma_f32_16x16x4f32(Zl[(h * CH + 16 * m + 4 * l4 + i) * 16 + l15], wq[i], eacc[i4], 0, 0, 0);
+                for (int nb = 0; nb < NB; ++nb) {
+                    wq[nb] = *reinterpret_cast<const f32x4*>(p.Wc + (size_t)(h * DV + (jv ? 16 * nb + l15 : 0)) * C + c0 + 16 * m + 4 * l4);
+                    if (!jv) wq[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float zv = Zl[(h * CH + 16 * m + 4 * l4 + i) * 16 + l15];
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb)
+                        eacc[i4][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(zv, wq[nb][i], eacc[i4][nb], 0, 0, 0);
+                }
             }
         }
         __syncthreads();
     }
 #pragma unroll
-    for (int i4 = 0; i4 < 4; ++i4) {
-        const int h = wv * 4 + i4;
+    for (int i4 = 0; i4 < HPW; ++i4) {
+        const int h = wv * HPW + i4;
         // + sum_t attn[h,t] pe[t][j]  (k = time step, zero beyond T)
         for (int t0 = 0; t0 < T; t0 += 4) {
             const int t = t0 + l4;
-            const float av = Sl[((t < T ? t : 0) * 16 + h) * 16 + l15];
-            const float pv = p.pe[(size_t)(b * T + (t < T ? t : 0)) * DV + l15];
-            eacc[i4] = __builtin_amdgcn_mfma_f32_16x16x4f32(t < T ? av : 0.f, pv, eacc[i4], 0, 0, 0);
+            const float av = Sl[((t < T ? t : 0) * NH + h) * 16 + l15];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const float pv = p.pe[(size_t)(b * T + (t < T ? t : 0)) * DV + (jv ? 16 * nb + l15 : 0)];
+                eacc[i4][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(t < T ? av : 0.f, pv, eacc[i4][nb], 0, 0, 0);
+            }
         }
-        // D[row = pixel 4*l4 + r][col = j = l15];  + (sum_t attn) * bc[j]
-        const float bcv = p.bc[h * DV + l15];
+        // D[row = pixel 4*l4 + r][col = j = 16*nb + l15];  + (sum_t attn) * bc[j]
+        float bcv[NB];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) bcv[nb] = p.bc[h * DV + (jv ? 16 * nb + l15 : 0)];
         const f32x4 as4 = *reinterpret_cast<const f32x4*>(ASl + h * 16 + 4 * l4);
-        if (pix0 + 4 * l4 < HW)
-            *reinterpret_cast<f32x4*>(p.emb + ((size_t)b * NH * DV + h * DV + l15) * HW + pix0 + 4 * l4) = eacc[i4] + as4 * bcv;
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+            if (jv && pix0 + 4 * l4 < HW)
+                *reinterpret_cast<f32x4*>(p.emb + ((size_t)b * NH * DV + h * DV + 16 * nb + l15) * HW + pix0 + 4 * l4) = eacc[i4][nb] + as4 * bcv[nb];
     }
 }
 
@@ -495,14 +521,16 @@ __global__ __launch_bounds__(256) void ltae_lds_fwd_kernel(LtaeParams p) {
 //   C  V (slots 0..63) and Z (slots 64..127)     slot % 64 = channel
 constexpr int BPT = 8;      // pixels per backward tile
 
+template <int NH = 16, int DV = 16>
 __global__ __launch_bounds__(256) void ltae_bwd_heads_kernel(LtaeParams p) {
+    static_assert((NH == 8 || NH == 16) && (DV == 8 || DV == 16 || DV == 32), "ltae_bwd_heads_kernel: unsupported head layout");
     constexpr int PT = BPT;
     constexpr int RC = 32;                       // channels per r-chunk
     extern __shared__ float lds[];
     const int C = p.C, T = p.T, HW = p.HW;
     float* ABl = lds;                            // [C][2][PT]
-    float* GEl = ABl + C * 2 * PT;               // [256][PT]
-    float* Rl = GEl + 256 * PT;                  // [16][RC][PT]
+    float* GEl = ABl + C * 2 * PT;               // [NH*DV][PT]
+    float* Rl = GEl + NH * DV * PT;              // [16][RC][PT]
     float* Dl = Rl + NH * RC * PT;               // [T][16][PT]  dot -> ga -> gs
     float* Al = Dl + T * NH * PT;                // [T][16][PT]  attention (post-dropout)
     float* APl = Al + T * NH * PT;               // [T][16][PT]  attention before dropout (softmax output)
@@ -550,13 +578,14 @@ __global__ __launch_bounds__(256) void ltae_bwd_heads_kernel(LtaeParams p) {
 
     if (p.g_emb != nullptr) {
         for (int c0 = 0; c0 < C; c0 += RC) {
-            // A1 on the 16x16x4 MFMA (rows = pixel, padded 8 -> 16; k = j; columns = 16 channels): wave w owns heads
-            // 4w..4w+3.  (One thread per (pixel, head, channel) with 16 scalar Wc loads each took 57% of this kernel.)
+            // A1 on the 16x16x4 MFMA (rows = pixel, padded 8 -> 16; k = j, DV/4 steps; columns = 16 channels): wave w owns
+            // heads (NH/4)w..(NH/4)w+NH/4-1.  (One thread per (pixel, head, channel) with 16 scalar Wc loads each took 57% of
+            // this kernel.)
             {
                 const int wv = tid >> 6, l15 = tid & 15, l4 = (tid & 63) >> 4;
 #pragma unroll
-                for (int hh = 0; hh < 4; ++hh) {
-                    const int h = wv * 4 + hh;
+                for (int hh = 0; hh < NH / 4; ++hh) {
+                    const int h = wv * (NH / 4) + hh;
 #pragma unroll
                     for (int cg = 0; cg < RC / 16; ++cg) {
                         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -686,13 +715,14 @@ __global__ __launch_bounds__(256) void ltae_bwd_heads_kernel(LtaeParams p) {
 // d xhat[t,c] = sum_h (attn[h,t] r[h,c] + gs[h,t] U[h,c]), then the per-pixel GroupNorm backward.
 // Streaming threads = (quad, slot): slot = (channel c = slot % 64 (+64), time half th = slot / 64).
 // GX = false (no input gradient): the d gamma / d beta partials only; p.gx is not touched.
-template <bool GX = true>
+template <bool GX = true, int NH = 16, int DV = 16>
 __global__ __launch_bounds__(256) void ltae_bwd_gx_kernel(LtaeParams p) {
+    static_assert((NH == 8 || NH == 16) && (DV == 8 || DV == 16 || DV == 32), "ltae_bwd_gx_kernel: unsupported head layout");
     constexpr int PT = BPT;
     extern __shared__ float lds[];
     const int C = p.C, T = p.T, HW = p.HW;
-    float* GEl = lds;                            // [256][PT]
-    float* Gl = GEl + 256 * PT;                  // [T][16][PT] gs
+    float* GEl = lds;                            // [NH*DV][PT]
+    float* Gl = GEl + NH * DV * PT;              // [T][16][PT] gs
     float* Al = Gl + T * NH * PT;                // [T][16][PT] attn
     float* Ml = Al + T * NH * PT;                // [C][2 th][2][PT]  partial (sum dxn, sum dxn*xn)
     float* STl = Ml + C * 4 * PT;                // [16][4][PT] mean, rstd, m1, m2 of each group
@@ -1142,19 +1172,26 @@ __global__ __launch_bounds__(64) void sum_over_pixels_kernel(const float* __rest
     if (lane == 0) out[row] = s;
 }
 
-// gWc[16h+j][c] = sum_{b,pix} ge[b,16h+j,pix] * Z[b,h,c,pix]    workgroup per (h,c): 16 j x 16 pixel lanes
+// gWc[DV*h+j][c] = sum_{b,pix} ge[b,DV*h+j,pix] * Z[b,h,c,pix]    workgroup per (h,c): 16 j x 16 pixel lanes; a wave holds
+// four j and DV is a multiple of 8, so the j loop is wave-uniform (DV = 16: one trip, DV = 8: waves 2 and 3 idle)
+template <int NH = 16, int DV = 16>
 __global__ __launch_bounds__(256) void gwc_kernel(const float* __restrict__ ge, const float* __restrict__ Z,
                                                   float* __restrict__ gWc, int B, int C, int HW) {
     const int h = blockIdx.x / C, c = blockIdx.x % C;
-    const int j = threadIdx.x >> 4, q = threadIdx.x & 15;
-    float s = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const float* z = Z + (((size_t)b * NH + h) * C + c) * HW;
-        const float* g = ge + ((size_t)b * NH * DV + h * DV + j) * HW;
-        for (int i = q; i < HW; i += 16) s += g[i] * z[i];
+    const int q = threadIdx.x & 15;
+#pragma unroll
+    for (int j0 = 0; j0 < DV; j0 += 16) {
+        const int j = j0 + (threadIdx.x >> 4);
+        if (DV < 16 && j >= DV) break;
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) {
+            const float* z = Z + (((size_t)b * NH + h) * C + c) * HW;
+            const float* g = ge + ((size_t)b * NH * DV + h * DV + j) * HW;
+            for (int i = q; i < HW; i += 16) s += g[i] * z[i];
+        }
+        s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 8, 64);
+        if (q == 0) gWc[(size_t)(h * DV + j) * C + c] = s;
     }
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 8, 64);
-    if (q == 0) gWc[(size_t)(h * DV + j) * C + c] = s;
 }
 
 // Large pixel counts: d Wc as 16 small GEMMs on the f32 MFMA (v_mfma_f32_16x16x4_f32), split over pixel slices.
@@ -1197,63 +1234,66 @@ __global__ __launch_bounds__(256) void gwc_mfma_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------ parameter fold
-// Parameter-only part of the re-association, d_model = 256, n_head = 16, d_k = 4:
-//   qWk[h][m] = (1/2) sum_d Q[h][d] Wk[4h+d][m]                    (1/sqrt(d_k) = 1/2)
+// Parameter-only part of the re-association for nh heads of width dv (d_model dm = nh * dv) and key
+// width dk, rsq = 1/sqrt(dk) (the defaults: 16, 16, 4, 1/2):
+//   qWk[h][m] = rsq sum_d Q[h][d] Wk[dk*h+d][m]
 //   U[h][c]   = sum_m qWk[h][m] Wc[m][c]
-//   s0[b,t,h] = sum_j (sum_{m = j mod 16} qWk[h][m]) pe[b,t,j] + sum_m qWk[h][m] bc[m] + (1/2) sum_d Q[h][d] bk[4h+d]
+//   s0[b,t,h] = sum_j (sum_{m = j mod dv} qWk[h][m]) pe[b,t,j] + sum_m qWk[h][m] bc[m] + rsq sum_d Q[h][d] bk[dk*h+d]
 // One workgroup per head for the forward, one workgroup per adjoint stage (a few MFLOP); fixed summation orders.
 // Replaces positional_encoding.py:16-33 and the key/query algebra of tae.py:790-830 on the parameter side.
-constexpr int DM = NH * DV;      // 256
-constexpr int DK = 4;
+constexpr int DM_MAX = 512, DV_MAX = 32, DK_MAX = 32;      // the widest fold: n_head 16 x head width 32
 
-__global__ void positional_table_kernel(const long long* __restrict__ dates, float* __restrict__ pe, long n, float period) {
+__global__ void positional_table_kernel(const long long* __restrict__ dates, float* __restrict__ pe, long n, float period, int dv) {
     const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (e >= n * DV) return;
-    const int j = (int)(e % DV);
-    const float denom = powf(period, (float)(2 * (j / 2)) / (float)DV);
-    const float a = (float)dates[e / DV] / denom;
+    if (e >= n * dv) return;
+    const int j = (int)(e % dv);
+    const float denom = powf(period, (float)(2 * (j / 2)) / (float)dv);
+    const float a = (float)dates[e / dv] / denom;
     pe[e] = (j & 1) ? cosf(a) : sinf(a);
 }
 
 // one workgroup per head (a single workgroup spent 47 us in 512 dependent loads per thread)
+// DKC, DVC > 0: the key / head width at compile time (4, 16: the default model, loops unrolled as before); 0: dk_, dv_
+template <int DKC, int DVC>
 __global__ __launch_bounds__(1024) void ltae_fold_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ Wk,
                                                              const float* __restrict__ bk, const float* __restrict__ Wc,
                                                              const float* __restrict__ bc, const float* __restrict__ pe,
                                                              float* __restrict__ U, float* __restrict__ s0,
-                                                             float* __restrict__ qwk, int BT, int C) {
-    __shared__ float q[DM];
-    __shared__ float qs[DV];
+                                                             float* __restrict__ qwk, int BT, int C, int dk_, int dv_, float rsq) {
+    __shared__ float q[DM_MAX];
+    __shared__ float qs[DV_MAX];
     __shared__ float red[1024];
     __shared__ float k0;
-    const int tid = threadIdx.x, h = blockIdx.x;
-    if (tid < DM) {
+    const int dk = DKC ? DKC : dk_, dv = DVC ? DVC : dv_;
+    const int tid = threadIdx.x, h = blockIdx.x, nh = gridDim.x, dm = nh * dv;
+    if (tid < dm) {
         float v = 0.f;
 #pragma unroll
-        for (int d = 0; d < DK; ++d) v = fmaf(Q[h * DK + d], Wk[(size_t)(h * DK + d) * DM + tid], v);
-        v *= 0.5f;
+        for (int d = 0; d < dk; ++d) v = fmaf(Q[h * dk + d], Wk[(size_t)(h * dk + d) * dm + tid], v);
+        v *= rsq;
         q[tid] = v;
-        qwk[h * DM + tid] = v;
+        qwk[h * dm + tid] = v;
     }
     __syncthreads();
-    if (tid < DV) {
+    if (tid < dv) {
         float v = 0.f;
-        for (int i = 0; i < DM / DV; ++i) v += q[i * DV + tid];
+        for (int i = 0; i < nh; ++i) v += q[i * dv + tid];
         qs[tid] = v;
     }
     if (tid == 64) {
         float v = 0.f;
-        for (int m = 0; m < DM; ++m) v = fmaf(q[m], bc[m], v);
+        for (int m = 0; m < dm; ++m) v = fmaf(q[m], bc[m], v);
         float qb = 0.f;
-        for (int d = 0; d < DK; ++d) qb = fmaf(Q[h * DK + d], bk[h * DK + d], qb);
-        k0 = v + 0.5f * qb;
+        for (int d = 0; d < dk; ++d) qb = fmaf(Q[h * dk + d], bk[h * dk + d], qb);
+        k0 = v + rsq * qb;
     }
     // U[h][c] = sum_m q[m] Wc[m][c]: thread = (c, part); the parts (contiguous m ranges) are summed in order through LDS
-    const int parts = 1024 / C, mlen = (DM + parts - 1) / parts;
+    const int parts = 1024 / C, mlen = (dm + parts - 1) / parts;
     {
         const int c = tid % C, part = tid / C;
         float v = 0.f;
         if (part < parts) {
-            const int m0 = part * mlen, m1 = min(DM, m0 + mlen);
+            const int m0 = part * mlen, m1 = min(dm, m0 + mlen);
 #pragma unroll 8
             for (int m = m0; m < m1; ++m) v = fmaf(q[m], Wc[(size_t)m * C + c], v);
         }
@@ -1268,44 +1308,46 @@ __global__ __launch_bounds__(1024) void ltae_fold_fwd_kernel(const float* __rest
     for (int bt = tid; bt < BT; bt += 1024) {
         float v = k0;
 #pragma unroll
-        for (int j = 0; j < DV; ++j) v = fmaf(qs[j], pe[(size_t)bt * DV + j], v);
-        s0[bt * NH + h] = v;
+        for (int j = 0; j < dv; ++j) v = fmaf(qs[j], pe[(size_t)bt * dv + j], v);
+        s0[bt * nh + h] = v;
     }
 }
 
-// adjoint: given gU [16][C], gs0 [BT][16] and the attention kernel's direct d Wc / d bc (or NULL), writes the final
+// adjoint: given gU [nh][C], gs0 [BT][nh] and the attention kernel's direct d Wc / d bc (or NULL), writes the final
 // gradients of Q, fc1_k.weight, fc1_k.bias, inconv.weight, inconv.bias (accumulating where acc_* is set).
 // Three small launches (a single workgroup doing everything took 0.30 ms: serial, uncoalesced reads of Wc):
 //   1  S[h] = sum_bt gs0, P[h][j] = sum_bt gs0 pe         one wave per output, lanes over bt
-//   2  per m (one wave each): gq[h][m] = gU[h].Wc[m] + P[h][m%16] + S[h] bc[m]  (lanes over c: coalesced),
+//   2  per m (one wave each): gq[h][m] = gU[h].Wc[m] + P[h][m%dv] + S[h] bc[m]  (lanes over c: coalesced),
 //      d inconv.weight[m][:], d inconv.bias[m]
 //   3  per (h,d) (one wave each): d fc1_k.weight row, d fc1_k.bias, d Q (lanes over m)
 __global__ __launch_bounds__(64) void ltae_fold_bwd1_kernel(const float* __restrict__ gs0, const float* __restrict__ pe,
-                                                            float* __restrict__ SP, int BT) {
-    const int o = blockIdx.x, lane = threadIdx.x;      // o < 16: S[h]; else P[h][j]
+                                                            float* __restrict__ SP, int BT, int nh, int dv) {
+    const int o = blockIdx.x, lane = threadIdx.x;      // o < nh: S[h]; else P[h][j]
     float v = 0.f;
-    if (o < NH) {
-        for (int bt = lane; bt < BT; bt += 64) v += gs0[(size_t)bt * NH + o];
+    if (o < nh) {
+        for (int bt = lane; bt < BT; bt += 64) v += gs0[(size_t)bt * nh + o];
     } else {
-        const int h = (o - NH) / DV, j = (o - NH) % DV;
-        for (int bt = lane; bt < BT; bt += 64) v = fmaf(gs0[(size_t)bt * NH + h], pe[(size_t)bt * DV + j], v);
+        const int h = (o - nh) / dv, j = (o - nh) % dv;
+        for (int bt = lane; bt < BT; bt += 64) v = fmaf(gs0[(size_t)bt * nh + h], pe[(size_t)bt * dv + j], v);
     }
     v = wave_sum(v);
     if (lane == 0) SP[o] = v;
 }
 
+template <int NH, int DV>
 __global__ __launch_bounds__(64) void ltae_fold_bwd2_kernel(const float* __restrict__ Wc, const float* __restrict__ bc,
                                                             const float* __restrict__ qwk, const float* __restrict__ gU,
                                                             const float* __restrict__ SP, const float* __restrict__ gWc_attn,
                                                             const float* __restrict__ gbc_attn, float* __restrict__ gq,
                                                             float* __restrict__ gWc, float* __restrict__ gbc, int C,
                                                             int acc_wc, int acc_bc) {
+    constexpr int dm = NH * DV, dv = DV;
     const int m = blockIdx.x, lane = threadIdx.x;
     const float* S = SP;
     const float* P = SP + NH;
     float q[NH];
 #pragma unroll
-    for (int h = 0; h < NH; ++h) q[h] = qwk[h * DM + m];
+    for (int h = 0; h < NH; ++h) q[h] = qwk[h * dm + m];
     float dot[NH];
 #pragma unroll
     for (int h = 0; h < NH; ++h) dot[h] = 0.f;
@@ -1324,7 +1366,7 @@ __global__ __launch_bounds__(64) void ltae_fold_bwd2_kernel(const float* __restr
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
         const float d = wave_sum(dot[h]);
-        if (lane == 0) gq[h * DM + m] = d + fmaf(S[h], bc[m], P[h * DV + m % DV]);
+        if (lane == 0) gq[h * dm + m] = d + fmaf(S[h], bc[m], P[h * dv + m % dv]);
         vb = fmaf(q[h], S[h], vb);
     }
     if (lane == 0) gbc[m] = acc_bc ? gbc[m] + vb : vb;
@@ -1334,21 +1376,21 @@ __global__ __launch_bounds__(64) void ltae_fold_bwd3_kernel(const float* __restr
                                                             const float* __restrict__ bk, const float* __restrict__ gq,
                                                             const float* __restrict__ SP, float* __restrict__ gQ,
                                                             float* __restrict__ gWk, float* __restrict__ gbk, int acc_q,
-                                                            int acc_wk, int acc_bk) {
-    const int hd = blockIdx.x, h = hd / DK, lane = threadIdx.x;
+                                                            int acc_wk, int acc_bk, int dk, int dm, float rsq) {
+    const int hd = blockIdx.x, h = hd / dk, lane = threadIdx.x;
     const float qv = Q[hd], S = SP[h];
     float acc = 0.f;
-    for (int m = lane; m < DM; m += 64) {
-        const float g = gq[h * DM + m];
-        const float v = 0.5f * qv * g;
-        gWk[(size_t)hd * DM + m] = acc_wk ? gWk[(size_t)hd * DM + m] + v : v;
-        acc = fmaf(g, Wk[(size_t)hd * DM + m], acc);
+    for (int m = lane; m < dm; m += 64) {
+        const float g = gq[h * dm + m];
+        const float v = rsq * qv * g;
+        gWk[(size_t)hd * dm + m] = acc_wk ? gWk[(size_t)hd * dm + m] + v : v;
+        acc = fmaf(g, Wk[(size_t)hd * dm + m], acc);
     }
     acc = wave_sum(acc);
     if (lane == 0) {
-        const float vb = 0.5f * qv * S;
+        const float vb = rsq * qv * S;
         gbk[hd] = acc_bk ? gbk[hd] + vb : vb;
-        const float vq = 0.5f * (acc + bk[hd] * S);
+        const float vq = rsq * (acc + bk[hd] * S);
         gQ[hd] = acc_q ? gQ[hd] + vq : vq;
     }
 }
@@ -3335,18 +3377,22 @@ size_t lds_bwd_bytes(const c2s_ltae_desc* d) {
     return ((size_t)d->T * (d->C + 1) * 4 + (size_t)NH * d->C * 4 + 4 * (size_t)d->T * 64 + 1024 + 2 * (size_t)d->C + 128 + 1024 + 128) *
            sizeof(float);
 }
+// the 16-pixel forward / 8-pixel backward family: the carve-ups of ltae_fwd_kernel, ltae_bwd_heads_kernel, ltae_bwd_gx_kernel
 size_t fwd_lds(const c2s_ltae_desc* d) {
-    const size_t CH = d->C > 64 ? 64 : d->C;
-    return ((size_t)d->C * 32 + (size_t)d->T * 256 + 256 + NH * CH * 16) * 4;
+    const size_t CH = d->C > 64 ? 64 : d->C, nh = d->n_head;
+    return ((size_t)d->C * 32 + (size_t)d->T * nh * 16 + nh * 16 + nh * CH * 16) * 4;
 }
 size_t bwd1_lds(const c2s_ltae_desc* d) {
-    const size_t PT = BPT;
-    return ((size_t)d->C * 2 * PT + 256 * PT + NH * 32 * PT + 4 * (size_t)d->T * NH * PT + 2 * NH * PT) * 4;
+    const size_t PT = BPT, nh = d->n_head, dm = d->d_model;
+    return ((size_t)d->C * 2 * PT + dm * PT + nh * 32 * PT + 4 * (size_t)d->T * nh * PT + 2 * nh * PT) * 4;
 }
 size_t bwd2_lds(const c2s_ltae_desc* d) {
-    const size_t PT = BPT;
-    return (256 * PT + 2 * (size_t)d->T * NH * PT + (size_t)d->C * 4 * PT + NH * 4 * PT + (size_t)d->C * 8) * 4;
+    const size_t PT = BPT, nh = d->n_head, dm = d->d_model;
+    return (dm * PT + 2 * (size_t)d->T * nh * PT + (size_t)d->C * 4 * PT + nh * 4 * PT + (size_t)d->C * 8) * 4;
 }
+
+// (n_head, d_model) other than the 16 x 16 the full-resolution, LDS-resident and time-chunked families are laid out for
+bool other_heads(const c2s_ltae_desc* d) { return d->n_head != NH || d->d_model != NH * DV; }
 
 // A/B switches of the family choice (tests and tools set them in child processes), read once per process.  C2S_LTAE_LONG=1
 // sends every shape to the time-chunked family; =0 turns off: C2S_LTAE_LDS / C2S_LTAE_LDS_BWD the LDS-resident 4-pixel
@@ -3370,8 +3416,14 @@ bool long_series(const c2s_ltae_desc* d) { return ltae_switches().long_all || d-
 
 int check(const c2s_ltae_desc* d) {
     C2S_REQUIRE(d && d->B > 0 && d->T > 0 && d->C > 0 && d->HW > 0, "ltae: bad shape");
-    C2S_REQUIRE(d->n_head == NH && d->d_model == NH * DV, "ltae: only n_head=16, d_model=256 are built");
-    if (long_series(d)) {
+    C2S_REQUIRE((d->n_head == 8 || d->n_head == 16) && d->d_model % d->n_head == 0 &&
+                    (d->d_model / d->n_head == 8 || d->d_model / d->n_head == 16 || d->d_model / d->n_head == 32),
+                "ltae: n_head must be 8 or 16 and d_model / n_head 8, 16 or 32");
+    if (other_heads(d)) {       // the 16-pixel / 8-pixel tile family only
+        C2S_REQUIRE(d->T <= 64, "ltae: n_head, d_model other than 16, 256 take T <= 64");
+        C2S_REQUIRE(d->C % d->n_head == 0 && d->C / d->n_head <= 16, "ltae: C must be a multiple of n_head with C / n_head <= 16");
+        C2S_REQUIRE(bwd1_lds(d) <= 160 * 1024 && bwd2_lds(d) <= 160 * 1024 && fwd_lds(d) <= 160 * 1024, "ltae: T*C too large for the LDS tile");
+    } else if (long_series(d)) {
         C2S_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256, "ltae: the long-series kernels (T > 64) take C = 64, 128 or 256");
         C2S_REQUIRE((long)d->B * ((d->HW + LONG_PX - 1) / LONG_PX) < (1L << 31), "ltae: too many pixel tiles");
     } else {
@@ -3425,26 +3477,27 @@ struct LtaeBwdWs {
 };
 LtaeBwdWs ltae_bwd_ws(const c2s_ltae_desc* d, const LtaePlan& pl) {
     const size_t P = (size_t)d->B * d->HW, tiles4 = (size_t)d->B * ((d->HW + 3) / 4);
-    const size_t kmax = (size_t)d->B * d->T * NH > (size_t)NH * d->C ? (size_t)d->B * d->T * NH : (size_t)NH * d->C;
+    const size_t nh = d->n_head, dm = d->d_model;      // 16, 256 in the comment above
+    const size_t kmax = (size_t)d->B * d->T * nh > nh * d->C ? (size_t)d->B * d->T * nh : nh * d->C;
     LtaeBwdWs w = {};
-    w.V = w.GS + (size_t)NH * d->B * d->T * d->HW;
-    w.Z = w.V + (size_t)d->B * NH * d->C * d->HW;
-    w.part_s0 = w.Z + (size_t)d->B * NH * d->C * d->HW;
-    w.part_bc = w.part_s0 + tiles4 * d->T * NH;
-    w.part_gb = w.part_bc + tiles4 * 256;
+    w.V = w.GS + nh * d->B * d->T * d->HW;
+    w.Z = w.V + (size_t)d->B * nh * d->C * d->HW;
+    w.part_s0 = w.Z + (size_t)d->B * nh * d->C * d->HW;
+    w.part_bc = w.part_s0 + tiles4 * d->T * nh;
+    w.part_gb = w.part_bc + tiles4 * dm;
     w.rtmp = w.part_gb + tiles4 * d->C * 2;
-    w.total = w.rtmp + 2 + 2 * (size_t)RR_SLICES * (kmax > 256 ? kmax : 256);      // groups * RR_SLICES * K doubles, widest sum
+    w.total = w.rtmp + 2 + 2 * (size_t)RR_SLICES * (kmax > dm ? kmax : dm);      // groups * RR_SLICES * K doubles, widest sum
     size_t v = w.V;
     if (pl.bwd != BWD_TILE8 && pl.bwd != BWD_LDS4) {
         w.M = v;
-        v += P * NH * 2;
+        v += P * nh * 2;
     }
     if (pl.bwd == BWD_LONG) {
         w.ASG = v;
-        v += 2 * NH * P;
+        v += 2 * nh * P;
     }
     w.part_U = v;
-    w.part_wc = v + pl.tiles * NH * d->C;
+    w.part_wc = v + pl.tiles * nh * d->C;
     return w;
 }
 
@@ -3453,7 +3506,10 @@ LtaeBwdWs ltae_bwd_ws(const c2s_ltae_desc* d, const LtaePlan& pl) {
 LtaePlan ltae_plan(const c2s_ltae_desc* d, const LtaeCall& call) {
     const LtaeSwitches& sw = ltae_switches();
     LtaePlan pl = {};
-    if (long_series(d)) {
+    if (other_heads(d)) {      // before any other rule: only the tile family is instantiated for these head layouts
+        pl.fwd = FWD_TILE16;
+        pl.bwd = BWD_TILE8;
+    } else if (long_series(d)) {
         pl.fwd = FWD_LONG;
         pl.bwd = BWD_LONG;
     } else {
@@ -3522,8 +3578,44 @@ void fill(LtaeParams& p, const c2s_ltae_desc* d) {
     p.keepbits = (unsigned long long*)d->keep_bits;
 }
 
+// The tile family's instantiations: F(n_head, d_model / n_head) for the layout of a descriptor that passed check().
+#define C2S_LTAE_HEADS(d, F)                                  \
+    switch ((d)->n_head * 64 + (d)->d_model / (d)->n_head) {  \
+    case 8 * 64 + 8: F(8, 8); break;                          \
+    case 8 * 64 + 16: F(8, 16); break;                        \
+    case 8 * 64 + 32: F(8, 32); break;                        \
+    case 16 * 64 + 8: F(16, 8); break;                        \
+    case 16 * 64 + 32: F(16, 32); break;                      \
+    default: F(16, 16); break;                                \
+    }
+
+void launch_tile_fwd(const c2s_ltae_desc* d, const LtaeParams& p, hipStream_t st) {
+    const dim3 grid(d->B * ((d->HW + 15) / 16));
+#define F(H, D) hipLaunchKernelGGL((ltae_fwd_kernel<H, D>), grid, dim3(256), fwd_lds(d), st, p)
+    C2S_LTAE_HEADS(d, F)
+#undef F
+}
+void launch_tile_bwd_heads(const c2s_ltae_desc* d, const LtaeParams& p, dim3 tiles, hipStream_t st) {
+#define F(H, D) hipLaunchKernelGGL((ltae_bwd_heads_kernel<H, D>), tiles, dim3(256), bwd1_lds(d), st, p)
+    C2S_LTAE_HEADS(d, F)
+#undef F
+}
+template <bool GX>
+void launch_tile_bwd_gx(const c2s_ltae_desc* d, const LtaeParams& p, dim3 tiles, hipStream_t st) {
+#define F(H, D) hipLaunchKernelGGL((ltae_bwd_gx_kernel<GX, H, D>), tiles, dim3(256), bwd2_lds(d), st, p)
+    C2S_LTAE_HEADS(d, F)
+#undef F
+}
+
 void init_hook() {
-    C2S_RAISE_LDS(ltae_fwd_kernel);
+#define F(H, D)                                          \
+    C2S_RAISE_LDS((ltae_fwd_kernel<H, D>));              \
+    C2S_RAISE_LDS((ltae_bwd_heads_kernel<H, D>));        \
+    C2S_RAISE_LDS((ltae_bwd_gx_kernel<true, H, D>));     \
+    C2S_RAISE_LDS((ltae_bwd_gx_kernel<false, H, D>))
+    F(8, 8); F(8, 16); F(8, 32); F(16, 8); F(16, 32);
+#undef F
+    C2S_RAISE_LDS(ltae_fwd_kernel<>);
     C2S_RAISE_LDS(ltae_lds_fwd_kernel<64>);
     C2S_RAISE_LDS(ltae_lds_fwd_kernel<128>);
     C2S_RAISE_LDS(ltae_lds_fwd_kernel<256>);
@@ -3533,7 +3625,7 @@ void init_hook() {
     C2S_RAISE_LDS((ltae_lds_bwd_kernel<64, false>));
     C2S_RAISE_LDS((ltae_lds_bwd_kernel<128, false>));
     C2S_RAISE_LDS((ltae_lds_bwd_kernel<256, false>));
-    C2S_RAISE_LDS(ltae_bwd_heads_kernel);
+    C2S_RAISE_LDS(ltae_bwd_heads_kernel<>);
     C2S_RAISE_LDS(ltae_bwd_gx_kernel<true>);
     C2S_RAISE_LDS(ltae_bwd_gx_kernel<false>);
     C2S_RAISE_LDS(ltae_stream_bwd_heads_kernel<4>);
@@ -3642,7 +3734,7 @@ extern "C" int c2s_ltae_attn_fwd_ws(const c2s_ltae_desc* d, const float* x, cons
         return C2S_OK;
     }
     case FWD_TILE16:
-        hipLaunchKernelGGL(ltae_fwd_kernel, dim3(d->B * ((d->HW + 15) / 16)), dim3(256), fwd_lds(d), st, p);
+        launch_tile_fwd(d, p, st);
         C2S_CHECK_LAUNCH("ltae_fwd");
         return C2S_OK;
     }
@@ -3740,7 +3832,7 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
         break;
     }
     case BWD_TILE8:
-        hipLaunchKernelGGL(ltae_bwd_heads_kernel, tiles, dim3(256), bwd1_lds(d), st, p);
+        launch_tile_bwd_heads(d, p, tiles, st);
         C2S_CHECK_LAUNCH("ltae_bwd_heads");
         break;
     }
@@ -3759,24 +3851,25 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
         break;
     }
     case DX_TILE8:
-        if (gx != nullptr) hipLaunchKernelGGL(ltae_bwd_gx_kernel<true>, tiles, dim3(256), bwd2_lds(d), st, p);
-        else hipLaunchKernelGGL(ltae_bwd_gx_kernel<false>, tiles, dim3(256), bwd2_lds(d), st, p);
+        if (gx != nullptr) launch_tile_bwd_gx<true>(d, p, tiles, st);
+        else launch_tile_bwd_gx<false>(d, p, tiles, st);
         C2S_CHECK_LAUNCH("ltae_bwd_gx");
         break;
     case DX_NONE: case DX_FUSED:
         break;
     }
     // reductions
-    reduce_rows(p.part_s0, gs0, d->B, (d->HW + pl.px - 1) / pl.px, d->T * NH, rtmp, st);      // gs0[b][t][h]: the tiles of b
+    const int nh = d->n_head, dm = d->d_model;
+    reduce_rows(p.part_s0, gs0, d->B, (d->HW + pl.px - 1) / pl.px, d->T * nh, rtmp, st);      // gs0[b][t][h]: the tiles of b
     C2S_CHECK_LAUNCH("ltae_reduce_s0");
-    reduce_rows(p.part_bc, gbc, 1, (int)pl.tiles, 256, rtmp, st);
+    reduce_rows(p.part_bc, gbc, 1, (int)pl.tiles, dm, rtmp, st);
     C2S_CHECK_LAUNCH("ltae_reduce_bc");
     if (call.gb) {   // interleaved (dgamma, dbeta) partials -> the two outputs
         reduce_rows(p.part_gb, ggamma, 1, pl.gb_tiles, 2 * d->C, rtmp, st, gbeta);
         C2S_CHECK_LAUNCH("ltae_reduce_gb");
     }
-    if (pl.gU_rows) reduce_rows(part_U, gU, 1, (int)pl.tiles, NH * d->C, rtmp, st);
-    else hipLaunchKernelGGL(sum_over_pixels_kernel, dim3(NH * d->C), dim3(64), 0, st, p.V, gU, d->B, NH * d->C, d->HW);
+    if (pl.gU_rows) reduce_rows(part_U, gU, 1, (int)pl.tiles, nh * d->C, rtmp, st);
+    else hipLaunchKernelGGL(sum_over_pixels_kernel, dim3(nh * d->C), dim3(64), 0, st, p.V, gU, d->B, nh * d->C, d->HW);
     C2S_CHECK_LAUNCH("ltae_gU");
     switch (pl.gwc) {
     case GWC_MFMA: {
@@ -3788,55 +3881,111 @@ extern "C" int c2s_ltae_attn_bwd(const c2s_ltae_desc* d, const float* x, const f
         C2S_CHECK_LAUNCH("ltae_gWc_reduce");
         break;
     }
-    case GWC_DIRECT:
-        hipLaunchKernelGGL(gwc_kernel, dim3(NH * d->C), dim3(256), 0, st, g_emb, p.Z, gWc, d->B, d->C, d->HW);
+    case GWC_DIRECT: {
+#define F(H, D) hipLaunchKernelGGL((gwc_kernel<H, D>), dim3(nh * d->C), dim3(256), 0, st, g_emb, p.Z, gWc, d->B, d->C, d->HW)
+        C2S_LTAE_HEADS(d, F)
+#undef F
         C2S_CHECK_LAUNCH("ltae_gWc");
         break;
+    }
     case GWC_ZERO:
-        hipMemsetAsync(gWc, 0, (size_t)256 * d->C * sizeof(float), st);
+        hipMemsetAsync(gWc, 0, (size_t)dm * d->C * sizeof(float), st);
         break;
     }
     return C2S_OK;
 }
 
-extern "C" int c2s_positional_table(const long long* dates, float* pe, long n, float period, void* stream) {
-    C2S_REQUIRE(dates && pe && n > 0 && period > 0.f, "positional_table: bad args");
-    hipLaunchKernelGGL(positional_table_kernel, dim3(cdiv(n * DV, 256)), dim3(256), 0, (hipStream_t)stream, dates, pe, n, period);
+extern "C" int c2s_positional_table_ex(const long long* dates, float* pe, long n, float period, int d_v, void* stream) {
+    C2S_REQUIRE(dates && pe && n > 0 && period > 0.f && d_v > 0, "positional_table: bad args");
+    hipLaunchKernelGGL(positional_table_kernel, dim3(cdiv(n * d_v, 256)), dim3(256), 0, (hipStream_t)stream, dates, pe, n, period, d_v);
     C2S_CHECK_LAUNCH("positional_table");
+    return C2S_OK;
+}
+
+extern "C" int c2s_positional_table(const long long* dates, float* pe, long n, float period, void* stream) {
+    return c2s_positional_table_ex(dates, pe, n, period, DV, stream);
+}
+
+namespace {
+// the head layouts of the fold: those of check(), and a key width the query row of a wave-sized block covers
+int fold_check(int n_head, int d_k, int d_model) {
+    C2S_REQUIRE((n_head == 8 || n_head == 16) && d_model > 0 && d_model % n_head == 0 &&
+                    (d_model / n_head == 8 || d_model / n_head == 16 || d_model / n_head == 32),
+                "ltae_fold: n_head must be 8 or 16 and d_model / n_head 8, 16 or 32");
+    C2S_REQUIRE(d_k >= 1 && d_k <= DK_MAX, "ltae_fold: d_k must be in 1..32");
+    return C2S_OK;
+}
+}  // namespace
+
+extern "C" int c2s_ltae_fold_fwd_ex(const float* Q, const float* Wk, const float* bk, const float* Wc, const float* bc,
+                                    const float* pe, float* U, float* s0, float* qwk, int BT, int C, int n_head, int d_k,
+                                    int d_model, void* stream) {
+    C2S_REQUIRE(Q && Wk && bk && Wc && bc && pe && U && s0 && qwk && BT > 0 && C > 0, "ltae_fold_fwd: bad args");
+    C2S_REQUIRE(C <= 1024, "ltae_fold_fwd: C > 1024");
+    if (int rc = fold_check(n_head, d_k, d_model)) return rc;
+    const float rsq = (float)(1.0 / sqrt((double)d_k));
+    if (d_k == 4 && d_model == n_head * DV)
+        hipLaunchKernelGGL((ltae_fold_fwd_kernel<4, DV>), dim3(n_head), dim3(1024), 0, (hipStream_t)stream, Q, Wk, bk, Wc, bc, pe, U,
+                           s0, qwk, BT, C, d_k, DV, rsq);
+    else
+        hipLaunchKernelGGL((ltae_fold_fwd_kernel<0, 0>), dim3(n_head), dim3(1024), 0, (hipStream_t)stream, Q, Wk, bk, Wc, bc, pe, U,
+                           s0, qwk, BT, C, d_k, d_model / n_head, rsq);
+    C2S_CHECK_LAUNCH("ltae_fold_fwd");
     return C2S_OK;
 }
 
 extern "C" int c2s_ltae_fold_fwd(const float* Q, const float* Wk, const float* bk, const float* Wc, const float* bc,
                                  const float* pe, float* U, float* s0, float* qwk, int BT, int C, void* stream) {
-    C2S_REQUIRE(Q && Wk && bk && Wc && bc && pe && U && s0 && qwk && BT > 0 && C > 0, "ltae_fold_fwd: bad args");
-    C2S_REQUIRE(C <= 1024, "ltae_fold_fwd: C > 1024");
-    hipLaunchKernelGGL(ltae_fold_fwd_kernel, dim3(NH), dim3(1024), 0, (hipStream_t)stream, Q, Wk, bk, Wc, bc, pe, U, s0, qwk, BT, C);
-    C2S_CHECK_LAUNCH("ltae_fold_fwd");
-    return C2S_OK;
+    return c2s_ltae_fold_fwd_ex(Q, Wk, bk, Wc, bc, pe, U, s0, qwk, BT, C, NH, 4, NH * DV, stream);
 }
 
-extern "C" size_t c2s_ltae_fold_bwd_workspace_floats(void) { return (size_t)NH + NH * DV + NH * DM; }
+// S [n_head] | P [n_head][d_v] | gq [n_head][d_model]
+extern "C" size_t c2s_ltae_fold_bwd_workspace_floats_ex(int n_head, int d_model) {
+    if (n_head <= 0 || d_model <= 0) return 0;
+    return (size_t)n_head + d_model + (size_t)n_head * d_model;
+}
+
+extern "C" size_t c2s_ltae_fold_bwd_workspace_floats(void) { return c2s_ltae_fold_bwd_workspace_floats_ex(NH, NH * DV); }
+
+extern "C" int c2s_ltae_fold_bwd_ex(const float* Q, const float* Wk, const float* bk, const float* Wc, const float* bc,
+                                    const float* pe, const float* qwk, const float* gU, const float* gs0,
+                                    const float* gWc_attn, const float* gbc_attn, float* gQ, float* gWk, float* gbk,
+                                    float* gWc, float* gbc, int BT, int C, int n_head, int d_k, int d_model, int acc_mask,
+                                    float* workspace, size_t ws_floats, void* stream) {
+    C2S_REQUIRE(Q && Wk && bk && Wc && bc && pe && qwk && gU && gs0 && gQ && gWk && gbk && gWc && gbc && workspace && BT > 0 &&
+                    C > 0, "ltae_fold_bwd: bad args");
+    if (int rc = fold_check(n_head, d_k, d_model)) return rc;
+    C2S_REQUIRE(ws_floats >= c2s_ltae_fold_bwd_workspace_floats_ex(n_head, d_model), "ltae_fold_bwd: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int d_v = d_model / n_head;
+    const float rsq = (float)(1.0 / sqrt((double)d_k));
+    float* SP = workspace;                           // S [n_head] | P [n_head][d_v]
+    float* gq = workspace + n_head + d_model;        // [n_head][d_model]
+    hipLaunchKernelGGL(ltae_fold_bwd1_kernel, dim3(n_head + d_model), dim3(64), 0, st, gs0, pe, SP, BT, n_head, d_v);
+    C2S_CHECK_LAUNCH("ltae_fold_bwd1");
+    switch (n_head * 64 + d_v) {
+#define F(H, D)                                                                                                                 \
+    case H * 64 + D:                                                                                                            \
+        hipLaunchKernelGGL((ltae_fold_bwd2_kernel<H, D>), dim3(d_model), dim3(64), 0, st, Wc, bc, qwk, gU, SP, gWc_attn, gbc_attn, \
+                           gq, gWc, gbc, C, (acc_mask >> 3) & 1, (acc_mask >> 4) & 1);                                          \
+        break
+        F(8, 8); F(8, 16); F(8, 32); F(16, 8); F(16, 16); F(16, 32);
+#undef F
+    }
+    C2S_CHECK_LAUNCH("ltae_fold_bwd2");
+    hipLaunchKernelGGL(ltae_fold_bwd3_kernel, dim3(n_head * d_k), dim3(64), 0, st, Q, Wk, bk, gq, SP, gQ, gWk, gbk, acc_mask & 1,
+                       (acc_mask >> 1) & 1, (acc_mask >> 2) & 1, d_k, d_model, rsq);
+    C2S_CHECK_LAUNCH("ltae_fold_bwd3");
+    return C2S_OK;
+}
 
 extern "C" int c2s_ltae_fold_bwd(const float* Q, const float* Wk, const float* bk, const float* Wc, const float* bc,
                                  const float* pe, const float* qwk, const float* gU, const float* gs0,
                                  const float* gWc_attn, const float* gbc_attn, float* gQ, float* gWk, float* gbk,
                                  float* gWc, float* gbc, int BT, int C, int acc_mask, float* workspace, size_t ws_floats,
                                  void* stream) {
-    C2S_REQUIRE(Q && Wk && bk && Wc && bc && pe && qwk && gU && gs0 && gQ && gWk && gbk && gWc && gbc && workspace && BT > 0 &&
-                    C > 0, "ltae_fold_bwd: bad args");
-    C2S_REQUIRE(ws_floats >= c2s_ltae_fold_bwd_workspace_floats(), "ltae_fold_bwd: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    float* SP = workspace;                    // S [16] | P [16][16]
-    float* gq = workspace + NH + NH * DV;     // [16][256]
-    hipLaunchKernelGGL(ltae_fold_bwd1_kernel, dim3(NH + NH * DV), dim3(64), 0, st, gs0, pe, SP, BT);
-    C2S_CHECK_LAUNCH("ltae_fold_bwd1");
-    hipLaunchKernelGGL(ltae_fold_bwd2_kernel, dim3(DM), dim3(64), 0, st, Wc, bc, qwk, gU, SP, gWc_attn, gbc_attn, gq, gWc, gbc, C,
-                       (acc_mask >> 3) & 1, (acc_mask >> 4) & 1);
-    C2S_CHECK_LAUNCH("ltae_fold_bwd2");
-    hipLaunchKernelGGL(ltae_fold_bwd3_kernel, dim3(NH * DK), dim3(64), 0, st, Q, Wk, bk, gq, SP, gQ, gWk, gbk, acc_mask & 1,
-                       (acc_mask >> 1) & 1, (acc_mask >> 2) & 1);
-    C2S_CHECK_LAUNCH("ltae_fold_bwd3");
-    return C2S_OK;
+    return c2s_ltae_fold_bwd_ex(Q, Wk, bk, Wc, bc, pe, qwk, gU, gs0, gWc_attn, gbc_attn, gQ, gWk, gbk, gWc, gbc, BT, C, NH, 4,
+                                NH * DV, acc_mask, workspace, ws_floats, stream);
 }
 
 extern "C" int c2s_pixel_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats, int B,

@@ -132,22 +132,22 @@ __global__ __launch_bounds__(256) void pe_grad_kernel(const float* __restrict__ 
     }
 }
 
-// pe part of the key fold's adjoint: P[h][m] = sum_bt gs0[bt,h] pe[bt,m];  gWk[4h+d][m] += Q[4h+d] P[m] / 2,
-// gQ[4h+d] += sum_m P[m] Wk[4h+d][m] / 2.   One block per head, thread = m.
+// pe part of the key fold's adjoint, rsq = 1/sqrt(dk): P[h][m] = sum_bt gs0[bt,h] pe[bt,m];  gWk[dk*h+d][m] += rsq Q[dk*h+d] P[m],
+// gQ[dk*h+d] += rsq sum_m P[m] Wk[dk*h+d][m].   One block per head, thread = m.
 __global__ __launch_bounds__(256) void pe_fold_adj_kernel(const float* __restrict__ Q, const float* __restrict__ Wk,
                                                           const float* __restrict__ gs0, const float* __restrict__ pe,
-                                                          float* __restrict__ gWk, float* __restrict__ gQ, int BT) {
+                                                          float* __restrict__ gWk, float* __restrict__ gQ, int BT, int dk, float rsq) {
     __shared__ float red[4];
     const int h = blockIdx.x, m = threadIdx.x, lane = m & 63, wave = m >> 6;
     float P = 0.f;
     for (int bt = 0; bt < BT; ++bt) P = fmaf(gs0[(size_t)bt * NH + h], pe[(size_t)bt * DM + m], P);
-    for (int d = 0; d < DK; ++d) {
-        const int hd = h * DK + d;
-        gWk[(size_t)hd * DM + m] += 0.5f * Q[hd] * P;
+    for (int d = 0; d < dk; ++d) {
+        const int hd = h * dk + d;
+        gWk[(size_t)hd * DM + m] += rsq * Q[hd] * P;
         const float v = wave_sum(P * Wk[(size_t)hd * DM + m]);
         if (lane == 0) red[wave] = v;
         __syncthreads();
-        if (m == 0) gQ[hd] += 0.5f * ((red[0] + red[1]) + (red[2] + red[3]));
+        if (m == 0) gQ[hd] += rsq * ((red[0] + red[1]) + (red[2] + red[3]));
         __syncthreads();
     }
 }
@@ -243,10 +243,11 @@ extern "C" int c2s_ltae_pe_gattn(const float* g_emb, const float* pe, const floa
     return C2S_OK;
 }
 
-extern "C" int c2s_ltae_pe_bwd(int mode, const long long* dates0, const long long* dates1, const float* Q, const float* Wk,
-                               const float* qwk, const float* pe, const float* sin256, const float* attn, const float* g_emb,
-                               const float* gs0, float* g_pe, float* gWk, float* gQ, float* gW, float* gb, int B, int T, int HW,
-                               void* stream) {
+extern "C" int c2s_ltae_pe_bwd_ex(int mode, const long long* dates0, const long long* dates1, const float* Q, const float* Wk,
+                                  const float* qwk, const float* pe, const float* sin256, const float* attn, const float* g_emb,
+                                  const float* gs0, float* g_pe, float* gWk, float* gQ, float* gW, float* gb, int B, int T, int HW,
+                                  int d_k, void* stream) {
+    C2S_REQUIRE(d_k >= 1 && d_k <= 32, "ltae_pe_bwd: d_k must be in 1..32");
     C2S_REQUIRE(mode >= 1 && mode <= 3 && dates0 && Q && Wk && qwk && pe && attn && gs0 && g_pe && gWk && gQ && gW && gb,
                 "ltae_pe_bwd: null pointer");
     C2S_REQUIRE(mode != 2 || dates1, "ltae_pe_bwd: abs_rel needs the day-of-year dates");
@@ -255,10 +256,19 @@ extern "C" int c2s_ltae_pe_bwd(int mode, const long long* dates0, const long lon
     const int BT = B * T;
     hipLaunchKernelGGL(pe_grad_kernel, dim3(BT * NH), dim3(256), 0, st, attn, g_emb, gs0, qwk, g_pe, B, T, HW);
     C2S_CHECK_LAUNCH("ltae_pe_grad");
-    hipLaunchKernelGGL(pe_fold_adj_kernel, dim3(NH), dim3(256), 0, st, Q, Wk, gs0, pe, gWk, gQ, BT);
+    hipLaunchKernelGGL(pe_fold_adj_kernel, dim3(NH), dim3(256), 0, st, Q, Wk, gs0, pe, gWk, gQ, BT, d_k,
+                       (float)(1.0 / sqrt((double)d_k)));
     C2S_CHECK_LAUNCH("ltae_pe_fold_adj");
     if (mode == 3) hipLaunchKernelGGL(pe_lin_bwd_kernel, dim3(DM), dim3(256), 0, st, g_pe, sin256, gW, gb, BT);
     else hipLaunchKernelGGL(pe_abs_bwd_kernel, dim3(DV), dim3(384), 0, st, mode == 1 ? dates0 : dates1, g_pe, gW, gb, BT);
     C2S_CHECK_LAUNCH("ltae_pe_param_bwd");
     return C2S_OK;
+}
+
+extern "C" int c2s_ltae_pe_bwd(int mode, const long long* dates0, const long long* dates1, const float* Q, const float* Wk,
+                               const float* qwk, const float* pe, const float* sin256, const float* attn, const float* g_emb,
+                               const float* gs0, float* g_pe, float* gWk, float* gQ, float* gW, float* gb, int B, int T, int HW,
+                               void* stream) {
+    return c2s_ltae_pe_bwd_ex(mode, dates0, dates1, Q, Wk, qwk, pe, sin256, attn, g_emb, gs0, g_pe, gWk, gQ, gW, gb, B, T, HW, DK,
+                              stream);
 }

@@ -1088,11 +1088,10 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
 # L-TAE
 # =================================================================================================
 def positional_table(dates: Tensor, d: int, period: float) -> Tensor:
-    """[B,T] int days -> [B,T,16] sinusoid table (reference positional_encoding.py:16-33)."""
-    assert d == 16, "the kernels are built for d_model / n_head = 16"
+    """[B,T] int days -> [B,T,d] sinusoid table, d = d_model / n_head (reference positional_encoding.py:16-33)."""
     dl = dates.to(torch.int64).contiguous()
     pe = torch.empty(*dl.shape, d, device=dl.device, dtype=torch.float32)
-    check(lib().c2s_positional_table(dl.data_ptr(), pe.data_ptr(), dl.numel(), float(period), _stream()), "positional_table")
+    check(lib().c2s_positional_table_ex(dl.data_ptr(), pe.data_ptr(), dl.numel(), float(period), d, _stream()), "positional_table")
     return pe
 
 
@@ -1120,15 +1119,17 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
     Wc3 = ctx.p[prefix + ".inconv.weight"]
     bc = ctx.p[prefix + ".inconv.bias"]
     gamma, beta = ctx.p[prefix + ".in_norm.weight"], ctx.p[prefix + ".in_norm.bias"]
-    assert n_head == 16 and d_k == 4 and d_model == 256, "the fold kernels are built for n_head=16, d_k=4, d_model=256"
     mode = PE_MODES[pe_mode]
+    if mode != 0 and (n_head, d_model) != (16, 256):
+        raise NotImplementedError("crop2seg_amd: the learnable positional encoders (csrc/ltae_pe.hip) are built for n_head=16, "
+                                  f"d_model=256; got n_head={n_head}, d_model={d_model}")
     dev = x5.device
     pe256 = sin256 = d0 = d1 = None
     if mode == 0:
         pe = positional_table(dates, d_model // n_head, period)
     else:
-        pe = ctx.ws.get("ltae_pe_zero", B * T * 16)
-        check(lib().c2s_fill(pe.data_ptr(), B * T * 16, 0.0, _stream()), "fill")
+        pe = ctx.ws.get("ltae_pe_zero", B * T * (d_model // n_head))
+        check(lib().c2s_fill(pe.data_ptr(), B * T * (d_model // n_head), 0.0, _stream()), "fill")
         dl = dates.to(torch.int64)
         two = mode in (2, 4, 5)                      # dates [B,T,2]: (relative date, day of year)
         kmode = {4: 1, 5: 3}.get(mode, mode)         # the table kernel's mode for the first encoder
@@ -1147,12 +1148,13 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         if enc2 is not None:
             check(lib().c2s_ltae_pe_abs_add(d1.data_ptr(), ctx.p[enc2 + ".weight"].data_ptr(), ctx.p[enc2 + ".bias"].data_ptr(),
                                             pe256.data_ptr(), bad.data_ptr(), B * T, _stream()), "ltae_pe_abs_add")
-    # parameter-only fold: U [16,C], s0 [B,T,16]; qwk is kept for the adjoint
+    # parameter-only fold: U [n_head,C], s0 [B,T,n_head]; qwk is kept for the adjoint
     U = torch.empty(n_head, Cc, device=dev, dtype=torch.float32)
     s0 = torch.empty(B, T, n_head, device=dev, dtype=torch.float32)
     qwk = torch.empty(n_head, d_model, device=dev, dtype=torch.float32)
-    check(lib().c2s_ltae_fold_fwd(Q.data_ptr(), Wk.data_ptr(), bk.data_ptr(), Wc3.data_ptr(), bc.data_ptr(), pe.data_ptr(),
-                                  U.data_ptr(), s0.data_ptr(), qwk.data_ptr(), B * T, Cc, _stream()), "ltae_fold_fwd")
+    check(lib().c2s_ltae_fold_fwd_ex(Q.data_ptr(), Wk.data_ptr(), bk.data_ptr(), Wc3.data_ptr(), bc.data_ptr(), pe.data_ptr(),
+                                     U.data_ptr(), s0.data_ptr(), qwk.data_ptr(), B * T, Cc, n_head, d_k, d_model, _stream()),
+          "ltae_fold_fwd")
     if mode != 0:
         check(lib().c2s_ltae_pe_fwd(qwk.data_ptr(), pe256.data_ptr(), None, s0.data_ptr(), None, B, T, HW, 0, _stream()),
               "ltae_pe_fwd")
@@ -1259,20 +1261,20 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
         # adjoint of the parameter fold: final gradients of Q, fc1_k, inconv in one launch (frozen ones into scratch)
         sinks = [ctx.grad_sink(nme) if ctx.trains(nme) else (torch.empty_like(ctx.p[nme]), 0) for nme in fold_names]
         acc_mask = sum((1 << i) for i, (_, acc) in enumerate(sinks) if acc)
-        fbw = ctx.ws.get("ltae_fold_bwd", lib().c2s_ltae_fold_bwd_workspace_floats())
-        check(lib().c2s_ltae_fold_bwd(Q.data_ptr(), Wk.data_ptr(), bk.data_ptr(), Wc3.data_ptr(), bc.data_ptr(), pe.data_ptr(),
-                                      qwk.data_ptr(), gU.data_ptr(), gs0.data_ptr(),
-                                      gWc.data_ptr() if emb is not None else None, gbc.data_ptr() if emb is not None else None,
-                                      *[t.data_ptr() for t, _ in sinks], B * T, Cc, acc_mask, fbw.data_ptr(), fbw.numel(),
-                                      _stream()), "ltae_fold_bwd")
+        fbw = ctx.ws.get("ltae_fold_bwd", lib().c2s_ltae_fold_bwd_workspace_floats_ex(n_head, d_model))
+        check(lib().c2s_ltae_fold_bwd_ex(Q.data_ptr(), Wk.data_ptr(), bk.data_ptr(), Wc3.data_ptr(), bc.data_ptr(), pe.data_ptr(),
+                                         qwk.data_ptr(), gU.data_ptr(), gs0.data_ptr(),
+                                         gWc.data_ptr() if emb is not None else None, gbc.data_ptr() if emb is not None else None,
+                                         *[t.data_ptr() for t, _ in sinks], B * T, Cc, n_head, d_k, d_model, acc_mask,
+                                         fbw.data_ptr(), fbw.numel(), _stream()), "ltae_fold_bwd")
         if mode != 0:
             g_pe = torch.empty(B, T, d_model, device=dev, dtype=torch.float32)
             gW = sink(enc + ".weight")
             gb = sink(enc + ".bias")
-            check(lib().c2s_ltae_pe_bwd(kmode, d0.data_ptr(), _ptr(d1), Q.data_ptr(), Wk.data_ptr(), qwk.data_ptr(),
-                                        pe256.data_ptr(), _ptr(sin256), attn.data_ptr(), _ptr(g_emb), gs0.data_ptr(),
-                                        g_pe.data_ptr(), sinks[1][0].data_ptr(), sinks[0][0].data_ptr(), gW.data_ptr(),
-                                        gb.data_ptr(), B, T, HW, _stream()), "ltae_pe_bwd")
+            check(lib().c2s_ltae_pe_bwd_ex(kmode, d0.data_ptr(), _ptr(d1), Q.data_ptr(), Wk.data_ptr(), qwk.data_ptr(),
+                                           pe256.data_ptr(), _ptr(sin256), attn.data_ptr(), _ptr(g_emb), gs0.data_ptr(),
+                                           g_pe.data_ptr(), sinks[1][0].data_ptr(), sinks[0][0].data_ptr(), gW.data_ptr(),
+                                           gb.data_ptr(), B, T, HW, d_k, _stream()), "ltae_pe_bwd")
             if enc2 is not None:
                 gW2 = sink(enc2 + ".weight")
                 gb2 = sink(enc2 + ".bias")

@@ -386,7 +386,9 @@ int c2s_frame_flags(const float* x, int* valid, int N, long frame_elems, float p
  * ------------------------------------------------------------------------------------------------ */
 typedef struct c2s_ltae_desc {
     int B, T, C, HW;      /* HW = h*w pixels per frame at the L-TAE resolution */
-    int n_head, d_model;  /* built for 16 / 256 */
+    int n_head, d_model;  /* n_head 8 or 16, d_model / n_head 8, 16 or 32; the shapes in the comments are those of 16 / 256.  Other
+                             pairs than 16 / 256 run the 16-pixel / 8-pixel family (paths 0 / 0) at every map size: C % n_head
+                             == 0, C / n_head <= 16, T <= 64, attn never optional */
     float eps;
     float dropout_p;      /* 0 => no dropout */
     uint64_t seed;        /* dropout RNG key */
@@ -461,6 +463,17 @@ int c2s_ltae_fold_bwd(const float* Q, const float* Wk, const float* bk, const fl
                       float* gQ, float* gWk, float* gbk, float* gWc, float* gbc, int BT, int C, int acc_mask,
                       float* workspace, size_t ws_floats, void* stream);
 size_t c2s_ltae_fold_bwd_workspace_floats(void);
+/* The same for n_head in {8, 16}, d_model / n_head = d_v in {8, 16, 32} and d_k in 1..32 (tae.py:355-449): Q [n_head,1,d_k],
+ * Wk [n_head*d_k, d_model], bk [n_head*d_k], Wc [d_model,C], bc [d_model], pe [BT,d_v]; U [n_head,C], s0 [BT,n_head],
+ * qwk [n_head,d_model]; the scores scale by 1/sqrt(d_k).  The entry points above are these at 16 / 4 / 256. */
+int c2s_positional_table_ex(const long long* dates, float* pe, long n, float period, int d_v, void* stream);
+int c2s_ltae_fold_fwd_ex(const float* Q, const float* Wk, const float* bk, const float* Wc, const float* bc, const float* pe,
+                         float* U, float* s0, float* qwk, int BT, int C, int n_head, int d_k, int d_model, void* stream);
+int c2s_ltae_fold_bwd_ex(const float* Q, const float* Wk, const float* bk, const float* Wc, const float* bc, const float* pe,
+                         const float* qwk, const float* gU, const float* gs0, const float* gWc_attn, const float* gbc_attn,
+                         float* gQ, float* gWk, float* gbk, float* gWc, float* gbc, int BT, int C, int n_head, int d_k,
+                         int d_model, int acc_mask, float* workspace, size_t ws_floats, void* stream);
+size_t c2s_ltae_fold_bwd_workspace_floats_ex(int n_head, int d_model);
 
 /* Learnable positional encoders of the L-TAE (constructor flags use_doy / use_abs_rel_enc / add_linear: tae.py:404-430,
  * 467-479; positional_encoding.py:7-73).  The attention kernels above keep running with a ZERO table pe[BT,16]; the general
@@ -490,6 +503,12 @@ int c2s_ltae_pe_bwd(int mode, const long long* dates0, const long long* dates1, 
                     const float* qwk, const float* pe256, const float* sin256, const float* attn, const float* g_emb,
                     const float* gs0, float* g_pe, float* gWk, float* gQ, float* gW, float* gb, int B, int T, int HW,
                     void* stream);
+/* c2s_ltae_pe_bwd for a key width d_k in 1..32 (Q [16,1,d_k], Wk / gWk [16*d_k,256]); c2s_ltae_pe_bwd is this at d_k = 4.  The
+ * other entry points of this group never see d_k: they work from qwk. */
+int c2s_ltae_pe_bwd_ex(int mode, const long long* dates0, const long long* dates1, const float* Q, const float* Wk,
+                       const float* qwk, const float* pe256, const float* sin256, const float* attn, const float* g_emb,
+                       const float* gs0, float* g_pe, float* gWk, float* gQ, float* gW, float* gb, int B, int T, int HW,
+                       int d_k, void* stream);
 
 /* L-TAE tail (tae.py:442-449,486-488).  Linear(256,C') is a 1x1 convolution on the NCHW embedding
  * (c2s_conv_igemm), BatchNorm1d over P is c2s_norm_* with kind BATCH; the two pieces below are the rest:
