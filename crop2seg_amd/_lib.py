@@ -167,6 +167,11 @@ SIGNATURES = {
     "c2s_collate_series": (I, [P, I, P, P, P, P, P, I, I, I, I, I, C.POINTER(I), C.POINTER(F), C.POINTER(F), F, P]),
     "c2s_collate_series_ndvi": (I, [P, I, P, P, P, P, P, I, I, I, I, I, C.POINTER(I), C.POINTER(F), C.POINTER(F), F, I, I, P]),
     "c2s_softmax_stitch": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),
+    "c2s_window_count": (I, [I, I, I]),
+    "c2s_window_origin": (I, [I, I, I, I]),
+    "c2s_cut_windows": (I, [P, P, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(F), P]),
+    "c2s_softmax_blend": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+    "c2s_blend_finish": (I, [P, P, P, I, I, I, P]),
     "c2s_adam_flat": (I, [P, P, P, P, L, F, F, F, F, I, P, F, P]),
     "c2s_grad_sumsq_workspace_doubles": (SZ, []),
     "c2s_grad_sumsq": (I, [P, P, P, I, L, P, SZ, P, P]),

@@ -8,6 +8,9 @@
 //  * c2s_softmax_stitch : tiled-inference tail, src/webapp/prediction.py:310-333: Softmax(dim=1) of every patch's logits,
 //    top-1 class, the einops re-tiling '(h w) c h1 w1 -> c (h h1) (w w1)' and the crop to 1098 x 1098, written straight
 //    into the tile rasters.
+//  * c2s_cut_windows / c2s_softmax_blend / c2s_blend_finish : the same tail for a whole raster series predicted on
+//    overlapping windows (inference.predict_raster; no counterpart in the reference): windows cut out of the series on the
+//    device, their softmax blended into the raster with a taper by a per-pixel gather, normalised and arg-maxed in place.
 //
 // Both are HBM/PCIe-bound byte movers (no reuse): the collate kernel reads each source element once with 16-byte lanes
 // (8-byte for 16-bit sources) and writes 16-byte lanes; padding frames are written as zeros by the same grid.
@@ -122,7 +125,213 @@ __global__ __launch_bounds__(256) void softmax_stitch_kernel(const float* __rest
     }
 }
 
+// ---------------------------------------------------------------- overlapped sliding windows over a whole raster
+// Window placement along one axis (include/c2s_hip.h): the ONE statement of it, used by the exported host functions, by
+// the launch code and by the kernels.
+__host__ __device__ __forceinline__ int win_count(int size, int patch, int stride) {
+    return size <= patch ? 1 : (size - patch + stride - 1) / stride + 1;
+}
+__host__ __device__ __forceinline__ int win_origin(int i, int size, int patch, int stride) {
+    const long long o = (long long)i * stride, last = size > patch ? size - patch : 0;
+    return (int)(o < last ? o : last);                                  // the last window is clamped to the raster edge
+}
+
+struct CutParams {
+    const float* series;        // [T][C][H][W]
+    float* x;                   // [nwin][T][C][ph][pw]
+    int T, C, H, W, ph, pw, sy, sx, nx, first, nwin, flip;
+    float fill[16];             // per channel, where the raster is smaller than a window
+};
+
+// Every thread writes 4 consecutive pixels of a window row (one 16-byte store: pw % 8 == 0) from 4 dword loads: a raster
+// row starts at any 4-byte boundary, and under flip & 1 the lanes read their row backwards.  Grid-stride over the quads.
+__global__ __launch_bounds__(256) void cut_windows_kernel(CutParams p) {
+    const int qw = p.pw >> 2;
+    const size_t total = (size_t)p.nwin * p.T * p.C * p.ph * qw;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        size_t r = e;
+        const int xq = (int)(r % qw); r /= qw;
+        const int y1 = (int)(r % p.ph); r /= p.ph;
+        const int c = (int)(r % p.C); r /= p.C;
+        const int t = (int)(r % p.T);
+        const int w = p.first + (int)(r / p.T);
+        const int oy = win_origin(w / p.nx, p.H, p.ph, p.sy), ox = win_origin(w % p.nx, p.W, p.pw, p.sx);
+        const int sy = oy + ((p.flip & 2) ? p.ph - 1 - y1 : y1);
+        const float fv = p.fill[c];
+        float o[4] = {fv, fv, fv, fv};
+        if (sy < p.H) {
+            const float* row = p.series + (((size_t)t * p.C + c) * p.H + sy) * p.W;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x1 = xq * 4 + j;
+                const int sx = ox + ((p.flip & 1) ? p.pw - 1 - x1 : x1);
+                if (sx < p.W) o[j] = row[sx];
+            }
+        }
+        reinterpret_cast<float4*>(p.x)[e] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// Gather: one thread owns one raster pixel of the rows [y0, y0 + rows) that the batch's windows touch, and visits the
+// covering windows of [first, first + nwin) in ascending index; the softmax arithmetic is softmax_stitch_kernel's.  The K
+// running sums live in registers (KMAX: the instantiation that holds K); __fmul_rn / __fadd_rn keep the sum one fixed
+// left-to-right expression of separate multiplies and adds.
+template <int KMAX>
+__global__ __launch_bounds__(256) void softmax_blend_kernel(const float* __restrict__ logits, float* __restrict__ acc,
+                                                            float* __restrict__ wsum, const float* __restrict__ ty,
+                                                            const float* __restrict__ tx, int first, int nwin, int K, int ph,
+                                                            int pw, int H, int W, int sy, int sx, int flip, int ny, int nx,
+                                                            int y0, int rows) {
+    const size_t total = (size_t)rows * W, hw = (size_t)H * W, cs = (size_t)ph * pw;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int y = y0 + (int)(e / W), x = (int)(e % W);
+        const size_t pix = (size_t)y * W + x;
+        // unclamped window i covers y iff i * stride <= y < i * stride + patch; the clamped last window lies lower, never
+        // below its neighbour, so the scan starts at the first unclamped candidate and stops at the first origin past y
+        const int iy0 = y >= ph ? (y - ph) / sy + 1 : 0, ix0 = x >= pw ? (x - pw) / sx + 1 : 0;
+        float a[KMAX];
+        float ws = 0.f;
+        bool any = false;
+        for (int iy = iy0; iy < ny; ++iy) {
+            const int oy = win_origin(iy, H, ph, sy);
+            if (oy > y) break;
+            if (y - oy >= ph) continue;
+            for (int ix = ix0; ix < nx; ++ix) {
+                const int ox = win_origin(ix, W, pw, sx);
+                if (ox > x) break;
+                if (x - ox >= pw) continue;
+                const int wi = iy * nx + ix - first;
+                if (wi < 0 || wi >= nwin) continue;
+                if (!any) {
+                    any = true;
+                    ws = wsum[pix];
+#pragma unroll
+                    for (int k = 0; k < KMAX; ++k)
+                        if (k < K) a[k] = acc[k * hw + pix];
+                }
+                const int y1 = y - oy, x1 = x - ox;
+                const int ly = (flip & 2) ? ph - 1 - y1 : y1, lx = (flip & 1) ? pw - 1 - x1 : x1;   // un-mirror the pass
+                const float* lp = logits + ((size_t)wi * K * ph + ly) * pw + lx;
+                float l[KMAX];
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k)
+                    if (k < K) l[k] = lp[k * cs];
+                float mx = l[0];
+#pragma unroll
+                for (int k = 1; k < KMAX; ++k)
+                    if (k < K) mx = fmaxf(mx, l[k]);
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k)
+                    if (k < K) s += expf(l[k] - mx);
+                const float w = (ty || tx) ? __fmul_rn(ty ? ty[y1] : 1.f, tx ? tx[x1] : 1.f) : 1.f;
+#pragma unroll
+                for (int k = 0; k < KMAX; ++k)
+                    if (k < K) a[k] = __fadd_rn(a[k], __fmul_rn(w, expf(l[k] - mx) / s));
+                ws = __fadd_rn(ws, w);
+            }
+        }
+        if (!any) continue;                                             // no window of this batch covers the pixel
+        wsum[pix] = ws;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) acc[k * hw + pix] = a[k];
+    }
+}
+
+// acc / wsum in place (IEEE divide) and the first maximum of the probabilities, as softmax_stitch_kernel picks it.
+__global__ __launch_bounds__(256) void blend_finish_kernel(float* __restrict__ acc, const float* __restrict__ wsum,
+                                                           long long* __restrict__ top1, int K, size_t hw) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < hw; e += (size_t)gridDim.x * 256) {
+        const float s = wsum[e];
+        float best = -1.f;
+        int arg = 0;
+        for (int k = 0; k < K; ++k) {
+            const float pk = __fdiv_rn(acc[k * hw + e], s);
+            acc[k * hw + e] = pk;
+            if (pk > best) { best = pk; arg = k; }
+        }
+        if (top1) top1[e] = arg;
+    }
+}
+
+int mover_blocks(size_t items) {
+    size_t b = (items + 255) / 256;
+    return (int)(b > 2048 ? 2048 : (b ? b : 1));
+}
+
+bool window_args_ok(int size, int patch, int stride) { return size >= 1 && patch >= 1 && stride >= 1 && stride <= patch; }
+
 }  // namespace
+
+extern "C" int c2s_window_count(int size, int patch, int stride) {
+    C2S_REQUIRE(window_args_ok(size, patch, stride), "window_count: need size >= 1 and 1 <= stride <= patch");
+    return win_count(size, patch, stride);
+}
+
+extern "C" int c2s_window_origin(int i, int size, int patch, int stride) {
+    C2S_REQUIRE(window_args_ok(size, patch, stride), "window_origin: need size >= 1 and 1 <= stride <= patch");
+    C2S_REQUIRE(i >= 0 && i < win_count(size, patch, stride), "window_origin: window index %d out of range", i);
+    return win_origin(i, size, patch, stride);
+}
+
+extern "C" int c2s_cut_windows(const float* series, float* x, int T, int C, int H, int W, int ph, int pw, int stride_y,
+                               int stride_x, int first_window, int nwin, int flip, const float* host_fill, void* stream) {
+    C2S_REQUIRE(series && x, "cut_windows: null pointer");
+    C2S_REQUIRE(T > 0 && C > 0 && C <= 16 && H > 0 && W > 0, "cut_windows: bad shape (T, H, W >= 1, 1 <= C <= 16)");
+    C2S_REQUIRE(ph >= 16 && pw >= 16 && ph % 8 == 0 && pw % 8 == 0, "cut_windows: window sides must be multiples of 8, >= 16");
+    C2S_REQUIRE(stride_y >= 1 && stride_y <= ph && stride_x >= 1 && stride_x <= pw, "cut_windows: need 1 <= stride <= patch");
+    C2S_REQUIRE(flip >= 0 && flip <= 3, "cut_windows: flip is a mask of 1 (x) and 2 (y)");
+    const int ny = win_count(H, ph, stride_y), nx = win_count(W, pw, stride_x);
+    C2S_REQUIRE(first_window >= 0 && nwin > 0 && (long long)first_window + nwin <= (long long)ny * nx,
+                "cut_windows: windows [%d, %d + %d) outside the %d x %d grid", first_window, first_window, nwin, ny, nx);
+    CutParams p = {};
+    p.series = series; p.x = x; p.T = T; p.C = C; p.H = H; p.W = W; p.ph = ph; p.pw = pw; p.sy = stride_y; p.sx = stride_x;
+    p.nx = nx; p.first = first_window; p.nwin = nwin; p.flip = flip;
+    for (int c = 0; c < C; ++c) p.fill[c] = host_fill ? host_fill[c] : 0.f;
+    const size_t quads = (size_t)nwin * T * C * ph * (pw / 4);
+    hipLaunchKernelGGL(cut_windows_kernel, dim3(mover_blocks(quads)), dim3(256), 0, (hipStream_t)stream, p);
+    C2S_CHECK_LAUNCH("cut_windows");
+    return C2S_OK;
+}
+
+extern "C" int c2s_softmax_blend(const float* logits, float* acc, float* wsum, const float* wy, const float* wx,
+                                 int first_window, int nwin, int K, int ph, int pw, int H, int W, int stride_y, int stride_x,
+                                 int flip, void* stream) {
+    C2S_REQUIRE(logits && acc && wsum, "softmax_blend: null pointer");
+    C2S_REQUIRE(K >= 1 && K <= 32, "softmax_blend: need 1 <= K <= 32");
+    C2S_REQUIRE(ph > 0 && pw > 0 && H > 0 && W > 0, "softmax_blend: bad shape");
+    C2S_REQUIRE(stride_y >= 1 && stride_y <= ph && stride_x >= 1 && stride_x <= pw, "softmax_blend: need 1 <= stride <= patch");
+    C2S_REQUIRE(flip >= 0 && flip <= 3, "softmax_blend: flip is a mask of 1 (x) and 2 (y)");
+    const int ny = win_count(H, ph, stride_y), nx = win_count(W, pw, stride_x);
+    C2S_REQUIRE(first_window >= 0 && nwin > 0 && (long long)first_window + nwin <= (long long)ny * nx,
+                "softmax_blend: windows [%d, %d + %d) outside the %d x %d grid", first_window, first_window, nwin, ny, nx);
+    const int y0 = win_origin(first_window / nx, H, ph, stride_y);
+    int y1 = win_origin((first_window + nwin - 1) / nx, H, ph, stride_y) + ph;
+    if (y1 > H) y1 = H;
+    const int rows = y1 - y0;
+    const dim3 grid(mover_blocks((size_t)rows * W)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define C2S_BLEND(KM)                                                                                                     \
+    hipLaunchKernelGGL(softmax_blend_kernel<KM>, grid, block, 0, st, logits, acc, wsum, wy, wx, first_window, nwin, K, ph, \
+                       pw, H, W, stride_y, stride_x, flip, ny, nx, y0, rows)
+    if (K <= 8) C2S_BLEND(8);
+    else if (K <= 16) C2S_BLEND(16);
+    else if (K <= 24) C2S_BLEND(24);
+    else C2S_BLEND(32);
+#undef C2S_BLEND
+    C2S_CHECK_LAUNCH("softmax_blend");
+    return C2S_OK;
+}
+
+extern "C" int c2s_blend_finish(float* acc_proba, const float* wsum, long long* top1, int K, int H, int W, void* stream) {
+    C2S_REQUIRE(acc_proba && wsum, "blend_finish: null pointer");
+    C2S_REQUIRE(K >= 1 && H > 0 && W > 0, "blend_finish: bad shape");
+    const size_t hw = (size_t)H * W;
+    hipLaunchKernelGGL(blend_finish_kernel, dim3(mover_blocks(hw)), dim3(256), 0, (hipStream_t)stream, acc_proba, wsum, top1, K, hw);
+    C2S_CHECK_LAUNCH("blend_finish");
+    return C2S_OK;
+}
 
 extern "C" int c2s_collate_series(const void* src, int src_dtype, const long long* offsets, const long long* src_dates,
                                   float* x, long long* dates, int* valid, int B, int T, int C, int Cs, int HW,

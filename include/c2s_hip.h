@@ -746,6 +746,34 @@ int c2s_collate_series_ndvi(const void* src, int src_dtype, const long long* off
 int c2s_softmax_stitch(const float* logits, float* proba, long long* top1, int first_patch, int npatch, int K, int ph,
                        int pw, int grid_w, int out_h, int out_w, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Overlapped sliding-window inference over a whole raster, blended on the device (inference.predict_raster).
+ *   Window placement, per axis, from size (raster extent), patch and stride with 1 <= stride <= patch:
+ *     n = 1 if size <= patch, else ceil((size - patch) / stride) + 1;    origin(i) = min(i * stride, max(size - patch, 0)):
+ *     the last window is clamped to the raster edge, every pixel is covered, by at most ceil(patch / stride) + 1 windows
+ *     per axis.  Windows are numbered row-major, w = wy * nx + wx.  c2s_window_count / c2s_window_origin are host-only and
+ *     are the placement the two kernels use; bad arguments (or i outside [0, n)) return a negative value.
+ *   c2s_cut_windows: series [T,C,H,W] f32 (any H, W >= 1) -> x [nwin,T,C,ph,pw] for windows first_window .. + nwin - 1:
+ *     x[w,t,c,y1,x1] = series[t,c,oy + y1',ox + x1'],  y1' = ph-1-y1 when flip & 2, x1' = pw-1-x1 when flip & 1; a source
+ *     position outside the raster (only when H < ph or W < pw) takes host_fill[c] (host array of C floats, NULL = 0).
+ *     C <= 16; ph, pw multiples of 8, >= 16.
+ *   c2s_softmax_blend: logits [nwin,K,ph,pw] of the batch cut with the same flip -> acc [K,H,W] += w * softmax, wsum [H,W]
+ *     += w, w = wy[y1] * wx[x1] at the un-mirrored in-window position (device tables; NULL = exactly 1.0f).  A gather: one
+ *     thread per raster pixel of the rows the batch touches visits the covering windows of the batch in ascending index and
+ *     stores once; mx = max, s = sum expf(l - mx), p_k = expf(l_k - mx) / s as c2s_softmax_stitch, then separate IEEE
+ *     multiply and add.  No atomics: launches on one stream give every pixel one fixed sequence of additions, whatever the
+ *     batch size.  acc and wsum start at 0 (c2s_fill); pixels no window of the batch covers are not written.  K <= 32.
+ *   c2s_blend_finish: in place proba_k = acc_k / wsum (IEEE divide); top1 [H,W] int64 = first maximum of the
+ *     probabilities (may be NULL).
+ * ------------------------------------------------------------------------------------------------ */
+int c2s_window_count(int size, int patch, int stride);
+int c2s_window_origin(int i, int size, int patch, int stride);
+int c2s_cut_windows(const float* series, float* x, int T, int C, int H, int W, int ph, int pw, int stride_y, int stride_x,
+                    int first_window, int nwin, int flip, const float* host_fill, void* stream);
+int c2s_softmax_blend(const float* logits, float* acc, float* wsum, const float* wy, const float* wx, int first_window,
+                      int nwin, int K, int ph, int pw, int H, int W, int stride_y, int stride_x, int flip, void* stream);
+int c2s_blend_finish(float* acc_proba, const float* wsum, long long* top1, int K, int H, int W, void* stream);
+
 /* elementwise helpers */
 int c2s_fill(float* p, long n, float v, void* stream);
 int c2s_add_inplace(float* dst, const float* src, long n, void* stream);

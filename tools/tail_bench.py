@@ -3,6 +3,7 @@
 HIP-event time per call and algorithmic bytes / time against the 8 TB/s HBM peak.
 Usage (GPU box): python tools/tail_bench.py [--reps 20]"""
 import argparse
+import math
 import os
 import sys
 
@@ -107,6 +108,63 @@ def main():
                                             torch.cuda.current_stream().cuda_stream), "softmax_stitch")
     ms = timed(stitch, a.reps)
     line("N3 c2s_softmax_stitch, 100 patches -> 1098^2", ms, 100 * K * H * H * 4 + K * 1098 * 1098 * 4 + 1098 * 1098 * 8)
+    del lg, probs, top1
+
+    # N3, whole raster: 1098^2, T = 60, 12 x 12 overlapping windows of 128 every 96 pixels, K = 20, batches of 20 windows
+    import crop2seg_amd as C2S
+    from crop2seg_amd.inference import predict_raster, window_origins
+    R, T, Kr, P, S, BS = 1098, 60, 20, 128, 96, 20
+    oys = window_origins(R, P, S)
+    nwin = len(oys) ** 2
+    stream = torch.cuda.current_stream().cuda_stream
+    series = torch.randn(T, 10, R, R, device=dev)
+    xb = torch.empty(BS, T, 10, P, P, device=dev)
+
+    def cut():
+        for first in range(0, nwin, BS):
+            _lib.check(L.c2s_cut_windows(series.data_ptr(), xb.data_ptr(), T, 10, R, R, P, P, S, S, first, min(BS, nwin - first), 0,
+                                         None, stream), "cut_windows")
+    ms = timed(cut, max(3, a.reps // 4))
+    line(f"N3 c2s_cut_windows, {nwin} windows of 1098^2 T=60", ms, series.numel() * 4 + nwin * xb[0].numel() * 4,
+         "(raster read once + windows written)")
+
+    lg = torch.randn(BS, Kr, P, P, device=dev)
+    acc = torch.empty(Kr, R, R, device=dev)
+    wsum = torch.empty(R, R, device=dev)
+    top1 = torch.empty(R, R, dtype=torch.int64, device=dev)
+    hann = torch.sin(math.pi * (torch.arange(P, dtype=torch.float64) + 0.5) / P).pow(2).float().to(dev)
+    moved = (Kr + 1) * R * R * 4 + Kr * R * R * 4 + R * R * 8           # finish: acc, wsum in; proba, top1 out
+    for first in range(0, nwin, BS):
+        n = min(BS, nwin - first)
+        rows = min(oys[(first + n - 1) // len(oys)] + P, R) - oys[first // len(oys)]
+        moved += n * Kr * P * P * 4 + 2 * rows * R * (Kr + 1) * 4      # logits in; the batch's rows of acc / wsum in and out
+
+    def blend():
+        for first in range(0, nwin, BS):
+            _lib.check(L.c2s_softmax_blend(lg.data_ptr(), acc.data_ptr(), wsum.data_ptr(), hann.data_ptr(), hann.data_ptr(), first,
+                                           min(BS, nwin - first), Kr, P, P, R, R, S, S, 0, stream), "softmax_blend")
+        _lib.check(L.c2s_blend_finish(acc.data_ptr(), wsum.data_ptr(), top1.data_ptr(), Kr, R, R, stream), "blend_finish")
+    _lib.check(L.c2s_fill(acc.data_ptr(), acc.numel(), 0.0, stream), "fill")
+    _lib.check(L.c2s_fill(wsum.data_ptr(), wsum.numel(), 0.0, stream), "fill")     # the repeats keep adding: values stay finite
+    ms = timed(blend, a.reps)
+    line(f"N3 c2s_softmax_blend + c2s_blend_finish, {nwin} windows", ms, moved, "(rows of acc / wsum re-read per batch)")
+    del lg, acc, wsum, top1, xb
+
+    net = C2S.TimeUNet_v1(input_dim=10, out_conv=[32, Kr]).cuda()
+    net.apply(C2S.weight_init)
+    net.eval()
+    dates1 = 5 * torch.arange(T, device=dev)
+    ms_r = timed(lambda: predict_raster(net, series, dates1, patch=P, stride=S, batch_size=BS), 3)
+    padded = torch.zeros(T, 10, 10 * P, 10 * P, device=dev)             # dataset_creator pads 1098 -> 1280 with zeros
+    padded[:, :, :R, :R] = series
+    tiles = padded.view(T, 10, 10, P, 10, P).permute(2, 4, 0, 1, 3, 5).reshape(100, T, 10, P, P).contiguous()
+    del padded
+    ms_t = timed(lambda: predict_tile(net, tiles, dates1[None].repeat(100, 1), batch_size=BS), 3)
+    print(f"{'N3 predict_raster 1098^2 stride 96 (' + str(nwin) + ' windows)':44s} {ms_r:9.1f} ms   predict_tile (100 patches) "
+          f"{ms_t:9.1f} ms   ratio {ms_r / ms_t:5.2f} (windows alone: {nwin / 100:4.2f})")
+    # batches of 20 leave a last batch of 4 windows; 24 divides 144
+    ms_24 = timed(lambda: predict_raster(net, series, dates1, patch=P, stride=S, batch_size=24), 3)
+    print(f"{'N3 predict_raster, batch_size 24 (6 full batches)':44s} {ms_24:9.1f} ms   ratio {ms_24 / ms_t:5.2f}")
 
 
 if __name__ == "__main__":
