@@ -164,6 +164,8 @@ SIGNATURES = {
     "c2s_label_components": (I, [P, P, P, I, I, I, I, P, SZ, P, P]),
     "c2s_parcel_vote_workspace_bytes": (SZ, [I, I, I]),
     "c2s_parcel_vote": (I, [P, P, P, P, I, I, I, I, I, F, I, P, SZ, P, P]),
+    "c2s_parcel_soft_vote_workspace_bytes": (SZ, [I, I, I]),
+    "c2s_parcel_soft_vote": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, SZ, P, P]),
     "c2s_collate_series": (I, [P, I, P, P, P, P, P, I, I, I, I, I, C.POINTER(I), C.POINTER(F), C.POINTER(F), F, P]),
     "c2s_collate_series_ndvi": (I, [P, I, P, P, P, P, P, I, I, I, I, I, C.POINTER(I), C.POINTER(F), C.POINTER(F), F, I, I, P]),
     "c2s_softmax_stitch": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),

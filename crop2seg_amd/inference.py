@@ -30,13 +30,17 @@ Tensor = torch.Tensor
 
 @torch.no_grad()
 def predict_tile(model, x: Tensor, dates: Tensor, grid: int = 10, crop: int = 1098, batch_size: int = 10,
-                 parcels: Optional[Tensor] = None, boundary_homogenize: bool = False, boundary_code: int = 15):
+                 parcels: Optional[Tensor] = None, boundary_homogenize: bool = False, boundary_code: int = 15,
+                 parcel_mode: str = "hard", parcel_cap: Optional[int] = None):
     """x [grid*grid, T, C, h1, w1] (patches in row-major tile order, as the reference's test loader yields them), dates
     [grid*grid, T] -> (proba [K, crop, crop] f32, top1 [crop, crop] int64) on the device.
     With `parcels` ([crop, crop] parcel ids of the tile, 0 = no parcel) or `boundary_homogenize` a third element follows: the
     tile raster homogenised per parcel ([crop, crop] int64), as the web app does (crop2seg.py:335-371): by the given
     parcels (postprocess.homogenize), or by the parcels that the boundary class `boundary_code` of the stitched
-    probabilities outlines (postprocess.homogenize_boundaries)."""
+    probabilities outlines (postprocess.homogenize_boundaries).  parcel_mode 'hard' votes with the top-1 pixels of every
+    parcel, 'soft' with the mean of the returned probabilities over it (homogenize(type_='soft')); `parcel_cap` (the largest
+    parcel id) goes to either vote as `cap`, so that a whole tile does not need a table of crop * crop rows."""
+    _check_parcel_mode("predict_tile", parcel_mode, parcel_cap)
     if not x.is_cuda:
         raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
     if parcels is not None and boundary_homogenize:
@@ -65,9 +69,24 @@ def predict_tile(model, x: Tensor, dates: Tensor, grid: int = 10, crop: int = 10
     finally:
         model.train(was_training)
     model.check_health()                 # one host synchronisation per tile: a failed normalisation wait must not reach a map
+    return _with_homogenised(proba, top1, parcels, boundary_homogenize, boundary_code, parcel_mode, parcel_cap)
+
+
+def _check_parcel_mode(who: str, parcel_mode: str, parcel_cap: Optional[int]) -> None:
+    if parcel_mode not in ("hard", "soft"):
+        raise ValueError(f"{who}: parcel_mode is 'hard' or 'soft', got {parcel_mode!r}")
+    if parcel_cap is not None and (isinstance(parcel_cap, bool) or not isinstance(parcel_cap, int) or parcel_cap < 1):
+        raise ValueError(f"{who}: parcel_cap is an int >= 1 (the largest parcel id), got {parcel_cap!r}")
+
+
+def _with_homogenised(proba: Tensor, top1: Tensor, parcels: Optional[Tensor], boundary_homogenize: bool, boundary_code: int,
+                      parcel_mode: str, parcel_cap: Optional[int]):
+    """(proba, top1), followed by the homogenised raster where the caller asked for one."""
     if parcels is not None:
         from .postprocess import homogenize
-        return proba, top1, homogenize(top1, parcels, proba.shape[0])
+        if parcel_mode == "soft":
+            return proba, top1, homogenize(proba, parcels, proba.shape[0], cap=parcel_cap, type_="soft", from_logits=False)
+        return proba, top1, homogenize(top1, parcels, proba.shape[0], cap=parcel_cap)
     if boundary_homogenize:
         from .postprocess import homogenize_boundaries
         return proba, top1, homogenize_boundaries(proba, boundary_code=boundary_code, from_logits=False)
@@ -112,7 +131,8 @@ def taper(window: str, patch: int) -> Optional[Tensor]:
 def predict_raster(model, series: Tensor, dates: Tensor, patch: Union[int, Tuple[int, int]] = 128,
                    stride: Union[int, Tuple[int, int]] = 96, window: str = "hann", batch_size: int = 20,
                    flips: Sequence[str] = ("",), fill: Union[float, Sequence[float]] = 0.0, parcels: Optional[Tensor] = None,
-                   boundary_homogenize: bool = False, boundary_code: int = 15):
+                   boundary_homogenize: bool = False, boundary_code: int = 15, parcel_mode: str = "hard",
+                   parcel_cap: Optional[int] = None):
     """series [T, C, H, W] f32 on the device (one collated raster series, any H and W), dates [T] int64 ->
     (proba [K, H, W] f32, top1 [H, W] int64): the model run on overlapping `patch` windows every `stride` pixels (the last
     window of an axis clamped to the raster edge), the windows' softmax blended with the `window` taper and, for every entry
@@ -121,7 +141,9 @@ def predict_raster(model, series: Tensor, dates: Tensor, patch: Union[int, Tuple
     into the accumulators, c2s_blend_finish normalises and takes the top-1 class; nothing leaves HBM.  The passes run flips
     outer, window batches inner, and the blend is a gather in ascending window index, so the result does not depend on
     `batch_size`, bit for bit.  `fill` (a float or one per channel) is what a window reads beyond a raster smaller than
-    itself.  `parcels` / `boundary_homogenize` append the homogenised raster exactly as in predict_tile."""
+    itself.  `parcels` / `boundary_homogenize` / `parcel_mode` / `parcel_cap` append the homogenised raster exactly as
+    in predict_tile."""
+    _check_parcel_mode("predict_raster", parcel_mode, parcel_cap)
     if parcels is not None and boundary_homogenize:
         raise ValueError("predict_raster: give `parcels` or `boundary_homogenize`, not both")
     if series.dim() != 4 or series.dtype != torch.float32:
@@ -187,10 +209,4 @@ def predict_raster(model, series: Tensor, dates: Tensor, patch: Union[int, Tuple
         model.train(was_training)
     model.check_health()                 # one host synchronisation per raster, as predict_tile
     proba = acc                          # the accumulator itself, finished in place
-    if parcels is not None:
-        from .postprocess import homogenize
-        return proba, top1, homogenize(top1, parcels, proba.shape[0])
-    if boundary_homogenize:
-        from .postprocess import homogenize_boundaries
-        return proba, top1, homogenize_boundaries(proba, boundary_code=boundary_code, from_logits=False)
-    return proba, top1
+    return _with_homogenised(proba, top1, parcels, boundary_homogenize, boundary_code, parcel_mode, parcel_cap)

@@ -199,12 +199,16 @@ class StepMeters:
         return self.iou_boundary.get_miou_acc()
 
     def update(self, out: Tensor, y: Tensor, loss: Optional[Tensor] = None, want_pred: bool = False,
-               parcels: Optional[Tensor] = None):
+               parcels: Optional[Tensor] = None, parcel_mode: str = "hard"):
         """out [B,K,H,W] f32 logits, y [B,H,W] int64, loss: 1-element device tensor.  Returns (pred, pred_top2) int64
         [B,H,W] when want_pred, else None.
         parcels [B,H,W] (a rasterised parcel id map, 0 = no parcel): the top-1 prediction is homogenised per parcel before
         the IoU meter sees it, as iterate() does under --get_affine (utils.py:341-361,383; postprocess.homogenize); the top-2
-        and the loss meter are fed as without it, and `pred` is then the homogenised prediction."""
+        and the loss meter are fed as without it, and `pred` is then the homogenised prediction.  parcel_mode 'soft': the
+        parcels vote with the mean of their pixels' softmax instead (homogenize(out, parcels, K, type_='soft'), the call
+        iterate() carries commented out, utils.py:354-360)."""
+        if parcel_mode not in ("hard", "soft"):
+            raise ValueError(f"parcel_mode is 'hard' or 'soft', got {parcel_mode!r}")
         _require_hip(out, "out")
         B, K = out.shape[:2]
         assert K == self.num_classes and out.dtype == torch.float32
@@ -221,7 +225,8 @@ class StepMeters:
                                        pred2.data_ptr() if want_pred else None, B, K, HW, _stream()), "metrics_update")
         if parcels is not None:
             from ..postprocess import homogenize
-            pred = homogenize(pred, parcels, K)
+            pred = (homogenize(pred, parcels, K) if parcel_mode == "hard" else
+                    homogenize(out, parcels, K, type_="soft", from_logits=True))
             check(lib().c2s_confusion_add(pred.data_ptr(), y.data_ptr(), self.iou.conf_metric.conf.data_ptr(), y.numel(), K,
                                           _stream()), "confusion_add")
         if loss is not None:

@@ -4,7 +4,16 @@ src/helpers/postprocess.py:377-604 (`homogenize`, `homogenize_boundaries`), whic
 
 A parcel is a set of pixels with one integer id, an area is a pixel count.  The vector side of the reference's helpers
 (shapefiles, CRS, polygonisation, rasterising an LPIS layer) stays with the caller, who supplies the id raster
-(DESIGN.md section 7).  Everything here only enqueues HIP kernels (csrc/parcels.hip) on the current stream; `check_errors`
+(DESIGN.md section 7).
+
+`homogenize` has both label types of the reference.  'hard' (`parcel_vote`) counts arg-max pixels per parcel.  'soft'
+(`parcel_soft_vote`) restates `soften` (:238-281) and the rasterisation of its `soft_label` (:491-507): the per-parcel mean of
+the K class probabilities over the pixels inside the parcel, the class of the largest mean, the runner-up
+(`soft_top2_label`) and the rule that a parcel becomes background only above a mean background probability of 0.7.  What
+`soften` does with geometry (the spatial join of pixel centres with polygons, CRS, the merge back into the vector layer)
+stays with the caller, who rasterises the parcels and gets the per-parcel table back to write as attributes.
+
+Everything here only enqueues HIP kernels (csrc/parcels.hip) on the current stream; `check_errors`
 is the one call that synchronises.  Inputs must be HIP tensors: there is no CPU fallback.  [H,W] rasters are taken as B = 1.
 """
 from __future__ import annotations
@@ -17,7 +26,7 @@ from ._lib import check, lib
 
 Tensor = torch.Tensor
 
-_ERRORS = {}        # device -> int32 [4]: iteration-cap flag | labels outside [0,cap] | classes outside [0,K) | unused
+_ERRORS = {}        # device -> int32 [4]: iteration-cap flag | labels outside [0,cap] | classes outside [0,K) | non-finite scores
 
 
 def _stream() -> int:
@@ -41,13 +50,23 @@ def _errors(device) -> Tensor:
 def check_errors(device="cuda") -> Tuple[int, int]:
     """The one host-synchronising reader of the device error words.  Raises when a union-find loop of `label_components`
     hit its iteration cap (memory was damaged: the labels of that call are not to be trusted); returns
-    (labels outside [0,cap], classes outside [0,K)) that `parcel_vote` skipped since the last call, and clears all three."""
+    (labels outside [0,cap], classes outside [0,K)) that `parcel_vote` / `parcel_soft_vote` skipped since the last call, and
+    clears these three words (not the count that `nonfinite_scores` reads)."""
     err = _errors(device)
     cap_hit, skipped, bad, _ = err.tolist()
-    err.zero_()
+    err[:3].zero_()
     if cap_hit:
         raise RuntimeError("crop2seg_amd.postprocess: a union-find loop of label_components hit its iteration cap")
     return skipped, bad
+
+
+def nonfinite_scores(device="cuda") -> int:
+    """Parcel pixels that `parcel_soft_vote` left out of their parcel's mean since the last call because one of their scores
+    was NaN or infinite; clears the count (and nothing else).  Synchronises, like `check_errors`."""
+    err = _errors(device)
+    n = int(err[3].item())
+    err[3:].zero_()
+    return n
 
 
 def _batched(t: Tensor, dims: int) -> Tuple[Tensor, bool]:
@@ -144,11 +163,75 @@ def parcel_vote(pred: Tensor, labels: Tensor, num_classes: int, bg_share: Option
     return (out[0], parcel_class[0]) if squeezed else (out, parcel_class)
 
 
+def _check_soft_args(scores: Tensor, labels: Tensor, bg_mean, outside: str, cap: Optional[int]):
+    """The argument checks of the soft vote: they need no device."""
+    if outside not in ("zero", "keep"):
+        raise ValueError("outside is 'zero' or 'keep'")
+    if bg_mean is None or float(bg_mean) != float(bg_mean):
+        raise ValueError("bg_mean is a number (the reference's 0.7), not None or NaN")
+    if cap is not None and int(cap) < 1:
+        raise ValueError(f"cap {cap} < 1")
+    scores, squeezed = _batched(scores, 4)
+    labels = _batched(labels, 3)[0]
+    B, K, H, W = scores.shape
+    if tuple(labels.shape) != (B, H, W):
+        raise ValueError(f"scores {tuple(scores.shape)} need labels [{B},{H},{W}], got {tuple(labels.shape)}")
+    if not 2 <= K <= 32:
+        raise ValueError(f"2 <= K <= 32 classes, got {K}")
+    if not scores.dtype.is_floating_point:
+        raise ValueError(f"scores are floating point (probabilities or logits), got {scores.dtype}")
+    return scores, labels, squeezed
+
+
+def parcel_soft_vote(scores: Tensor, labels: Tensor, bg_mean: float = 0.7, from_logits: bool = True, outside: str = "zero",
+                     cap: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """One class per parcel by the largest mean probability (`soften`, postprocess.py:238-281).  scores f32 [B,K,H,W]
+    (logits, or probabilities with from_logits=False), labels [B,H,W] (0 = no parcel, ids 1..cap; cap as in `parcel_vote`) ->
+    (out int64 [B,H,W], parcel_label int32 [B,cap], parcel_top2 int32 [B,cap], parcel_mean f32 [B,cap,K],
+    parcel_pixels int32 [B,cap]).  The means are sums of 2^-32 fixed-point probabilities: bit-reproducible.  Classes are
+    ordered by (mean descending, class ascending); parcel_top2 is the second, parcel_label the first -- unless the first is
+    class 0 and its mean is not strictly above `bg_mean`, then the second.  Ids that no pixel carries give 0 / 0 / zeros / 0.
+    outside: what pixels without a parcel become: 'zero' or 'keep' (their own top-1 class).  Pixels with a label outside
+    [0,cap] are skipped and left unwritten in `out` (`check_errors`); parcel pixels with a NaN or infinite score add nothing
+    to their parcel (`nonfinite_scores`)."""
+    scores, labels, squeezed = _check_soft_args(scores, labels, bg_mean, outside, cap)
+    _require_hip(scores, "scores")
+    _require_hip(labels, "labels")
+    scores = scores.to(torch.float32).contiguous()
+    labels = labels.to(torch.int32).contiguous()
+    B, K, H, W = scores.shape
+    cap = H * W + 1 if cap is None else int(cap)
+    L = lib()
+    need = L.c2s_parcel_soft_vote_workspace_bytes(B, cap, K)
+    dev = scores.device
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    parcel_label = torch.empty(B, cap, dtype=torch.int32, device=dev)
+    parcel_top2 = torch.empty(B, cap, dtype=torch.int32, device=dev)
+    parcel_mean = torch.empty(B, cap, K, dtype=torch.float32, device=dev)
+    parcel_pixels = torch.empty(B, cap, dtype=torch.int32, device=dev)
+    check(L.c2s_parcel_soft_vote(scores.data_ptr(), labels.data_ptr(), out.data_ptr(), parcel_label.data_ptr(),
+                                 parcel_top2.data_ptr(), parcel_mean.data_ptr(), parcel_pixels.data_ptr(), B, K, H, W, cap,
+                                 1 if from_logits else 0, float(bg_mean), 1 if outside == "keep" else 0, ws.data_ptr(), need,
+                                 _errors(dev).data_ptr() + 4, _stream()), "parcel_soft_vote")
+    res = (out, parcel_label, parcel_top2, parcel_mean, parcel_pixels)
+    return tuple(t[0] for t in res) if squeezed else res
+
+
 def homogenize(pred: Tensor, parcels: Tensor, num_classes: int, bg_share: Optional[float] = 0.75, outside: str = "zero",
-               cap: Optional[int] = None) -> Tensor:
-    """postprocess.homogenize (:377-507, type_='hard', array_out=True) with the LPIS layer as a rasterised id map `parcels`
-    [B,H,W] (0 = no parcel): every parcel takes the class that covers most of it; background only above `bg_share` of it."""
-    return parcel_vote(pred, parcels, num_classes, bg_share, outside, cap)[0]
+               cap: Optional[int] = None, type_: str = "hard", from_logits: bool = True, bg_mean: float = 0.7) -> Tensor:
+    """postprocess.homogenize (:377-507, array_out=True) with the LPIS layer as a rasterised id map `parcels` [B,H,W]
+    (0 = no parcel).  type_='hard': `pred` is the int64 class raster; every parcel takes the class that covers most of it,
+    background only above `bg_share` of it.  type_='soft': `pred` is the score tensor [B,K,H,W] (logits, or probabilities with
+    from_logits=False; K must equal num_classes); every parcel takes the class of its largest mean probability, background
+    only above a mean of `bg_mean` (`parcel_soft_vote`, which also returns the per-parcel table)."""
+    if type_ == "hard":
+        return parcel_vote(pred, parcels, num_classes, bg_share, outside, cap)[0]
+    if type_ != "soft":
+        raise ValueError(f"type_ is 'hard' or 'soft', got {type_!r}")
+    if pred.dim() not in (3, 4) or pred.shape[-3] != num_classes:
+        raise ValueError(f"type_='soft' takes scores [B,{num_classes},H,W], got {tuple(pred.shape)}")
+    return parcel_soft_vote(pred, parcels, bg_mean, from_logits, outside, cap)[0]
 
 
 def homogenize_boundaries(scores: Tensor, boundary_code: int = 15, second_threshold: float = 0.3, from_logits: bool = True,

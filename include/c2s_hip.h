@@ -704,6 +704,25 @@ int c2s_smooth_ce_ex(const float* logits, const long long* target, const float* 
  *     outside [0,cap] or whose class lies outside [0,K) take no part and out is not written there; error[0] += the
  *     former, error[1] += the latter (device ints, never reset by the call).  For labels that come from
  *     c2s_label_components, cap = H * W / min_size + 1 always suffices.
+ *   c2s_parcel_soft_vote: homogenize's type_='soft' (postprocess.py:238-281 `soften`, :491-507; the call iterate() carries
+ *     commented out, src/learning/utils.py:354-360): every pixel centre inside a parcel contributes its K probabilities, the
+ *     parcel takes the class of the largest MEAN probability and keeps the runner-up (`soft_top2_label`).  scores [B,K,H,W]
+ *     f32 (2 <= K <= 32): probabilities, or logits with from_logits = 1 (softmax inside, fp32, max-subtracted, as
+ *     c2s_parcel_seeds); labels int32 [B,H,W] (0 = no parcel, ids 1..cap; parcels need not be connected).  A live pixel
+ *     (label in [1,cap], all K scores finite) adds
+ *         q(p_k) = (u64) rint(clamp(p_k, 0, 1) * 2^32)   to S[b][label-1][k] for every k,   1 to n[b][label-1]
+ *     (64-bit integer sums: bit-reproducible, independent of arrival order; q(1.0) = 2^32).  Per parcel with n > 0: classes
+ *     ordered by (S_k descending, k ascending) give t1, t2;
+ *         parcel_top2 = t2;   parcel_label = t1, except t2 when t1 == 0 and not
+ *         (double)S_0 > (double)bg_mean * (double)n * 4294967296.0          (strict, the `> 0.7` of :273);
+ *         parcel_mean[k] = (float)((double)S_k / ((double)n * 4294967296.0));  parcel_pixels = n.
+ *     n == 0: label = top2 = 0, mean = 0, pixels = 0.  parcel_label / parcel_top2 / parcel_pixels int32 [B,cap], parcel_mean
+ *     f32 [B,cap,K].  out int64 [B,H,W]: parcel_label of the pixel's parcel; where the label is 0: 0 (rasterize(fill=0)) with
+ *     outside = 0, the pixel's own top-1 class (first maximum, as c2s_parcel_seeds) with outside = 1.  Pixels whose label
+ *     lies outside [0,cap] take no part and out is not written there: error[0] += their number.  Pixels of a parcel with a
+ *     NaN or infinite score add nothing (neither to S nor to n) but are written like their neighbours: error[2] += their
+ *     number (error: 3 device ints, never reset by the call; error[1] is not touched).  workspace: the sums u64 [B][cap][K],
+ *     then the counts int32 [B][cap]; 16-byte aligned, see the query (0 when B * cap * K exceeds INT_MAX); the call zeroes it.
  *   Deviations from the reference (it cannot be run where geopandas / rasterio are missing; stated, not measured): :580
  *   takes the class of the largest single same-class patch inside a component, here the largest per-class pixel count wins
  *   (homogenize's own aggregation, :449); ties are unordered there, the lower class wins here.
@@ -716,6 +735,10 @@ int c2s_label_components(const unsigned char* mask, int* labels, int* count, int
 size_t c2s_parcel_vote_workspace_bytes(int B, int cap, int K);
 int c2s_parcel_vote(const long long* pred, const int* labels, long long* out, int* parcel_class, int B, int H, int W, int K,
                     int cap, float bg_share, int outside, void* workspace, size_t ws_bytes, int* error, void* stream);
+size_t c2s_parcel_soft_vote_workspace_bytes(int B, int cap, int K);
+int c2s_parcel_soft_vote(const float* scores, const int* labels, long long* out, int* parcel_label, int* parcel_top2,
+                         float* parcel_mean, int* parcel_pixels, int B, int K, int H, int W, int cap, int from_logits,
+                         float bg_mean, int outside, void* workspace, size_t ws_bytes, int* error, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch movers on either side of the path.

@@ -1,7 +1,7 @@
 """Times of the parcel homogenisation (crop2seg_amd/postprocess.py, csrc/parcels.hip) on one tile of the web app's size:
 1098 x 1098 pixels, K = 16 classes (15 = boundary), fields of random blobs with boundary lines between them.
 
-    python tools/homogenize_bench.py [--size 1098] [--reps 20] [--warmup 5] [--seed 1]
+    python tools/homogenize_bench.py [--size 1098] [--reps 20] [--warmup 5] [--seed 1] [--soft]
 
 Per entry point and for the two chains (homogenize_boundaries: seeds + labelling + vote; homogenize: the vote over a given
 parcel raster) the script prints one JSON line: the median and the minimum of `reps` HIP-event times in microseconds, next
@@ -10,6 +10,11 @@ find and the atomics come on top and depend on the mask).  The Python entry poin
 call; that is inside the timed window, as a caller pays it.  Where scipy imports, the host time of the same work on the same
 raster follows (scipy.ndimage.label with the plus element, the size filter and a numpy bincount vote: the raster part of
 what the reference does on the host behind a .cpu(); its vector part is not restated).  No number here is a pass criterion.
+
+--soft times the soft vote (postprocess.parcel_soft_vote, on probabilities and on logits) beside the hard vote instead, on two
+parcel rasters: the components of the scene above (LPIS-like: hundreds of parcels, label 0 on the lines) and ONE parcel over
+the whole raster, where every wave adds to the same K sums (the contention worst case).  Both votes get a table cut to the
+largest id.  `read_share_of_8TBps` is 4 * K * H * W bytes (the scores, read once) / time / 8e12.
 """
 import argparse
 import json
@@ -48,6 +53,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--min-size", type=int, default=13)
+    ap.add_argument("--soft", action="store_true", help="time the soft vote beside the hard vote on two parcel rasters")
     args = ap.parse_args()
     import torch
     from crop2seg_amd import postprocess as PP
@@ -74,6 +80,22 @@ def main():
             b.synchronize()
             times.append(a.elapsed_time(b) * 1e3)
         return {"median_us": round(statistics.median(times), 1), "min_us": round(min(times), 1)}
+
+    if args.soft:
+        proba = torch.softmax(logits, 1)
+        head = {"tile": [S, S], "classes": K, "device": torch.cuda.get_device_name(0), "score_bytes": 4 * K * N}
+        print(json.dumps(head), flush=True)
+        for name, lab, top in (("lpis_like", labels, max(ncomp, 1)), ("one_parcel", torch.ones_like(labels), 1)):
+            rows = [("parcel_vote", lambda: PP._vote(t1, lab, K, 0.75, "zero", top)),
+                    ("parcel_soft_vote", lambda: PP.parcel_soft_vote(proba, lab, 0.7, False, "zero", top)),
+                    ("parcel_soft_vote_from_logits", lambda: PP.parcel_soft_vote(logits, lab, 0.7, True, "zero", top))]
+            for entry, fn in rows:
+                row = {"scene": name, "parcels": top, "entry": entry, **timed(fn)}
+                if entry != "parcel_vote":
+                    row["read_share_of_8TBps"] = round(4 * K * N / (row["median_us"] * 1e-6) / 8e12, 4)
+                print(json.dumps(row), flush=True)
+        assert PP.check_errors() == (0, 0) and PP.nonfinite_scores() == 0
+        return
 
     nblk = -(-N // 256)
     rows = [
