@@ -2,6 +2,8 @@
 // HBM-bound: every kernel that touches activations is "one wave per (row, segment)" with float4 loads,
 // a row being the HW contiguous floats of one (frame, channel); per-row scale/shift and backward
 // coefficients are wave-uniform scalars.  The tiny per-group reductions run in double precision.
+// Two forms, same bits: the two-pass kernels (statistics / sums, then apply) and the one-pass kernels (one read, the waves
+// of a group meet through memory) are both built from the one set of element, moment, merge and walk functions below.
 //
 // Reference call sites replaced: nn.GroupNorm(4)+ReLU (src/backbones/conv.py:56-60,85-88),
 // nn.BatchNorm2d+ReLU (conv.py:52-53,380,388), the residual adds (conv.py:292,410) and their backward.
@@ -14,6 +16,199 @@ constexpr int SEG = 2048;  // floats per wave-segment (32 per lane = 8 float4 in
 __host__ __device__ inline int seg_len(int HW) { return HW < SEG ? HW : SEG; }
 __host__ __device__ inline int n_segs(int HW) { return (HW + seg_len(HW) - 1) / seg_len(HW); }
 
+// item of the two-pass launches = (row, segment), one wave each: len floats at offset base of the activation
+struct SegItem { long row; int seg, len; size_t base; };
+__device__ __forceinline__ SegItem seg_item(long item, int HW, int segs) {
+    SegItem it;
+    it.row = item / segs;
+    it.seg = (int)(item % segs);
+    const int L = seg_len(HW);
+    const int beg = it.seg * L;
+    it.len = (HW - beg) < L ? (HW - beg) : L;
+    it.base = (size_t)it.row * HW + beg;
+    return it;
+}
+
+// ================================================================= the arithmetic of both forms
+// The engine mixes the forms within one layer (one-pass forward, two-pass backward when only gamma / beta train), so every
+// element formula, every order of summation and every merge is written here and nowhere else.
+
+// ---------------------------------------------------------------- elements
+// forward: relu?((x - mu) * a + b) (+ residual) with a = gamma * rstd, b = beta
+__device__ __forceinline__ float fwd_element(float x, float mu, float a, float b, int relu, bool has_res, float r) {
+    float t = (x - mu) * a + b;
+    if (relu) t = fmaxf(t, 0.f);
+    if (has_res) t += r;
+    return t;
+}
+// backward: g' = g where the ReLU let the forward element through (xc = x - mean), and the two sums it feeds:
+// s1 = sum g', s2 = sum g' * xhat with xhat = (x - mean) * rstd
+__device__ __forceinline__ float masked_grad(float g, float xc, float a, float b, int relu) {
+    return (!relu || xc * a + b > 0.f) ? g : 0.f;
+}
+__device__ __forceinline__ void grad_sums(float gg, float xc, float rstd, float& s1, float& s2) {
+    s1 += gg;
+    s2 += gg * (xc * rstd);
+}
+// dx = k1*g' + k2*(x-mu) + k3 and its running sum (for the producing convolution's bias gradient)
+__device__ __forceinline__ float bwd_element(float gg, float xc, float k1, float k2, float k3, float& sdx) {
+    const float o = k1 * gg + k2 * xc + k3;
+    sdx += o;
+    return o;
+}
+
+// ---------------------------------------------------------------- one wave over its (row, segment)
+// A lane meets its floats in chunks: four at a time (f32x4) or, where the segment length is no multiple of 4, one.  The
+// moments sum a chunk pairwise before they add it to the lane's total.
+__device__ __forceinline__ float chunk_sum(const f32x4& v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float chunk_sum(float v) { return v; }
+__device__ __forceinline__ float chunk_sqdev(const f32x4& v, float mean) {
+    const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
+    return (a * a + b * b) + (c * c + d * d);
+}
+__device__ __forceinline__ float chunk_sqdev(float v, float mean) {
+    const float a = v - mean;
+    return a * a;
+}
+// fe(x, r, o) on every float of a chunk
+template <typename F>
+__device__ __forceinline__ void each(float x, float r, float& o, F fe) { fe(x, r, o); }
+template <typename F>
+__device__ __forceinline__ void each(const f32x4& x, const f32x4& r, f32x4& o, F fe) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float t = 0.f;
+        fe(x[e], r[e], t);
+        o[e] = t;
+    }
+}
+
+// the NK float4 of a lane of a segment of NK * 256 floats, every load requested before the first use.  V = f32x4u where the
+// row base is only 4-byte aligned.
+template <typename V, int NK>
+__device__ __forceinline__ void load_segment(const float* __restrict__ p, int lane, f32x4 (&v)[NK]) {
+#pragma unroll
+    for (int k = 0; k < NK; ++k) v[k] = *reinterpret_cast<const V*>(p + lane * 4 + 256 * k);
+}
+
+// (mean, lane's share of M2) of a segment of NK * 256 floats held in registers: two passes over the registers
+template <int NK>
+__device__ __forceinline__ void segment_moments(const f32x4 (&v)[NK], float& mean, float& m2) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) s += chunk_sum(v[k]);
+    s = wave_sum(s);
+    mean = s / (float)(NK * 256);
+    m2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) m2 += chunk_sqdev(v[k], mean);
+}
+
+// The access shapes of a segment of len floats at offset base of x (and of the second input r when has_r, and of out when
+// STORE): f(x chunk, r chunk, out chunk&) runs on every chunk of the lane, r chunk = 0 without a second input.
+//   * full segment: every load of the lane is requested before the first use (a rolled loop keeps one round per wave in
+//     flight: 3.2 instead of 4.3 TB/s on the 537 MB layers); a row of HW % 4 != 0 floats starts anywhere, hence f32x4u;
+//   * shorter segments of a multiple of 4 floats (then HW is one too and the base is 16-byte aligned): float4 loop;
+//   * anything else: scalar loop.
+template <bool STORE, typename F>
+__device__ __forceinline__ void walk_tail(const float* __restrict__ x, const float* __restrict__ r, bool has_r,
+                                          float* __restrict__ out, size_t base, int len, int lane, F f) {
+    if ((len & 3) == 0) {
+        for (int i = lane * 4; i < len; i += 256) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base + i);
+            f32x4 rv = {0.f, 0.f, 0.f, 0.f}, o;
+            if (has_r) rv = *reinterpret_cast<const f32x4*>(r + base + i);
+            f(xv, rv, o);
+            if (STORE) *reinterpret_cast<f32x4*>(out + base + i) = o;
+        }
+    } else {
+        for (int i = lane; i < len; i += 64) {
+            float o;
+            f(x[base + i], has_r ? r[base + i] : 0.f, o);
+            if (STORE) out[base + i] = o;
+        }
+    }
+}
+template <bool STORE, typename F>
+__device__ __forceinline__ void walk_segment(const float* __restrict__ x, const float* __restrict__ r, bool has_r,
+                                             float* __restrict__ out, size_t base, int len, int lane, F f) {
+    if (len != SEG) return walk_tail<STORE>(x, r, has_r, out, base, len, lane, f);
+    f32x4 xv[SEG / 256], rv[SEG / 256];
+    load_segment<f32x4u>(x + base, lane, xv);
+    if (has_r) load_segment<f32x4u>(r + base, lane, rv);
+#pragma unroll
+    for (int k = 0; k < SEG / 256; ++k) {
+        f32x4 o;
+        f(xv[k], has_r ? rv[k] : f32x4{0.f, 0.f, 0.f, 0.f}, o);
+        if (STORE) *reinterpret_cast<f32x4u*>(out + base + lane * 4 + 256 * k) = o;
+    }
+}
+
+// ---------------------------------------------------------------- merges of the per-(row, segment) partials
+// Group statistics from (mean, M2) partials of known length, Chan's formula in double, one wave: partial(it, mean, m2, len)
+// gives partial `it` of the group and returns false where the group has none (a padded frame).  `unbiased` returns the
+// variance for the running-statistics update.
+template <typename P>
+__device__ __forceinline__ void merge_moments(int items, int lane, float eps, P partial, float& mean_f, float& rstd_f,
+                                              float& unbiased) {
+    double cnt = 0.0, sum = 0.0;
+    for (int it = lane; it < items; it += 64) {
+        float pm, pm2;
+        int len;
+        if (!partial(it, pm, pm2, len)) continue;
+        cnt += len;
+        sum += (double)pm * len;
+    }
+    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o, 64); sum += __shfl_xor(sum, o, 64); }
+    const double mean = cnt > 0 ? sum / cnt : 0.0;
+    double m2 = 0.0;
+    for (int it = lane; it < items; it += 64) {
+        float pm, pm2;
+        int len;
+        if (!partial(it, pm, pm2, len)) continue;
+        const double dm = (double)pm - mean;
+        m2 += (double)pm2 + dm * dm * len;
+    }
+    for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
+    const double var = cnt > 0 ? m2 / cnt : 0.0;
+    mean_f = (float)mean;
+    rstd_f = (float)(1.0 / sqrt(var + (double)eps));
+    unbiased = (float)(cnt > 1 ? m2 / (cnt - 1.0) : var);
+}
+
+// The backward partials (sum g', sum g'*xhat) are reduced where they are needed, in double and in a fixed order.  A row sums
+// its segments in segment order, partial(seg, p1, p2) giving the pair of a segment, and rounds to float.
+template <typename P>
+__device__ __forceinline__ void row_sums(int segs, P partial, float& s1, float& s2) {
+    double t1 = 0.0, t2 = 0.0;
+    for (int s = 0; s < segs; ++s) {
+        float p1, p2;
+        partial(s, p1, p2);
+        t1 += p1;
+        t2 += p2;
+    }
+    s1 = (float)t1;
+    s2 = (float)t2;
+}
+// The coefficients k2, k3 of dx (bwd_element) come from the rows of the group, lanes over rows, weighted by gamma, one wave:
+// row(r, gamma, s1, s2) gives the row sums of row r of the group and returns false for a row of a padded frame.
+template <typename R>
+__device__ __forceinline__ void merge_coeffs(int n_rows, int lane, int HW, float rstd, R row, float& k2, float& k3) {
+    double A = 0.0, Bv = 0.0, cnt = 0.0;
+    for (int r = lane; r < n_rows; r += 64) {
+        float gm, s1, s2;
+        if (!row(r, gm, s1, s2)) continue;
+        A += (double)gm * (double)s1;
+        Bv += (double)gm * (double)s2;
+        cnt += HW;
+    }
+    for (int o = 32; o > 0; o >>= 1) { A += __shfl_xor(A, o, 64); Bv += __shfl_xor(Bv, o, 64); cnt += __shfl_xor(cnt, o, 64); }
+    const double m = cnt > 0 ? cnt : 1.0;
+    k2 = (float)(-(double)rstd * rstd * Bv / m);
+    k3 = (float)(-(double)rstd * A / m);
+}
+
+// ================================================================= two-pass forms
 // ---------------------------------------------------------------- forward statistics
 // part[row][seg] = (mean, M2) of the segment (two passes over the segment; the second hits L1/L2)
 __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict__ x, float* __restrict__ part,
@@ -22,52 +217,20 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
     const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= nitems) return;
     const int lane = threadIdx.x & 63;
-    const long row = item / segs;
-    const int seg = (int)(item % segs);
+    const auto [row, seg, len, base] = seg_item(item, HW, segs);
     if (valid != nullptr && valid[row / C] == 0) return;
-    const int L = seg_len(HW);
-    const int beg = seg * L;
-    const int len = (HW - beg) < L ? (HW - beg) : L;
-    const float* xr = x + row * HW + beg;
-    float s = 0.f, m2 = 0.f, mean;
+    float mean, m2 = 0.f;
     if (len == SEG) {
-        // full segment: all eight float4 of the lane are requested at once (the rolled loop below keeps one load per wave in
-        // flight: 3.2 TB/s on the 537 MB layers) and stay in registers for the second pass; same summation order
+        // full segment: the eight float4 of the lane stay in registers for the second pass
         f32x4 v[SEG / 256];
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) v[k] = *reinterpret_cast<const f32x4u*>(xr + lane * 4 + 256 * k);
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-        s = wave_sum(s);
-        mean = s / (float)len;
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) {
-            const float a = v[k].x - mean, b = v[k].y - mean, c = v[k].z - mean, d = v[k].w - mean;
-            m2 += (a * a + b * b) + (c * c + d * d);
-        }
+        load_segment<f32x4u>(x + base, lane, v);
+        segment_moments(v, mean, m2);
     } else {
-        if ((len & 3) == 0) {
-            for (int i = lane * 4; i < len; i += 256) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(xr + i);
-                s += (v.x + v.y) + (v.z + v.w);
-            }
-        } else {
-            for (int i = lane; i < len; i += 64) s += xr[i];
-        }
+        float s = 0.f;
+        walk_tail<false>(x, nullptr, false, nullptr, base, len, lane, [&](auto v, auto, auto&) { s += chunk_sum(v); });
         s = wave_sum(s);
         mean = s / (float)len;
-        if ((len & 3) == 0) {
-            for (int i = lane * 4; i < len; i += 256) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(xr + i);
-                const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
-                m2 += (a * a + b * b) + (c * c + d * d);
-            }
-        } else {
-            for (int i = lane; i < len; i += 64) {
-                const float a = xr[i] - mean;
-                m2 += a * a;
-            }
-        }
+        walk_tail<false>(x, nullptr, false, nullptr, base, len, lane, [&](auto v, auto, auto&) { m2 += chunk_sqdev(v, mean); });
     }
     m2 = wave_sum(m2);
     if (lane == 0) {
@@ -76,11 +239,10 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
     }
 }
 
-// Group statistics from the (mean, M2) partials of equal-or-known length, Chan's formula in double, one wave.
+// Statistics of a group from the partials of row_stats_kernel.
 // GROUP: group = (n, g): rows (n, g*cpg .. g*cpg+cpg-1).   BATCH: group = c: rows (n, c) for all valid n.
 // Every wave of the apply pass recomputes the statistics of its own group (a few hundred partials, L2-resident) -- that
-// is cheaper than a separate one-wave-per-group launch between the two activation passes.  `unbiased` returns the
-// variance for the running-statistics update.
+// is cheaper than a separate one-wave-per-group launch between the two activation passes.
 __device__ __forceinline__ void group_mean_rstd(const float* __restrict__ part, const int* __restrict__ valid,
                                                 const c2s_norm_desc& d, int segs, int grp, int lane, float& mean_f,
                                                 float& rstd_f, float& unbiased) {
@@ -88,32 +250,15 @@ __device__ __forceinline__ void group_mean_rstd(const float* __restrict__ part, 
     const bool batch = d.kind == C2S_NORM_BATCH;
     const int cpg = batch ? 1 : d.C / d.groups;
     const int n_rows = batch ? d.N : cpg;         // rows in this group
-    const int items = n_rows * segs;
-    double cnt = 0.0, sum = 0.0;
-    for (int it = lane; it < items; it += 64) {
+    merge_moments(n_rows * segs, lane, d.eps, [&](int it, float& pm, float& pm2, int& len) {
         const int r = it / segs, sg = it % segs;
         const long row = batch ? (long)r * d.C + grp : (long)(grp / d.groups) * d.C + (grp % d.groups) * cpg + r;
-        if (batch && valid != nullptr && valid[r] == 0) continue;
-        const int len = (d.HW - sg * L) < L ? (d.HW - sg * L) : L;
-        cnt += len;
-        sum += (double)part[(row * segs + sg) * 2] * len;
-    }
-    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o, 64); sum += __shfl_xor(sum, o, 64); }
-    const double mean = cnt > 0 ? sum / cnt : 0.0;
-    double m2 = 0.0;
-    for (int it = lane; it < items; it += 64) {
-        const int r = it / segs, sg = it % segs;
-        const long row = batch ? (long)r * d.C + grp : (long)(grp / d.groups) * d.C + (grp % d.groups) * cpg + r;
-        if (batch && valid != nullptr && valid[r] == 0) continue;
-        const int len = (d.HW - sg * L) < L ? (d.HW - sg * L) : L;
-        const double dm = (double)part[(row * segs + sg) * 2] - mean;
-        m2 += (double)part[(row * segs + sg) * 2 + 1] + dm * dm * len;
-    }
-    for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
-    const double var = cnt > 0 ? m2 / cnt : 0.0;
-    mean_f = (float)mean;
-    rstd_f = (float)(1.0 / sqrt(var + (double)d.eps));
-    unbiased = (float)(cnt > 1 ? m2 / (cnt - 1.0) : var);
+        if (batch && valid != nullptr && valid[r] == 0) return false;
+        len = (d.HW - sg * L) < L ? (d.HW - sg * L) : L;
+        pm = part[(row * segs + sg) * 2];
+        pm2 = part[(row * segs + sg) * 2 + 1];
+        return true;
+    }, mean_f, rstd_f, unbiased);
 }
 
 // ---------------------------------------------------------------- forward apply
@@ -132,13 +277,8 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
     if (item >= nitems) return;
     const int lane = threadIdx.x & 63;
     const int C = d.C, HW = d.HW;
-    const long row = item / segs;
-    const int seg = (int)(item % segs);
+    const auto [row, seg, len, base] = seg_item(item, HW, segs);
     const int n = (int)(row / C), c = (int)(row % C);
-    const int L = seg_len(HW);
-    const int beg = seg * L;
-    const int len = (HW - beg) < L ? (HW - beg) : L;
-    const size_t base = (size_t)row * HW + beg;
     const bool ok = valid == nullptr || valid[n] != 0;
     const bool batch = d.kind == C2S_NORM_BATCH;
     const int cpg = batch ? 1 : C / d.groups;
@@ -165,52 +305,15 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
     }
     const float a = gamma[c] * rstd, b = beta[c];
     if (seg == 0 && lane == 0) { row_ab[row * 3] = a; row_ab[row * 3 + 1] = b; row_ab[row * 3 + 2] = mu; }
-    if (len == SEG) {
-        // full segment: every load of the lane is requested before the first use (the rolled loop below keeps one round per
-        // wave in flight)
-        f32x4 v[SEG / 256], r[SEG / 256];
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) v[k] = *reinterpret_cast<const f32x4u*>(x + base + lane * 4 + 256 * k);
-        if (res != nullptr) {
-#pragma unroll
-            for (int k = 0; k < SEG / 256; ++k) r[k] = *reinterpret_cast<const f32x4u*>(res + base + lane * 4 + 256 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = (v[k][e] - mu) * a + b;
-                if (relu) t = fmaxf(t, 0.f);
-                if (res != nullptr) t += r[k][e];
-                o[e] = t;
-            }
-            *reinterpret_cast<f32x4u*>(y + base + lane * 4 + 256 * k) = o;
-        }
-    } else if ((len & 3) == 0) {
-        for (int i = lane * 4; i < len; i += 256) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(x + base + i);
-            v.x = (v.x - mu) * a + b; v.y = (v.y - mu) * a + b; v.z = (v.z - mu) * a + b; v.w = (v.w - mu) * a + b;
-            if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            if (res != nullptr) {
-                const f32x4 r = *reinterpret_cast<const f32x4*>(res + base + i);
-                v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-            }
-            *reinterpret_cast<f32x4*>(y + base + i) = v;
-        }
-    } else {
-        for (int i = lane; i < len; i += 64) {
-            float v = (x[base + i] - mu) * a + b;
-            if (relu) v = fmaxf(v, 0.f);
-            if (res != nullptr) v += res[base + i];
-            y[base + i] = v;
-        }
-    }
+    const bool has_res = res != nullptr;
+    walk_segment<true>(x, res, has_res, y, base, len, lane, [&](auto xv, auto rv, auto& o) {
+        each(xv, rv, o, [&](float xe, float re, float& t) { t = fwd_element(xe, mu, a, b, relu, has_res, re); });
+    });
 }
 
 // ---------------------------------------------------------------- backward
-// part[item] = (sum g', sum g'*xhat, -) with g' = g * [a*x+b > 0] (relu) ; xhat = (x-mean)*rstd; the third slot is
-// filled by the apply pass (sum of dx, for the producing convolution's bias gradient)
+// part[item] = (sum g', sum g'*xhat, -): the third slot is filled by the apply pass (sum of dx, for the producing
+// convolution's bias gradient)
 __global__ __launch_bounds__(256) void norm_bwd_sums_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                             const float* __restrict__ row_ab,
                                                             const float* __restrict__ gstats, float* __restrict__ part,
@@ -219,71 +322,35 @@ __global__ __launch_bounds__(256) void norm_bwd_sums_kernel(const float* __restr
     const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= nitems) return;
     const int lane = threadIdx.x & 63;
-    const long row = item / segs;
-    const int seg = (int)(item % segs);
+    const auto [row, seg, len, base] = seg_item(item, d.HW, segs);
     const int n = (int)(row / d.C), c = (int)(row % d.C);
     if (valid != nullptr && valid[n] == 0) {
         if (lane == 0) { part[item * 3] = 0.f; part[item * 3 + 1] = 0.f; }
         return;
     }
-    const int L = seg_len(d.HW);
-    const int beg = seg * L;
-    const int len = (d.HW - beg) < L ? (d.HW - beg) : L;
-    const size_t base = (size_t)row * d.HW + beg;
     const int grp = d.kind == C2S_NORM_BATCH ? c : n * d.groups + c / (d.C / d.groups);
     const float mean = gstats[grp * 2], rstd = gstats[grp * 2 + 1];
     const float a = row_ab[row * 3], b = row_ab[row * 3 + 1];
     float s1 = 0.f, s2 = 0.f;
-    if (len == SEG) {
-        f32x4 xa[SEG / 256], ga[SEG / 256];                       // all 16 loads of the lane in flight at once
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) {
-            xa[k] = *reinterpret_cast<const f32x4u*>(x + base + lane * 4 + 256 * k);
-            ga[k] = *reinterpret_cast<const f32x4u*>(g + base + lane * 4 + 256 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float xx = xa[k][e];
-                const float gg = (!relu || (xx - mean) * a + b > 0.f) ? ga[k][e] : 0.f;
-                s1 += gg;
-                s2 += gg * ((xx - mean) * rstd);
-            }
-    } else if ((len & 3) == 0) {
-        for (int i = lane * 4; i < len; i += 256) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base + i);
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(g + base + i);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xx = xv[k];
-                const float gg = (!relu || (xx - mean) * a + b > 0.f) ? gv[k] : 0.f;
-                s1 += gg;
-                s2 += gg * ((xx - mean) * rstd);
-            }
-        }
-    } else {
-        for (int i = lane; i < len; i += 64) {
-            const float xx = x[base + i];
-            const float gg = (!relu || (xx - mean) * a + b > 0.f) ? g[base + i] : 0.f;
-            s1 += gg;
-            s2 += gg * ((xx - mean) * rstd);
-        }
-    }
+    walk_segment<false>(x, g, true, nullptr, base, len, lane, [&](auto xv, auto gv, auto& o) {
+        each(xv, gv, o, [&](float xe, float ge, float&) {
+            const float xc = xe - mean;
+            grad_sums(masked_grad(ge, xc, a, b, relu), xc, rstd, s1, s2);
+        });
+    });
     s1 = wave_sum(s1); s2 = wave_sum(s2);
     if (lane == 0) { part[item * 3] = s1; part[item * 3 + 1] = s2; }
 }
 
-// The per-(row, segment) partials are reduced where they are needed, in double and in a fixed order:
-//   * the apply pass: every wave derives the coefficients of its own row, dx = k1*g' + k2*(x-mean) + k3, from the sums of
-//     its group (a few hundred L2-resident partials; cheaper than a launch between the two activation passes);
+// The partials of the sums pass are reduced where they are needed:
+//   * the apply pass: every wave derives the coefficients of its own row from the sums of its group (a few hundred
+//     L2-resident partials; cheaper than a launch between the two activation passes);
 //   * norm_bwd_params_kernel, after the apply pass: dgamma, dbeta and the bias gradient of one channel per wave.
-__device__ __forceinline__ void row_sums(const float* __restrict__ part, long row, int segs, double& s1, double& s2) {
-    s1 = 0.0; s2 = 0.0;
-    for (int s = 0; s < segs; ++s) {
-        s1 += part[(row * segs + s) * 3];
-        s2 += part[(row * segs + s) * 3 + 1];
-    }
+__device__ __forceinline__ void part_row_sums(const float* __restrict__ part, long row, int segs, float& s1, float& s2) {
+    row_sums(segs, [&](int s, float& p1, float& p2) {
+        p1 = part[(row * segs + s) * 3];
+        p2 = part[(row * segs + s) * 3 + 1];
+    }, s1, s2);
 }
 
 __global__ __launch_bounds__(64) void norm_bwd_params_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
@@ -293,10 +360,10 @@ __global__ __launch_bounds__(64) void norm_bwd_params_kernel(const float* __rest
     double dg = 0, db = 0;
     for (int n = lane; n < N; n += 64) {
         if (valid != nullptr && valid[n] == 0) continue;
-        double s1, s2;
-        row_sums(part, (long)n * C + c, segs, s1, s2);
-        dg += (double)(float)s2;
-        db += (double)(float)s1;
+        float s1, s2;
+        part_row_sums(part, (long)n * C + c, segs, s1, s2);
+        dg += (double)s2;
+        db += (double)s1;
     }
     for (int o = 32; o > 0; o >>= 1) { dg += __shfl_xor(dg, o, 64); db += __shfl_xor(db, o, 64); }
     if (lane == 0) {
@@ -326,12 +393,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
     if (item >= nitems) return;
     const int lane = threadIdx.x & 63;
     const int C = d.C, HW = d.HW;
-    const long row = item / segs;
-    const int seg = (int)(item % segs);
-    const int L = seg_len(HW);
-    const int beg = seg * L;
-    const int len = (HW - beg) < L ? (HW - beg) : L;
-    const size_t base = (size_t)row * HW + beg;
+    const auto [row, seg, len, base] = seg_item(item, HW, segs);
     if (valid != nullptr && valid[row / C] == 0) {
         for (int i = lane; i < len; i += 64) gx[base + i] = 0.f;
         if (lane == 0) part[item * 3 + 2] = 0.f;
@@ -346,66 +408,22 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
     const float rstd = gstats[grp * 2 + 1];
     float k1 = rstd * gamma[cc], k2 = 0.f, k3 = 0.f;
     if (!(batch && !d.training)) {                      // eval-mode BatchNorm: statistics are constants
-        double A = 0.0, Bv = 0.0, cnt = 0.0;
-        for (int r = lane; r < n_rows; r += 64) {
+        merge_coeffs(n_rows, lane, HW, rstd, [&](int r, float& gm, float& s1, float& s2) {
             const long rr = batch ? (long)r * C + grp : (long)nn * C + (grp % d.groups) * cpg + r;
-            if (valid != nullptr && valid[rr / C] == 0) continue;
-            const float gm = gamma[rr % C];
-            double s1, s2;
-            row_sums(part, rr, segs, s1, s2);
-            A += (double)gm * (double)(float)s1;
-            Bv += (double)gm * (double)(float)s2;
-            cnt += HW;
-        }
-        for (int o = 32; o > 0; o >>= 1) { A += __shfl_xor(A, o, 64); Bv += __shfl_xor(Bv, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-        const double m = cnt > 0 ? cnt : 1.0;
-        k2 = (float)(-(double)rstd * rstd * Bv / m);
-        k3 = (float)(-(double)rstd * A / m);
+            if (valid != nullptr && valid[rr / C] == 0) return false;
+            gm = gamma[rr % C];
+            part_row_sums(part, rr, segs, s1, s2);
+            return true;
+        }, k2, k3);
     }
     const float a = row_ab[row * 3], b = row_ab[row * 3 + 1], mu = row_ab[row * 3 + 2];
     float sdx = 0.f;
-    if (len == SEG) {
-        f32x4 xa[SEG / 256], ga[SEG / 256];                       // all 16 loads of the lane in flight at once
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) {
-            xa[k] = *reinterpret_cast<const f32x4u*>(x + base + lane * 4 + 256 * k);
-            ga[k] = *reinterpret_cast<const f32x4u*>(g + base + lane * 4 + 256 * k);
-        }
-#pragma unroll
-        for (int k = 0; k < SEG / 256; ++k) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float xc = xa[k][e] - mu;
-                const float gg = (!relu || xc * a + b > 0.f) ? ga[k][e] : 0.f;
-                o[e] = k1 * gg + k2 * xc + k3;
-                sdx += o[e];
-            }
-            *reinterpret_cast<f32x4u*>(gx + base + lane * 4 + 256 * k) = o;
-        }
-    } else if ((len & 3) == 0) {
-        for (int i = lane * 4; i < len; i += 256) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base + i);
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(g + base + i);
-            f32x4 o;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xc = xv[k] - mu;
-                const float gg = (!relu || xc * a + b > 0.f) ? gv[k] : 0.f;
-                o[k] = k1 * gg + k2 * xc + k3;
-                sdx += o[k];
-            }
-            *reinterpret_cast<f32x4*>(gx + base + i) = o;
-        }
-    } else {
-        for (int i = lane; i < len; i += 64) {
-            const float xc = x[base + i] - mu;
-            const float gg = (!relu || xc * a + b > 0.f) ? g[base + i] : 0.f;
-            const float o = k1 * gg + k2 * xc + k3;
-            gx[base + i] = o;
-            sdx += o;
-        }
-    }
+    walk_segment<true>(x, g, true, gx, base, len, lane, [&](auto xv, auto gv, auto& o) {
+        each(xv, gv, o, [&](float xe, float ge, float& dx) {
+            const float xc = xe - mu;
+            dx = bwd_element(masked_grad(ge, xc, a, b, relu), xc, k1, k2, k3, sdx);
+        });
+    });
     sdx = wave_sum(sdx);
     if (lane == 0) part[item * 3 + 2] = sdx;
 }
@@ -419,8 +437,8 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
 // Hand-off = data-tagged granules (MI355X_MICROARCH.md, inter-workgroup visibility: 8-byte {data, tag} words written by ONE
 // sc1 store and read by sc1 loads need no ordering, no counter and no fence): wave w of a group stores its two partial sums
 // as two granules {value, epoch} at gran[first granule of the group + w]; wave 0 of every workgroup sweeps the granules of
-// its group (lane = granule) until all carry this launch's epoch, merges them in the fixed order of the two-pass form
-// (double: bit-identical results), and hands the two group values to the other waves through LDS.  The epoch word only
+// its group (lane = granule) until all carry this launch's epoch, merges them with the merge functions the two-pass form
+// calls (bit-identical results), and hands the two group values to the other waves through LDS.  The epoch word only
 // grows (the last workgroup of a launch advances it), so granules of earlier launches -- of any shape, the area is shared
 // by all layers of a stream -- never match and nothing is ever cleared: the area only has to be all zero before its first
 // use.  The grid is persistent (at most the workgroups the chip holds at once, positions dealt round-robin), so every
@@ -566,16 +584,7 @@ __global__ __launch_bounds__(256) void norm_onepass_fwd_kernel(const float* __re
     auto reduce_publish = [&](OpSlot<NK>& s, float& pmean, float& m2) {
         pmean = 0.f; m2 = 0.f;
         if (!(s.live && s.ok)) return;
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) t += (s.xv[k].x + s.xv[k].y) + (s.xv[k].z + s.xv[k].w);
-        t = wave_sum(t);
-        pmean = t / (float)L;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const float a = s.xv[k].x - pmean, b = s.xv[k].y - pmean, cc = s.xv[k].z - pmean, dd = s.xv[k].w - pmean;
-            m2 += (a * a + b * b) + (cc * cc + dd * dd);
-        }
+        segment_moments(s.xv, pmean, m2);
         m2 = wave_sum(m2);
         if (wpg > 1) onepass_publish(sv, s.v, epoch, pmean, m2, lane);
     };
@@ -594,7 +603,7 @@ __global__ __launch_bounds__(256) void norm_onepass_fwd_kernel(const float* __re
             }
             return;
         }
-        f32x4 rv[RES ? NK : 1];
+        f32x4 rv[NK];
         if constexpr (RES) {
             if (s.live) {
 #pragma unroll
@@ -606,18 +615,12 @@ __global__ __launch_bounds__(256) void norm_onepass_fwd_kernel(const float* __re
         if (wpg > 1) {
             if (wave == 0) {
                 onepass_sweep(sv, s.v - s.w, wpg, epoch, lane, poisoned, s_part[0], s_part[1]);
-                // group_mean_rstd of the two-pass form on the swept partials (same order, same arithmetic)
-                double cnt = 0.0, sum = 0.0;
-                for (int w = lane; w < wpg; w += 64) { cnt += L; sum += (double)s_part[0][w] * L; }
-                for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o, 64); sum += __shfl_xor(sum, o, 64); }
-                const double mean = cnt > 0 ? sum / cnt : 0.0;
-                double mm = 0.0;
-                for (int w = lane; w < wpg; w += 64) { const double dm = (double)s_part[0][w] - mean; mm += (double)s_part[1][w] + dm * dm * L; }
-                for (int o = 32; o > 0; o >>= 1) mm += __shfl_xor(mm, o, 64);
-                const double var = cnt > 0 ? mm / cnt : 0.0;
-                mu = (float)mean;
-                rstd = (float)(1.0 / sqrt(var + (double)d.eps));
-                unb = (float)(cnt > 1 ? mm / (cnt - 1.0) : var);
+                merge_moments(wpg, lane, d.eps, [&](int w, float& pm, float& pm2, int& len) {
+                    pm = s_part[0][w];
+                    pm2 = s_part[1][w];
+                    len = L;                                     // every segment of a one-pass shape is full
+                    return true;
+                }, mu, rstd, unb);
                 if (lane == 0) { s_stat[par][0] = mu; s_stat[par][1] = rstd; }
             }
             __syncthreads();
@@ -647,9 +650,7 @@ __global__ __launch_bounds__(256) void norm_onepass_fwd_kernel(const float* __re
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float t = (s.xv[k][e] - mu) * a + b;
-                if (relu) t = fmaxf(t, 0.f);
-                if constexpr (RES) t += rv[k][e];
+                const float t = fwd_element(s.xv[k][e], mu, a, b, relu, RES, RES ? rv[k][e] : 0.f);
                 o[e] = failed ? mu : t;
             }
             *reinterpret_cast<f32x4*>(y + s.base + lane * 4 + 256 * k) = o;
@@ -735,11 +736,10 @@ __global__ __launch_bounds__(256) void norm_onepass_bwd_kernel(const float* __re
         for (int k = 0; k < NK; ++k)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float xx = s.xa[k][e];
-                const float gg = (!relu || (xx - mean) * a + b > 0.f) ? s.ga[k][e] : 0.f;
+                const float xc = s.xa[k][e] - mean;
+                const float gg = masked_grad(s.ga[k][e], xc, a, b, relu);
                 s.ga[k][e] = gg;
-                s1 += gg;
-                s2 += gg * ((xx - mean) * rstd);
+                grad_sums(gg, xc, rstd, s1, s2);
             }
         s1 = wave_sum(s1); s2 = wave_sum(s2);
         if (wpg > 1) onepass_publish(sv, s.v, epoch, s1, s2, lane);
@@ -763,21 +763,15 @@ __global__ __launch_bounds__(256) void norm_onepass_bwd_kernel(const float* __re
         if (wpg > 1) {
             if (wave == 0) {
                 onepass_sweep(sv, s.v - s.w, wpg, epoch, lane, poisoned, s_part[0], s_part[1]);
-                // the per-row sums over the segments run in the order of row_sums(): lanes over rows
-                double A = 0.0, Bv = 0.0, cnt = 0.0;
-                for (int r = lane; r < n_rows; r += 64) {
+                merge_coeffs(n_rows, lane, HW, rstd, [&](int r, float& gm, float& t1, float& t2) {
                     const long rr = batch ? (long)r * C + s.grp : (long)s.grp * cpg + r;
-                    const float gm = gamma[rr % C];
-                    double t1 = 0.0, t2 = 0.0;
-                    for (int sg = 0; sg < segs; ++sg) { t1 += s_part[0][r * segs + sg]; t2 += s_part[1][r * segs + sg]; }
-                    A += (double)gm * (double)(float)t1;
-                    Bv += (double)gm * (double)(float)t2;
-                    cnt += HW;
-                }
-                for (int o = 32; o > 0; o >>= 1) { A += __shfl_xor(A, o, 64); Bv += __shfl_xor(Bv, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-                const double m = cnt > 0 ? cnt : 1.0;
-                k2 = (float)(-(double)rstd * rstd * Bv / m);
-                k3 = (float)(-(double)rstd * A / m);
+                    gm = gamma[rr % C];
+                    row_sums(segs, [&](int sg, float& p1, float& p2) {
+                        p1 = s_part[0][r * segs + sg];
+                        p2 = s_part[1][r * segs + sg];
+                    }, t1, t2);
+                    return true;
+                }, k2, k3);
                 if (lane == 0) { s_stat[par][0] = k2; s_stat[par][1] = k3; }
             }
             __syncthreads();
@@ -795,10 +789,7 @@ __global__ __launch_bounds__(256) void norm_onepass_bwd_kernel(const float* __re
         for (int k = 0; k < NK; ++k) {
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[e] = k1 * s.ga[k][e] + k2 * (s.xa[k][e] - mu) + k3;
-                sdx += o[e];
-            }
+            for (int e = 0; e < 4; ++e) o[e] = bwd_element(s.ga[k][e], s.xa[k][e] - mu, k1, k2, k3, sdx);
             *reinterpret_cast<f32x4*>(gx + s.base + lane * 4 + 256 * k) = o;
         }
         sdx = wave_sum(sdx);
