@@ -83,6 +83,8 @@ SIGNATURES = {
     "c2s_pack_weights_s2dgrad": (I, [P, P, I, I, I, L, L, C.POINTER(I), P]),
     "c2s_conv4x4s2_dgrad_winograd_supported": (I, [C.POINTER(ConvDesc)]),
     "c2s_conv4x4s2_dgrad_winograd": (I, [C.POINTER(ConvDesc), P, P, P, P, P]),
+    "c2s_conv4x4s2_dgrad_winograd_skip_supported": (I, [C.POINTER(ConvDesc), I, I]),
+    "c2s_conv4x4s2_dgrad_winograd_skip": (I, [C.POINTER(ConvDesc), P, P, P, P, P, P, I, I, P]),
     "c2s_bf16x3_packed_elems": (SZ, [I, I]),
     "c2s_pack_weights_bf16x3": (I, [P, P, P, I, I, I, I, L, L, C.POINTER(I), P]),
     "c2s_conv3x3_bf16x3": (I, [C.POINTER(ConvDesc), P, P, P, P, P, P, P, P]),
@@ -146,6 +148,8 @@ SIGNATURES = {
     "c2s_temporal_aggregate_fwd": (I, [C.POINTER(AggDesc), P, P, P, P, P]),
     "c2s_temporal_aggregate_bwd_workspace_floats": (SZ, [C.POINTER(AggDesc)]),
     "c2s_temporal_aggregate_bwd": (I, [C.POINTER(AggDesc), P, P, P, P, P, I, P, P, SZ, P]),
+    "c2s_temporal_aggregate_bwd_skip": (I, [C.POINTER(AggDesc), P, P, P, P, P, I, P, P, P, SZ, P]),
+    "c2s_agg_skip_term": (I, [C.POINTER(AggDesc), P, P, P, P, P]),
     "c2s_cross_entropy_workspace_floats": (SZ, [I, I]),
     "c2s_cross_entropy": (I, [P, P, P, P, P, I, I, I, F, C.c_longlong, P, SZ, P]),
     "c2s_metrics_update": (I, [P, P, P, P, P, P, I, I, I, P]),

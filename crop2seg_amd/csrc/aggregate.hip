@@ -55,12 +55,15 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const float* __restrict__ 
     for (int c = 0; c < CPG; ++c) op[(size_t)c * HW] = acc[c];
 }
 
-// gx = up(attn) * gout ;  gup[g,b,t,Y,X] = sum_{c in g} x * gout.  GX = false: gup only, gx is neither read nor written
-template <int CPG, bool GX = true>
+// gx = up(attn) * gout ;  gup[g,b,t,Y,X] = sum_{c in g} x * gout.  GX = false: gup only, gx is neither read nor written.
+// AUP (with GX = false): the interpolated weight goes to a_up[g,b,t,Y,X] instead of its products with gout to gx -- whoever
+// adds to gx next forms round(a_up * gout) itself (c2s_conv4x4s2_dgrad_winograd_skip); of gx only the padded frames are
+// written (zeros, unless gx_acc)
+template <int CPG, bool GX = true, bool AUP = false>
 __global__ __launch_bounds__(256) void agg_bwd_kernel(const float* __restrict__ x, const float* __restrict__ attn,
                                                       const int* __restrict__ valid, const float* __restrict__ gout,
                                                       float* __restrict__ gx, int gx_acc, float* __restrict__ gup,
-                                                      c2s_agg_desc d) {
+                                                      float* __restrict__ a_up, c2s_agg_desc d) {
     const long total = (long)d.B * d.n_head * d.H * d.W;
     const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (e >= total) return;
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const float* __restrict__ 
         const size_t xo = (((size_t)b * d.T + t) * d.C + g * CPG) * HW + (size_t)Y * d.W + X;
         const size_t uo = ((size_t)(g * d.B + b) * d.T + t) * HW + (size_t)Y * d.W + X;
         if (valid != nullptr && valid[b * d.T + t] == 0) {
-            if (GX && !gx_acc) {
+            if ((GX || AUP) && !gx_acc) {
 #pragma unroll
                 for (int c = 0; c < CPG; ++c) gx[xo + (size_t)c * HW] = 0.f;
             }
@@ -100,41 +103,94 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const float* __restrict__ 
             }
         }
         gup[uo] = s;
+        if constexpr (AUP) a_up[uo] = a;
     }
 }
 
-// adjoint of the bilinear upsample: one thread per low-resolution attention cell (gather, deterministic)
 // Adjoint of the bilinear upsampling of the attention masks: gattn[plane][i][j] += sum_{Y,X} wy(Y,i) wx(X,j) gup[plane][Y][X].
-// One workgroup per (plane, low-resolution row i), separable: thread X first folds the <= 3*H/h contributing rows
-// of column X (coalesced row reads), then thread j folds the <= 3*W/w contributing columns out of LDS.
+// One workgroup per plane, separable, gup read once: thread X walks the rows Y = 0..H-1 of column X (coalesced row reads,
+// AGG_ADJ_ROWS loads in flight) and keeps the running sums of the two low-resolution rows that row Y touches (i0 and
+// i0 + 1; i0 never decreases with Y); a low-resolution row that Y has left is parked in LDS ([ni][cw + 1] floats, 8 KB at
+// 16 x 128).  Then thread (i, j) folds the <= 3*W/w contributing columns of row i out of LDS.
+// A plane whose parked rows would not fit AGG_ADJ_LDS_FLOATS is cut into tiles of nj low-resolution columns and ni rows;
+// a tile reads one low-resolution cell of halo on each side (blockIdx.x = (plane * tiles_i + ti) * tiles_j + tj).
+// Order of every sum: ascending Y, then ascending X, whatever the tiling, B, T or the grid.  The rows of weight exactly 0
+// that a walk over [(i-1) H/h, (i+2) H/h) would also visit are left out: fma(0, v, acc) == acc for finite v, acc from +0.
+constexpr int AGG_ADJ_ROWS = 8;
+constexpr int AGG_ADJ_LDS_FLOATS = 8192;
+constexpr int AGG_ADJ_MAX_LDS_FLOATS = 16384;
+
 __global__ __launch_bounds__(256) void agg_upsample_adjoint_kernel(const float* __restrict__ gup, float* __restrict__ gattn,
-                                                                   c2s_agg_desc d) {
-    extern __shared__ float colsum[];               // [W]
-    const long plane = blockIdx.x / d.h;
-    const int i = blockIdx.x % d.h;
+                                                                   c2s_agg_desc d, int ni, int nj) {
+    extern __shared__ float parked[];               // [ni][cw + 1]
+    const int tiles_j = (d.w + nj - 1) / nj, tiles_i = (d.h + ni - 1) / ni;
+    const int tj = blockIdx.x % tiles_j, ti = (blockIdx.x / tiles_j) % tiles_i;
+    const long plane = blockIdx.x / (tiles_j * tiles_i);
     const int sy = d.H / d.h, sx = d.W / d.w;
-    const int y0 = max(0, (i - 1) * sy), y1 = min(d.H, (i + 2) * sy);
+    const int ia = ti * ni, ib = min(d.h, ia + ni), ja = tj * nj, jb = min(d.w, ja + nj);
+    const int ya = max(0, (ia - 1) * sy), yb = min(d.H, (ib + 1) * sy);
+    const int xa = max(0, (ja - 1) * sx), xb = min(d.W, (jb + 1) * sx);
+    const int ld = xb - xa + 1;                     // + 1: lanes of neighbouring i fold out of different banks
     const float* gp = gup + (size_t)plane * d.H * d.W;
-    for (int X = threadIdx.x; X < d.W; X += blockDim.x) {
-        float acc = 0.f;
-        for (int Y = y0; Y < y1; ++Y) {
+    for (int X = xa + threadIdx.x; X < xb; X += blockDim.x) {
+        float* col = parked + (X - xa);
+        int cur = taps_for(ya, d.h, d.H).i0;        // accA belongs to low-resolution row cur, accB to cur + 1
+        float accA = 0.f, accB = 0.f;
+        for (int i = ia; i < min(cur, ib); ++i) col[(i - ia) * ld] = 0.f;
+        auto add_row = [&](int Y, float v) {
             const Taps ty = taps_for(Y, d.h, d.H);
-            const float wy = (ty.i0 == i ? ty.w0 : 0.f) + (ty.i1 == i ? ty.w1 : 0.f);
-            acc += wy * gp[(size_t)Y * d.W + X];
+            while (cur < ty.i0) {
+                if (cur >= ia && cur < ib) col[(cur - ia) * ld] = accA;
+                accA = accB; accB = 0.f; ++cur;
+            }
+            // the weights (ty.i0 == i ? ty.w0 : 0.f) + (ty.i1 == i ? ty.w1 : 0.f) at i = i0 and at i = i0 + 1
+            const bool one = ty.i1 == ty.i0;
+            accA = fmaf(ty.w0 + (one ? ty.w1 : 0.f), v, accA);
+            if (!one) accB = fmaf(0.f + ty.w1, v, accB);
+        };
+        int Y = ya;
+        for (; Y + AGG_ADJ_ROWS <= yb; Y += AGG_ADJ_ROWS) {
+            float v[AGG_ADJ_ROWS];
+#pragma unroll
+            for (int k = 0; k < AGG_ADJ_ROWS; ++k) v[k] = gp[(size_t)(Y + k) * d.W + X];
+#pragma unroll
+            for (int k = 0; k < AGG_ADJ_ROWS; ++k) add_row(Y + k, v[k]);
         }
-        colsum[X] = acc;
+        for (; Y < yb; ++Y) add_row(Y, gp[(size_t)Y * d.W + X]);
+        for (; cur < ib; ++cur) {
+            if (cur >= ia) col[(cur - ia) * ld] = accA;
+            accA = accB; accB = 0.f;
+        }
     }
     __syncthreads();
-    for (int j = threadIdx.x; j < d.w; j += blockDim.x) {
+    const int tw = jb - ja;
+    for (int e = threadIdx.x; e < (ib - ia) * tw; e += blockDim.x) {
+        const int i = ia + e / tw, j = ja + e % tw;
+        const float* row = parked + (i - ia) * ld - xa;
         const int x0 = max(0, (j - 1) * sx), x1 = min(d.W, (j + 2) * sx);
         float acc = 0.f;
         for (int X = x0; X < x1; ++X) {
             const Taps tx = taps_for(X, d.w, d.W);
             const float wx = (tx.i0 == j ? tx.w0 : 0.f) + (tx.i1 == j ? tx.w1 : 0.f);
-            acc += wx * colsum[X];
+            acc = fmaf(wx, row[X], acc);
         }
         gattn[((size_t)plane * d.h + i) * d.w + j] += acc;
     }
+}
+
+// tile of the adjoint: the whole plane where its parked rows fit, else fewer low-resolution columns, then fewer rows
+struct AdjointTile {
+    int ni, nj, cw;                                 // low-resolution rows and columns of a tile; columns of gup it reads
+};
+AdjointTile adjoint_tile(const c2s_agg_desc* d) {
+    const int sx = d->W / d->w;
+    auto cw = [&](int n) { return n >= d->w || (n + 2) * sx > d->W ? d->W : (n + 2) * sx; };
+    auto fits = [&](int n_i, int n_j) { return (long)n_i * (cw(n_j) + 1) <= AGG_ADJ_LDS_FLOATS; };
+    int ni = d->h, nj = d->w;
+    while (nj > 1 && !fits(ni, nj) && cw(nj) > 1024) nj = (nj + 1) / 2;
+    while (ni > 1 && !fits(ni, nj)) ni = (ni + 1) / 2;
+    while (nj > 1 && !fits(ni, nj)) nj = (nj + 1) / 2;
+    return {ni, nj, cw(nj)};
 }
 
 // ---- agg_mode "att_mean" / "mean" (temporal_aggregator.py:46-56,71-77) reuse the kernels above with a derived weight tensor:
@@ -222,19 +278,29 @@ extern "C" size_t c2s_temporal_aggregate_bwd_workspace_floats(const c2s_agg_desc
     return (size_t)d->n_head * d->B * d->T * d->H * d->W;
 }
 
-extern "C" int c2s_temporal_aggregate_bwd(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
-                                          const float* gout, float* gx, int gx_accumulate, float* gattn,
-                                          float* workspace, size_t ws_floats, void* stream) {
+namespace {
+
+// a_up == NULL: gx = up(attn) * gout (or nothing where gx == NULL); a_up != NULL: the weight itself goes to a_up
+int aggregate_bwd(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid, const float* gout, float* gx,
+                  int gx_accumulate, float* gattn, float* a_up, float* workspace, size_t ws_floats, void* stream) {
     if (int rc = check(d)) return rc;
     // gx == NULL: only gattn (the input needs no gradient); gattn == NULL: only gx (the attention masks need none)
     C2S_REQUIRE(x && attn && gout && (gx || gattn) && workspace, "aggregate_bwd: null pointer");
     C2S_REQUIRE(ws_floats >= c2s_temporal_aggregate_bwd_workspace_floats(d), "aggregate_bwd: workspace too small");
+    const AdjointTile tile = adjoint_tile(d);
+    const long lds_floats = (long)tile.ni * (tile.cw + 1);
+    const long tiles = (long)d->n_head * d->B * d->T * cdiv(d->h, tile.ni) * cdiv(d->w, tile.nj);
+    if (gattn != nullptr) {
+        C2S_REQUIRE(lds_floats <= AGG_ADJ_MAX_LDS_FLOATS, "aggregate_bwd: W / w too large for the upsample adjoint");
+        C2S_REQUIRE(tiles <= 0x7fffffffL, "aggregate_bwd: too many planes for the upsample adjoint");
+    }
     const long total = (long)d->B * d->n_head * d->H * d->W;
     dim3 grid(cdiv(total, 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define C2S_AGG_BWD(CPG_)                                                                                                    \
-    if (gx != nullptr) hipLaunchKernelGGL(agg_bwd_kernel<CPG_>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, *d); \
-    else hipLaunchKernelGGL((agg_bwd_kernel<CPG_, false>), grid, block, 0, st, x, attn, valid, gout, gx, 0, workspace, *d);
+    if (a_up != nullptr) hipLaunchKernelGGL((agg_bwd_kernel<CPG_, false, true>), grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, a_up, *d); \
+    else if (gx != nullptr) hipLaunchKernelGGL(agg_bwd_kernel<CPG_>, grid, block, 0, st, x, attn, valid, gout, gx, gx_accumulate, workspace, a_up, *d); \
+    else hipLaunchKernelGGL((agg_bwd_kernel<CPG_, false>), grid, block, 0, st, x, attn, valid, gout, gx, 0, workspace, a_up, *d);
     switch (d->C / d->n_head) {
         case 1: C2S_AGG_BWD(1) break;
         case 2: C2S_AGG_BWD(2) break;
@@ -245,10 +311,52 @@ extern "C" int c2s_temporal_aggregate_bwd(const c2s_agg_desc* d, const float* x,
 #undef C2S_AGG_BWD
     C2S_CHECK_LAUNCH("aggregate_bwd");
     if (gattn == nullptr) return C2S_OK;
-    const long rows = (long)d->n_head * d->B * d->T * d->h;
-    const int threads = d->W >= 256 ? 256 : (d->W > 64 ? 128 : 64);
-    hipLaunchKernelGGL(agg_upsample_adjoint_kernel, dim3(rows), dim3(threads), (size_t)d->W * sizeof(float), st, workspace,
-                       gattn, *d);
+    const int threads = tile.cw >= 256 ? 256 : (tile.cw > 64 ? 128 : 64);
+    hipLaunchKernelGGL(agg_upsample_adjoint_kernel, dim3(tiles), dim3(threads), (size_t)lds_floats * sizeof(float), st,
+                       workspace, gattn, *d, tile.ni, tile.nj);
     C2S_CHECK_LAUNCH("aggregate_upsample_adjoint");
+    return C2S_OK;
+}
+
+// gx[b,t,c] = round(a_up[g,b,t] * gskip[b,c]) on the real frames: the product agg_bwd_kernel<CPG, true> stores
+__global__ __launch_bounds__(256) void agg_skip_term_kernel(const float* __restrict__ a_up, const float* __restrict__ gskip,
+                                                            const int* __restrict__ valid, float* __restrict__ gx,
+                                                            c2s_agg_desc d) {
+    const size_t HW = (size_t)d.H * d.W;
+    const size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (e >= (size_t)d.B * d.T * d.C * HW) return;
+    const size_t pix = e % HW;
+    size_t r = e / HW;
+    const int c = (int)(r % d.C); r /= d.C;
+    const int t = (int)(r % d.T), b = (int)(r / d.T);
+    if (valid != nullptr && valid[b * d.T + t] == 0) return;
+    const int g = c / (d.C / d.n_head);
+    gx[e] = a_up[((size_t)(g * d.B + b) * d.T + t) * HW + pix] * gskip[((size_t)b * d.C + c) * HW + pix];
+}
+
+}  // namespace
+
+extern "C" int c2s_temporal_aggregate_bwd(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
+                                          const float* gout, float* gx, int gx_accumulate, float* gattn,
+                                          float* workspace, size_t ws_floats, void* stream) {
+    return aggregate_bwd(d, x, attn, valid, gout, gx, gx_accumulate, gattn, nullptr, workspace, ws_floats, stream);
+}
+
+extern "C" int c2s_temporal_aggregate_bwd_skip(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
+                                               const float* gout, float* gx, int gx_accumulate, float* gattn, float* a_up,
+                                               float* workspace, size_t ws_floats, void* stream) {
+    C2S_REQUIRE(gx && gattn && a_up, "aggregate_bwd_skip: null pointer");
+    return aggregate_bwd(d, x, attn, valid, gout, gx, gx_accumulate, gattn, a_up, workspace, ws_floats, stream);
+}
+
+extern "C" int c2s_agg_skip_term(const c2s_agg_desc* d, const float* a_up, const float* gskip, const int* valid, float* gx,
+                                 void* stream) {
+    if (int rc = check(d)) return rc;
+    C2S_REQUIRE(a_up && gskip && gx, "agg_skip_term: null pointer");
+    const size_t n = (size_t)d->B * d->T * d->C * d->H * d->W;
+    C2S_REQUIRE(n <= 0x7fffffffUL * 256, "agg_skip_term: too many elements");
+    hipLaunchKernelGGL(agg_skip_term_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a_up, gskip,
+                       valid, gx, *d);
+    C2S_CHECK_LAUNCH("agg_skip_term");
     return C2S_OK;
 }

@@ -34,6 +34,11 @@ struct S2dParams {
     int Kc, Ho, Wo, Cs, CsP;
     int fold, accumulate;
     int N, tiles, tiles_x, nchunks;
+    // SKIP: out = this gradient + round(a_up * gskip), the skip term of the temporal aggregation (aggregate.hip)
+    // (read from the kernel arguments where the epilogue needs them, not held in SGPRs across the chunk loop)
+    const float* a_up;     // [n_head][N][2 Ho][2 Wo], frame n = b T + t
+    const float* gskip;    // [N / T][Cs][2 Ho][2 Wo]
+    int T, cpg_log2, a_bytes;      // a_bytes: ((n_head - 1) N + 1) 4 Ho Wo * 4, the bytes of a_up a frame's resource spans
 };
 
 constexpr int D2_UHALF = 4 * 128 * D2_UP;            // one k-step (4 gy channels x 128 virtual channels): 6,144 floats = 24 KB
@@ -49,9 +54,17 @@ constexpr int D2_LDS_FLOATS = D2_URING + D2_XSLOTS * D2_XS;      // 159,744 B (+
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// a * b rounded on its own: what a kernel that stores the product and one that adds it to something must agree on
+__device__ __forceinline__ f32x4 rounded_product(f32x4 a, f32x4 b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 #define C2S_AS1 __attribute__((address_space(1)))
 #define C2S_AS3 __attribute__((address_space(3)))
+#define C2S_AS4 __attribute__((address_space(4)))
 
+template <bool SKIP>
 __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x;
@@ -277,6 +290,16 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
         const bool in0 = ncol < p.Wo && mrow < p.Ho, in1 = in0 && mrow + 1 < p.Ho;
         const int vo0 = in0 ? (cof * HWin + (2 * mrow + ey) * Win + 2 * ncol) * 4 : 0x7FFF0000;
         const int vo1 = in1 ? vo0 + 2 * Win * 4 : 0x7FFF0000;
+        // SKIP: frame b = n / T of gskip has the layout of frame n of gx (same offsets); plane (head, n) of a_up
+        __amdgpu_buffer_rsrc_t rg = ro, ra = ro;
+        int cpg_log2 = 0;
+        if constexpr (SKIP) {
+            const S2dParams C2S_AS4* kp = (const S2dParams C2S_AS4*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kp));
+            cpg_log2 = kp->cpg_log2;
+            rg = __builtin_amdgcn_make_buffer_rsrc((void*)(kp->gskip + (size_t)(n / kp->T) * p.Cs * HWin), 0, p.Cs * HWin * 4, 0x00020000);
+            ra = __builtin_amdgcn_make_buffer_rsrc((void*)(kp->a_up + (size_t)n * HWin), 0, kp->a_bytes, 0x00020000);
+        }
         const f32x2 fl2 = {fl, fl}, fr2 = {fr, fr};
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -313,7 +336,20 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int i = 0; i < 2; ++i) v[j][i] = (f32x4){Y[0][i][0][j], Y[1][i][0][j], Y[0][i][1][j], Y[1][i][1][j]};
-                if (p.accumulate) {                                         // the four reads in flight before the first add
+                if constexpr (SKIP) {                                       // the six reads in flight before the first product
+                    const int ho = (((cof + 16 * mt) >> cpg_log2) * p.N - cof) * HWin * 4;   // to the head plane of this lane's channel quad
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {                           // per output row: three reads in flight
+                        const int vo = i == 0 ? vo0 : vo1;
+                        const u32x4 au = __builtin_amdgcn_raw_buffer_load_b128(ra, vo == 0x7FFF0000 ? vo : vo + ho, 0, 0);
+                        u32x4 o[2];
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) o[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, i == 0 ? vo0 : vo1, so + j * HWin * 4, 0);
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) v[j][i] += rounded_product(__builtin_bit_cast(f32x4, au), __builtin_bit_cast(f32x4, o[j]));
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else if (p.accumulate) {                                  // the four reads in flight before the first add
                     u32x4 o[2][2];
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
@@ -337,7 +373,8 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
 }
 
 void init_hook() {
-    C2S_RAISE_LDS(conv_s2dgrad_kernel);
+    C2S_RAISE_LDS(conv_s2dgrad_kernel<false>);
+    C2S_RAISE_LDS(conv_s2dgrad_kernel<true>);
 }
 C2sInitRegistrar registrar(init_hook);
 
@@ -351,8 +388,11 @@ extern "C" int c2s_conv4x4s2_dgrad_winograd_supported(const c2s_conv_desc* d) {
            d->Win >= 32 && d->Hin >= 8 && d->CoutP % 64 == 0 && d->N <= 32768;
 }
 
-extern "C" int c2s_conv4x4s2_dgrad_winograd(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx,
-                                            const int* valid, void* stream) {
+namespace {
+
+// a_up == NULL: gx (+)= the gradient; else gx = the gradient + round(a_up * gskip) (the descriptor's accumulate must be 0)
+int s2dgrad(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx, const int* valid, const float* a_up,
+            const float* gskip, int T, int n_head, void* stream) {
     C2S_REQUIRE(d && gy && upk && gx, "conv4x4s2_dgrad_winograd: null pointer");
     C2S_REQUIRE(c2s_conv4x4s2_dgrad_winograd_supported(d), "conv4x4s2_dgrad_winograd: data gradient of a 4x4 stride 2 pad 1 convolution, gy channels a multiple of 8 (>= 24), even gy planes at least 32 wide and 8 high, CoutP %% 64");
     C2S_REQUIRE(d->N > 0 && d->N <= 32768 && d->Cout > 0 && d->CoutP >= d->Cout,
@@ -369,6 +409,14 @@ extern "C" int c2s_conv4x4s2_dgrad_winograd(const c2s_conv_desc* d, const float*
     p.tiles = p.tiles_x * cdiv(d->Hin, 8);
     p.N = d->N;
     p.nchunks = d->C0 / 8;
+    p.a_up = a_up; p.gskip = gskip; p.T = T; p.cpg_log2 = 0;
+    p.a_bytes = (int)((((long)n_head - 1) * d->N + 1) * d->Hout * d->Wout * 4);
+    if (a_up != nullptr) {
+        C2S_REQUIRE(gskip && c2s_conv4x4s2_dgrad_winograd_skip_supported(d, n_head, T) && d->accumulate == 0,
+                    "conv4x4s2_dgrad_winograd_skip: needs Cout / n_head in {4, 8, 16}, N a multiple of T, accumulate 0 and "
+                    "(CoutP / (Cout / n_head) + 1) N Hout Wout floats below 2 GB");
+        while ((d->Cout / n_head) >> (p.cpg_log2 + 1)) ++p.cpg_log2;
+    }
     const int cus = c2s_cus();
     const int yblocks = 2 * (d->CoutP / 64);
     const long ntotal = (long)d->N * p.tiles;
@@ -376,7 +424,32 @@ extern "C" int c2s_conv4x4s2_dgrad_winograd(const c2s_conv_desc* d, const float*
     if (gx_ > ntotal) gx_ = ntotal;
     dim3 grid((unsigned)gx_, yblocks, 1);
     const size_t ldsb = (size_t)(D2_LDS_FLOATS + (d->N + 31) / 32) * sizeof(float);
-    hipLaunchKernelGGL(conv_s2dgrad_kernel, grid, dim3(512), ldsb, (hipStream_t)stream, p);
+    if (a_up != nullptr) hipLaunchKernelGGL(conv_s2dgrad_kernel<true>, grid, dim3(512), ldsb, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(conv_s2dgrad_kernel<false>, grid, dim3(512), ldsb, (hipStream_t)stream, p);
     C2S_CHECK_LAUNCH("conv4x4s2_dgrad_winograd");
     return C2S_OK;
+}
+
+}  // namespace
+
+extern "C" int c2s_conv4x4s2_dgrad_winograd(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx,
+                                            const int* valid, void* stream) {
+    return s2dgrad(d, gy, upk, gx, valid, nullptr, nullptr, 1, 1, stream);
+}
+
+// the same gradient with the skip term of the temporal aggregation added in the epilogue: gx[n] = gradient + round(a_up[g, n] *
+// gskip[n / T]) with g the head of the channel, a_up [n_head][N][Hout][Wout] as c2s_temporal_aggregate_bwd_skip stores it and
+// gskip [N / T][Cout][Hout][Wout]; gx is not read.  A lane's four channels must share a head: Cout / n_head in {4, 8, 16}
+extern "C" int c2s_conv4x4s2_dgrad_winograd_skip_supported(const c2s_conv_desc* d, int n_head, int T) {
+    if (!c2s_conv4x4s2_dgrad_winograd_supported(d) || n_head <= 0 || T <= 0 || d->N % T != 0 || d->Cout % n_head != 0) return 0;
+    const int cpg = d->Cout / n_head;
+    return (cpg == 4 || cpg == 8 || cpg == 16) &&
+           (long)(d->CoutP / cpg + 1) * d->N * d->Hout * d->Wout * 4 < 0x7FFF0000L;
+}
+
+extern "C" int c2s_conv4x4s2_dgrad_winograd_skip(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx,
+                                                 const int* valid, const float* a_up, const float* gskip, int n_head, int T,
+                                                 void* stream) {
+    C2S_REQUIRE(a_up && gskip, "conv4x4s2_dgrad_winograd_skip: null pointer");
+    return s2dgrad(d, gy, upk, gx, valid, a_up, gskip, T, n_head, stream);
 }

@@ -37,6 +37,11 @@ SIDE_FLUSH_POSITIONS = int(_os.environ.get("C2S_WGRAD_FLUSH_POSITIONS", str(1 <<
 # 12.25 ms for eager two-stream launches -- the graph executor serialises around the cross-stream edges -- so a capture stays
 # on one stream unless C2S_GRAPH_SIDE=1.
 GRAPH_SIDE = _os.environ.get("C2S_GRAPH_SIDE", "0") != "0"
+# The aggregator's input gradient up(attn) * d skip as a pending term of the tape: temporal_aggregate's backward stores the
+# interpolated weights once and the 4x4 stride-2 data gradient that follows adds the products in its epilogue
+# (c2s_conv4x4s2_dgrad_winograd_skip) instead of reading them back from the gradient buffer.  C2S_AGG_SKIP_TERM=0: the
+# aggregator writes the products and the data gradient accumulates (A/B runs; bit-identical results).
+AGG_SKIP_TERM = _os.environ.get("C2S_AGG_SKIP_TERM", "1") != "0"
 
 
 # Backward launch log: None (default) or a list to which every backward launch appends (op, name, kind), kind "dgrad" (the
@@ -226,6 +231,10 @@ class Tape:
         self.side_used = False
         self.side_pending: List[Callable[[], None]] = []   # weight-gradient launches waiting for the next fork
         self.finalizers: Dict[int, Callable[[], None]] = {}   # run once after the last side-stream launch (batched slice sums)
+        # data pointer of a conv2d source whose data gradient is the F(2x2,2x2) kernel -> (its descriptor, pointer of its frame
+        # flags); and the terms up(attn) * d skip that temporal_aggregate left for such a source instead of writing them
+        self.s2d_sources: Dict[int, Tuple[object, Optional[int]]] = {}
+        self.skip_terms: Dict[int, "SkipTerm"] = {}
 
     def fork(self) -> "torch.cuda.Stream":
         """Side HIP stream ordered after everything issued so far on the current stream.  Weight gradients feed nothing
@@ -245,14 +254,28 @@ class Tape:
         self.keep.append(t)
         return t
 
+    def settle(self, key: int) -> None:
+        """Write a pending skip term of the gradient buffer `key` into it: every reader but the data gradient that takes the
+        term itself (take_skip_term) sees the buffer temporal_aggregate would have written (the same rounded products)."""
+        term = self.skip_terms.pop(key, None)
+        if term is not None:
+            check(lib().c2s_agg_skip_term(C.byref(term.desc), term.a_up.data_ptr(), term.gskip.data_ptr(), _ptr(term.valid),
+                                          self.grads[key].data_ptr(), _stream()), "agg_skip_term")
+
+    def take_skip_term(self, t: Tensor) -> Optional["SkipTerm"]:
+        return self.skip_terms.pop(t.data_ptr(), None)
+
     def grad_of(self, t: Tensor) -> Optional[Tensor]:
+        self.settle(t.data_ptr())
         return self.grads.get(t.data_ptr())
 
     def pop_grad(self, t: Tensor) -> Optional[Tensor]:
+        self.settle(t.data_ptr())
         return self.grads.pop(t.data_ptr(), None)
 
     def add_grad(self, t: Tensor, g: Tensor, own: bool = True) -> None:
         """Accumulate g into the gradient of t.  If t has no gradient yet, g becomes it (own=True) or is copied."""
+        self.settle(t.data_ptr())
         cur = self.grads.get(t.data_ptr())
         if cur is None:
             self.grads[t.data_ptr()] = g if own else g.clone()
@@ -262,6 +285,7 @@ class Tape:
     def grad_buffer(self, t: Tensor) -> Tuple[Tensor, int]:
         """(gradient buffer of t, accumulate flag) for a kernel that adds in place: the buffer already on the tape with
         flag 1, else a fresh one nobody else holds, now on the tape, with flag 0 (the kernel overwrites it)."""
+        self.settle(t.data_ptr())
         g = self.grads.get(t.data_ptr())
         if g is not None:
             return g, 1
@@ -287,6 +311,10 @@ class Tape:
     def backward(self) -> None:
         for fn in reversed(self.ops):
             fn()
+        for key in list(self.skip_terms):           # a source nobody asked for its gradient (a leaf of the tape)
+            self.settle(key)
+        assert not self.skip_terms
+        self.s2d_sources.clear()
         self.flush_side()
         if self.finalizers:
             fins, self.finalizers = list(self.finalizers.values()), {}
@@ -305,6 +333,17 @@ class Tape:
         self.side_keep.clear()
         self.ops.clear()
         self.keep.clear()
+
+
+class SkipTerm(NamedTuple):
+    """up(attn) * d skip, not yet added to the gradient of the aggregator's input: gx[b,t,c] += a_up[g,b,t] * gskip[b,c]."""
+    a_up: Tensor            # [n_head,B,T,H,W], a workspace buffer of its own (name) until the term is added
+    gskip: Tensor           # [B,C,H,W]
+    desc: object            # AggDesc
+    valid: Optional[Tensor]
+    n_head: int
+    T: int
+    name: str
 
 
 class Ctx:
@@ -740,6 +779,11 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
     tape.track(out)
     train_w = ctx.trains(wname)
     need_src = [need_input_grad and ctx.needs(src) for src in srcs]
+    if AGG_SKIP_TERM and (K, S, pad) == (4, 2, 1):
+        for si, src in enumerate(srcs):             # temporal_aggregate's backward may leave its term to this data gradient
+            plan = conv_plan("dgrad", N, chans, Cout, Hin, Win, K, S, pad, pad_mode, si, 0) if need_src[si] else None
+            if plan is not None and plan.family == "s2dgrad":
+                tape.s2d_sources[src.data_ptr()] = (plan.launches[0].desc, _ptr(valid))
 
     def bwd():
         g = tape.pop_grad(out)
@@ -753,6 +797,17 @@ def conv2d(ctx: Ctx, srcs: Sequence[Tensor], wname: str, bname: Optional[str], K
             if not need_src[si]:
                 continue
             _log("conv2d", wname, "dgrad")
+            if src.data_ptr() in tape.skip_terms:
+                plan = conv_plan("dgrad", N, chans, Cout, Hin, Win, K, S, pad, pad_mode, si, 0)
+                if plan.family == "s2dgrad" and tape.s2d_sources.get(src.data_ptr(), (None, 0))[1] == _ptr(valid):
+                    term = tape.take_skip_term(src)
+                    desc, key, kind, *where = plan.launches[0]
+                    packed = ctx.pack((wname,) + key, W, *where, kind=kind)[0]
+                    check(lib().c2s_conv4x4s2_dgrad_winograd_skip(
+                        C.byref(desc), g.data_ptr(), packed.data_ptr(), tape.grads[src.data_ptr()].data_ptr(), _ptr(valid),
+                        term.a_up.data_ptr(), term.gskip.data_ptr(), term.n_head, term.T, _stream()),
+                        "conv4x4s2_dgrad_winograd_skip")
+                    continue
             gin, accf = tape.grad_buffer(src)
             _run_conv(ctx, conv_plan("dgrad", N, chans, Cout, Hin, Win, K, S, pad, pad_mode, si, accf), wname, W, g, None, None,
                       gin, valid)
@@ -1058,6 +1113,12 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
         g = tape.pop_grad(out)
         if g is None:
             return
+        key = x5.data_ptr()
+        reg = tape.s2d_sources.get(key)
+        skip = (AGG_SKIP_TERM and reg is not None and mode in ("att_group", "att_mean") and need_x and need_a
+                and key not in tape.grads and key not in tape.skip_terms and reg[1] == _ptr(valid)
+                and (reg[0].N, reg[0].Cout, reg[0].Hout, reg[0].Wout) == (B * T, Cc, H, W)
+                and lib().c2s_conv4x4s2_dgrad_winograd_skip_supported(C.byref(reg[0]), n_head, T) == 1)
         gx, accx = tape.grad_buffer(x5) if need_x else (None, 0)
         if need_x:
             _log("temporal_aggregate", mode, "dgrad")
@@ -1072,9 +1133,19 @@ def temporal_aggregate(ctx: Ctx, x5: Tensor, attn: Tensor, valid: Optional[Tenso
             gattn = torch.zeros_like(attn)          # gradient of the derived weights
         nws = lib().c2s_temporal_aggregate_bwd_workspace_floats(C.byref(d))
         ws = ctx.ws.get("agg", nws)
-        check(lib().c2s_temporal_aggregate_bwd(C.byref(d), x5.data_ptr(), attn.data_ptr(), _ptr(valid), g.data_ptr(),
-                                               _ptr(gx), accx, _ptr(gattn),
-                                               ws.data_ptr(), ws.numel(), _stream()), "temporal_aggregate_bwd")
+        if skip:
+            # the levels' terms are pending at once, and a captured step must not allocate: a named buffer per pending term
+            used = {t.name for t in tape.skip_terms.values()}
+            name = next(n for n in (f"agg_a_up:{H}x{W}:{k}" for k in range(len(used) + 1)) if n not in used)
+            a_up = ctx.ws.get(name, nws)
+            check(lib().c2s_temporal_aggregate_bwd_skip(C.byref(d), x5.data_ptr(), attn.data_ptr(), _ptr(valid), g.data_ptr(),
+                                                        gx.data_ptr(), accx, gattn.data_ptr(), a_up.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), _stream()), "temporal_aggregate_bwd_skip")
+            tape.skip_terms[key] = SkipTerm(a_up, g, d, valid, n_head, T, name)
+        else:
+            check(lib().c2s_temporal_aggregate_bwd(C.byref(d), x5.data_ptr(), attn.data_ptr(), _ptr(valid), g.data_ptr(),
+                                                   _ptr(gx), accx, _ptr(gattn),
+                                                   ws.data_ptr(), ws.numel(), _stream()), "temporal_aggregate_bwd")
         if mode == "att_mean" and need_a:
             tgt, acca = tape.grad_buffer(src_attn)
             check(lib().c2s_attn_head_mean_bwd(gattn.data_ptr(), tgt.data_ptr(), n_head, src_attn[0].numel(), acca, _stream()),

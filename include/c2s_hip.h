@@ -198,6 +198,15 @@ int c2s_pack_weights_s2dgrad(const float* src, float* upk, int kc, int cs, int c
 int c2s_conv4x4s2_dgrad_winograd_supported(const c2s_conv_desc* d);
 int c2s_conv4x4s2_dgrad_winograd(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx, const int* valid,
                                  void* stream);
+/* The same gradient with the skip term of the temporal aggregation added in the epilogue instead of read back from gx:
+ * gx[n, c] = gradient + round(a_up[g(c), n] * gskip[n / T, c]), g(c) = c / (Cout / n_head), a_up [n_head][N][Hout][Wout] as
+ * c2s_temporal_aggregate_bwd_skip stores it, gskip [N / T][Cout][Hout][Wout] the gradient of the aggregated map.  The product
+ * is rounded on its own, so the result has the bits of c2s_temporal_aggregate_bwd (gx written) followed by the accumulating
+ * c2s_conv4x4s2_dgrad_winograd.  accumulate must be 0; gx is not read; frames with valid == 0 are not written.  Supported
+ * where the plain form is, Cout / n_head is 4, 8 or 16 (the four channels of a lane share a head) and N % T == 0. */
+int c2s_conv4x4s2_dgrad_winograd_skip_supported(const c2s_conv_desc* d, int n_head, int T);
+int c2s_conv4x4s2_dgrad_winograd_skip(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx, const int* valid,
+                                      const float* a_up, const float* gskip, int n_head, int T, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Opt-in split-precision variant of the 3x3 stride-1 pad-1 convolution (forward and data gradient, same
@@ -550,6 +559,14 @@ size_t c2s_temporal_aggregate_bwd_workspace_floats(const c2s_agg_desc* d);
 int c2s_temporal_aggregate_bwd(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
                                const float* gout, float* gx, int gx_accumulate, float* gattn,
                                float* workspace, size_t ws_floats, void* stream);
+/* The backward for a caller that adds up(attn) * gout to gx itself (c2s_conv4x4s2_dgrad_winograd_skip): gattn as above; the
+ * interpolated weights go to a_up [n_head,B,T,H,W]; of gx only the frames with valid == 0 are written (zeros, unless
+ * gx_accumulate).  c2s_agg_skip_term writes gx[b,t,c] = round(a_up[g,b,t] * gout[b,c]) on the other frames: together the
+ * two calls leave the bits of c2s_temporal_aggregate_bwd with gx_accumulate = 0.  None of gx, gattn, a_up may be NULL. */
+int c2s_temporal_aggregate_bwd_skip(const c2s_agg_desc* d, const float* x, const float* attn, const int* valid,
+                                    const float* gout, float* gx, int gx_accumulate, float* gattn, float* a_up,
+                                    float* workspace, size_t ws_floats, void* stream);
+int c2s_agg_skip_term(const c2s_agg_desc* d, const float* a_up, const float* gout, const int* valid, float* gx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Loss + optimiser of the train step (train.py:454,463-468; src/learning/utils.py:314-328).
