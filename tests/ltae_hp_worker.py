@@ -2,7 +2,8 @@
 float64 reference of tests/ltae_hp_ref.py, in the manner of tests/ltae_ref_worker.py.
 
 argv[1]: JSON list of rows, argv[2]: the bound constants.  Each row prints one line "ROW <json>" (families reached, worst ratio
-per output); the process prints LTAE_HP_OK <n> when every row passed."""
+per output); the process prints LTAE_HP_OK <n> when every row passed.  Optional argv[3]: MiB of the guard-band arena, as in
+tests/ltae_ref_worker.py."""
 import ctypes
 import json
 import math
@@ -19,7 +20,7 @@ import torch  # noqa: E402
 import conv_ref  # noqa: E402
 import ltae_hp_ref as H  # noqa: E402
 import ltae_ref as R  # noqa: E402
-from ltae_ref_worker import ENC, FROB, thr_scale  # noqa: E402
+from ltae_ref_worker import ENC, FROB, run_row_in_arena, thr_scale  # noqa: E402
 
 FOLD = ["te.attention_head.Q", "te.attention_head.fc1_k.weight", "te.attention_head.fc1_k.bias", "te.inconv.weight",
         "te.inconv.bias"]
@@ -230,8 +231,9 @@ def fold_same(row):
 def main():
     rows = json.loads(sys.argv[1])
     C_F = json.loads(sys.argv[2])
+    arena_mib = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     for row in rows:
-        res = run_row(row, C_F)
+        res = run_row_in_arena(run_row, row, C_F, arena_mib) if arena_mib else run_row(row, C_F)
         if row.get("fold_same"):
             res.update(fold_same(row))
         print("ROW " + json.dumps(res), flush=True)

@@ -2,7 +2,8 @@
 process whose environment selects the kernel families (the C2S_LTAE_* switches are read once per process).
 
 argv[1]: JSON list of rows.  Each row prints one line "ROW <json>" (families reached, worst ratio per output); the process
-prints LTAE_REF_OK <n> when every row passed."""
+prints LTAE_REF_OK <n> when every row passed.  Optional argv[3]: MiB of a guard-band arena (tests/redzone.py) every row then
+runs in; its ROW line gains "redzone": "intact" (tests/test_redzone_gpu.py)."""
 import ctypes
 import json
 import math
@@ -167,11 +168,24 @@ def run_row(row, C_F):
     return res
 
 
+def run_row_in_arena(run, row, C_F, mib):
+    """run(row, C_F) with every device allocation between poisoned guard bands (tests/redzone.py, an arena of `mib` MiB):
+    the row's own checks hold on poisoned uninitialised memory and the guard bands are intact afterwards.  "unwritten" lists
+    the engine's allocations that still hold poison (site, shape, words)."""
+    import redzone
+    with redzone.arena("cuda", mib << 20) as a:
+        res = run(row, C_F)
+        left = [[b.site, list(b.shape), n] for b, n in a.unwritten()]
+    res.update(redzone="intact", unwritten=left, arena_used=a.used)
+    return res
+
+
 def main():
     rows = json.loads(sys.argv[1])
     C_F = json.loads(sys.argv[2])
+    arena_mib = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     for row in rows:
-        res = run_row(row, C_F)
+        res = run_row_in_arena(run_row, row, C_F, arena_mib) if arena_mib else run_row(row, C_F)
         print("ROW " + json.dumps(res), flush=True)
     print("LTAE_REF_OK", len(rows), flush=True)
 
