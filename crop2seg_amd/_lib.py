@@ -176,6 +176,9 @@ SIGNATURES = {
     "c2s_window_count": (I, [I, I, I]),
     "c2s_window_origin": (I, [I, I, I, I]),
     "c2s_cut_windows": (I, [P, P, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(F), P]),
+    "c2s_window_frames": (I, [P, I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, F, I, P]),
+    "c2s_cut_windows_raw": (I, [P, I, P, P, I, I, I, I, I, I, I, I, I, I, I, I, C.POINTER(I), C.POINTER(F), C.POINTER(F),
+                                C.POINTER(F), F, I, I, P]),
     "c2s_softmax_blend": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
     "c2s_blend_finish": (I, [P, P, P, I, I, I, P]),
     "c2s_adam_flat": (I, [P, P, P, P, L, F, F, F, F, I, P, F, P]),

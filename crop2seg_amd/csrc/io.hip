@@ -11,6 +11,9 @@
 //  * c2s_cut_windows / c2s_softmax_blend / c2s_blend_finish : the same tail for a whole raster series predicted on
 //    overlapping windows (inference.predict_raster; no counterpart in the reference): windows cut out of the series on the
 //    device, their softmax blended into the raster with a taper by a per-pixel gather, normalised and arg-maxed in place.
+//  * c2s_window_frames / c2s_cut_windows_raw : the same windows from the series as STORED (int16 / uint16 / float32):
+//    which acquisitions each window keeps (empty ones, nodata in every band, dropped per window), then cut + collate in
+//    one pass, so that no fp32 copy of the raster ever exists.
 //
 // Both are HBM/PCIe-bound byte movers (no reuse): the collate kernel reads each source element once with 16-byte lanes
 // (8-byte for 16-bit sources) and writes 16-byte lanes; padding frames are written as zeros by the same grid.
@@ -32,6 +35,17 @@ struct CollateParams {
     float pad_value;
     int ndvi_a, ndvi_b;         // >= 0: the LAST output channel is the NDVI of source channels (a, b), not normalised
 };
+
+// The ONE statement of the per-element arithmetic, shared by collate_kernel and cut_windows_raw_kernel.
+// (d - mean) / std with IEEE fp32 subtraction and division, as torch evaluates it (no reciprocal, no fma)
+__device__ __forceinline__ float normalised(float f, float m, float s) { return __fdiv_rn(__fsub_rn(f, m), s); }
+// add_ndvi (s2_ts_cz_crop.py:376-391,401-402): (NIR - red) / (NIR + red) of the raw bands, 0 where the sum is 0 and where
+// the quotient leaves [-1, 1]; appended after the normalised bands, itself not normalised.  IEEE fp32 add / sub / div.
+__device__ __forceinline__ float ndvi_of(float a, float b) {
+    const float sum = __fadd_rn(a, b);
+    const float v = sum == 0.f ? 0.f : __fdiv_rn(__fsub_rn(a, b), sum);
+    return (v < -1.f || v > 1.f) ? 0.f : v;
+}
 
 template <typename S> struct Vec4;
 template <> struct Vec4<float> { using type = float4; };
@@ -58,23 +72,13 @@ __global__ __launch_bounds__(256) void collate_kernel(CollateParams p) {
     }
     using V = typename Vec4<S>::type;
     if (p.ndvi_a >= 0 && c == p.C - 1) {
-        // add_ndvi (s2_ts_cz_crop.py:376-391,401-402): (NIR - red) / (NIR + red) of the raw bands, 0 where the sum is 0 and where
-        // the quotient leaves [-1, 1]; appended after the normalised bands, itself not normalised.  IEEE fp32 add / sub / div.
         const V* ia = reinterpret_cast<const V*>(static_cast<const S*>(p.src) + ((size_t)(beg + t) * p.Cs + p.ndvi_a) * p.HW);
         const V* ib = reinterpret_cast<const V*>(static_cast<const S*>(p.src) + ((size_t)(beg + t) * p.Cs + p.ndvi_b) * p.HW);
         for (int i = blockIdx.x * 256 + threadIdx.x; i < q; i += gridDim.x * 256) {
             const V va = ia[i], vb = ib[i];
             const float a4[4] = {(float)va.x, (float)va.y, (float)va.z, (float)va.w};
             const float b4[4] = {(float)vb.x, (float)vb.y, (float)vb.z, (float)vb.w};
-            float o[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float sum = __fadd_rn(a4[k], b4[k]);
-                float v = sum == 0.f ? 0.f : __fdiv_rn(__fsub_rn(a4[k], b4[k]), sum);
-                if (v < -1.f || v > 1.f) v = 0.f;
-                o[k] = v;
-            }
-            out[i] = make_float4(o[0], o[1], o[2], o[3]);
+            out[i] = make_float4(ndvi_of(a4[0], b4[0]), ndvi_of(a4[1], b4[1]), ndvi_of(a4[2], b4[2]), ndvi_of(a4[3], b4[3]));
         }
         return;
     }
@@ -84,11 +88,10 @@ __global__ __launch_bounds__(256) void collate_kernel(CollateParams p) {
         const V v = in[i];
         float4 f = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);      // .astype(np.float32): exact for 16-bit ints
         if (p.normalise) {
-            // (d - mean) / std with IEEE fp32 subtraction and division, as torch evaluates it (no reciprocal, no fma)
-            f.x = __fdiv_rn(__fsub_rn(f.x, m), s);
-            f.y = __fdiv_rn(__fsub_rn(f.y, m), s);
-            f.z = __fdiv_rn(__fsub_rn(f.z, m), s);
-            f.w = __fdiv_rn(__fsub_rn(f.w, m), s);
+            f.x = normalised(f.x, m, s);
+            f.y = normalised(f.y, m, s);
+            f.z = normalised(f.z, m, s);
+            f.w = normalised(f.w, m, s);
         }
         out[i] = f;
     }
@@ -169,6 +172,171 @@ __global__ __launch_bounds__(256) void cut_windows_kernel(CutParams p) {
             }
         }
         reinterpret_cast<float4*>(p.x)[e] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// ---------------------------------------------------------------- the same windows from the STORED series
+// Which frames a window keeps.  Count: one workgroup per (window, frame) over the window's pixels INSIDE the raster; a
+// pixel is empty when every source channel equals nodata.  (float)v is exact for the 16-bit types, so the comparison is
+// the integer one.  Channel 0 decides for almost every pixel of real data; the others are read only behind it.  Integer
+// sums: the result does not depend on the order, hence not on the launch geometry.
+struct FramesParams {
+    const void* src;            // [T][Cs][H][W]
+    const long long* dates;     // [T]
+    int* nodata_px;             // [nwin][T]
+    int* slots;                 // [nwin][T]
+    int* counts;                // [nwin]
+    long long* win_dates;       // [nwin][T]
+    int T, Cs, H, W, ph, pw, sy, sx, nx, first, nwin, permille;
+    float nodata;
+};
+
+template <typename S>
+__global__ __launch_bounds__(256) void count_nodata_kernel(FramesParams p) {
+    __shared__ int part[4];
+    const int wi = blockIdx.x / p.T, t = blockIdx.x % p.T;
+    const int w = p.first + wi;
+    const int oy = win_origin(w / p.nx, p.H, p.ph, p.sy), ox = win_origin(w % p.nx, p.W, p.pw, p.sx);
+    const int h = min(p.ph, p.H - oy), wd = min(p.pw, p.W - ox);
+    const size_t plane = (size_t)p.H * p.W;
+    const S* f0 = static_cast<const S*>(p.src) + (size_t)t * p.Cs * plane;
+    int n = 0;
+    for (int i = threadIdx.x; i < h * wd; i += 256) {
+        const size_t at = (size_t)(oy + i / wd) * p.W + (ox + i % wd);
+        bool empty = (float)f0[at] == p.nodata;
+        for (int cs = 1; empty && cs < p.Cs; ++cs) empty = (float)f0[cs * plane + at] == p.nodata;
+        n += empty ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) p.nodata_px[(size_t)wi * p.T + t] = part[0] + part[1] + part[2] + part[3];
+}
+
+// Ordered compaction: one wave (one workgroup of 64 lanes) per window walks T in chunks of 64; ballot + popcount place
+// the kept frames in ascending t.  A window that would keep none keeps the frame with the fewest empty pixels, lowest t
+// on a tie: the smallest (nodata_px, t) key.
+__global__ __launch_bounds__(64) void compact_frames_kernel(FramesParams p) {
+    const int wi = blockIdx.x, lane = threadIdx.x;
+    const int w = p.first + wi;
+    const int oy = win_origin(w / p.nx, p.H, p.ph, p.sy), ox = win_origin(w % p.nx, p.W, p.pw, p.sx);
+    const long long inside = (long long)min(p.ph, p.H - oy) * min(p.pw, p.W - ox);
+    const int* px = p.nodata_px + (size_t)wi * p.T;
+    int* slots = p.slots + (size_t)wi * p.T;
+    long long* wd = p.win_dates + (size_t)wi * p.T;
+    int count = 0;
+    long long best = 0x7fffffffffffffffLL;
+    for (int base = 0; base < p.T; base += 64) {
+        const int t = base + lane;
+        const int n = t < p.T ? px[t] : 0;
+        const bool keep = t < p.T && 1000LL * n <= (long long)p.permille * inside;
+        const unsigned long long mask = __ballot(keep);
+        if (keep) {
+            const int j = count + (int)__popcll(mask & ((1ULL << lane) - 1ULL));
+            slots[j] = t;
+            wd[j] = p.dates[t];
+        }
+        count += (int)__popcll(mask);
+        if (t < p.T) best = min(best, ((long long)n << 32) | t);
+    }
+    if (count == 0) {                                                   // uniform: count comes from ballots
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
+        const int t = (int)(best & 0xffffffffLL);
+        if (lane == 0) { slots[0] = t; wd[0] = p.dates[t]; }
+        count = 1;
+    }
+    for (int j = count + lane; j < p.T; j += 64) { slots[j] = -1; wd[j] = 0; }     // pad_collate's layout
+    if (lane == 0) p.counts[wi] = count;
+}
+
+struct CutRawParams {
+    const void* src;            // [T][Cs][H][W] in the storage type
+    float* x;                   // [nwin][T][C][ph][pw]
+    const int* slots;           // [nwin][T] or NULL
+    int T, C, Cs, H, W, ph, pw, sy, sx, nx, first, nwin, flip;
+    int order[16];              // output channel c reads source channel order[c]
+    float mean[16], stdv[16], fill[16];
+    int normalise;
+    float pad_value;
+    int ndvi_a, ndvi_b;         // >= 0: the LAST output channel is the NDVI of source channels (a, b), not normalised
+};
+
+// Four consecutive stored elements.  16-bit: two dword loads where the address is 4-byte aligned, else element, dword,
+// element -- the address itself decides, and exactly the four elements are read either way.
+template <typename S>
+__device__ __forceinline__ void load4(const S* q, S v[4]) {
+    if constexpr (sizeof(S) == 2) {
+        if ((reinterpret_cast<uintptr_t>(q) & 3) == 0) {
+            const unsigned a = *reinterpret_cast<const unsigned*>(q), b = *reinterpret_cast<const unsigned*>(q + 2);
+            v[0] = (S)(a & 0xffffu); v[1] = (S)(a >> 16); v[2] = (S)(b & 0xffffu); v[3] = (S)(b >> 16);
+        } else {
+            const unsigned b = *reinterpret_cast<const unsigned*>(q + 1);
+            v[0] = q[0]; v[1] = (S)(b & 0xffffu); v[2] = (S)(b >> 16); v[3] = q[3];
+        }
+    } else {
+        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+    }
+}
+
+// cut_windows_kernel's work on the stored series: every thread writes 4 consecutive pixels of a window row (one 16-byte
+// store) from its 4 source elements -- a 16-bit raster row starts at any 2-byte boundary (odd W, any ox), so load4 widens
+// per address (1.9 ms against 2.85 ms with four element loads for the 144 windows of a 1098^2, T = 60 raster, even and odd
+// widths alike: profiles/raster_raw_bench.txt); a quad that reaches past the raster goes element by element.
+// Grid (quads of one window plane, C, output frames): the frame, its slot, the window origin and
+// the channel's constants are uniform over a workgroup, and a thread's own index arithmetic is 32-bit.  Output frame j of
+// a window is source frame slots[w][j]; a slot of -1 is pad_value.
+template <typename S>
+__global__ __launch_bounds__(256) void cut_windows_raw_kernel(CutRawParams p) {
+    const int qw = p.pw >> 2, quads = p.ph * qw, c = blockIdx.y;
+    const size_t plane = (size_t)p.H * p.W;
+    const bool ndvi = p.ndvi_a >= 0 && c == p.C - 1;
+    const int ca = ndvi ? p.ndvi_a : p.order[c], cb = ndvi ? p.ndvi_b : 0;
+    const float fv = p.fill[c], m = p.mean[c], sd = p.stdv[c];
+    for (int f = blockIdx.z; f < p.nwin * p.T; f += gridDim.z) {        // f = wi * T + j
+        const int wi = f / p.T, w = p.first + wi;
+        const int s = p.slots ? p.slots[f] : f - wi * p.T;
+        float4* out = reinterpret_cast<float4*>(p.x) + ((size_t)f * p.C + c) * quads;
+        if (s < 0 || s >= p.T) {
+            const float4 pad = make_float4(p.pad_value, p.pad_value, p.pad_value, p.pad_value);
+            for (int i = blockIdx.x * 256 + threadIdx.x; i < quads; i += gridDim.x * 256) out[i] = pad;
+            continue;
+        }
+        const int oy = win_origin(w / p.nx, p.H, p.ph, p.sy), ox = win_origin(w % p.nx, p.W, p.pw, p.sx);
+        const S* fa = static_cast<const S*>(p.src) + ((size_t)s * p.Cs + ca) * plane;
+        const S* fb = static_cast<const S*>(p.src) + ((size_t)s * p.Cs + cb) * plane;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < quads; i += gridDim.x * 256) {
+            const int y1 = i / qw, xq = i - y1 * qw;
+            const int sy = oy + ((p.flip & 2) ? p.ph - 1 - y1 : y1);
+            const size_t row = (size_t)sy * p.W;
+            float o[4];
+            const int lo = ox + ((p.flip & 1) ? p.pw - 4 - xq * 4 : xq * 4);   // leftmost of the 4 source columns
+            if (sy < p.H && lo + 3 < p.W) {
+                S va[4], vb[4];
+                load4(fa + row + lo, va);
+                if (ndvi) load4(fb + row + lo, vb);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int kk = (p.flip & 1) ? 3 - k : k;
+                    const float a = (float)va[kk];
+                    o[k] = ndvi ? ndvi_of(a, (float)vb[kk]) : (p.normalise ? normalised(a, m, sd) : a);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int x1 = xq * 4 + k;
+                    const int sx = ox + ((p.flip & 1) ? p.pw - 1 - x1 : x1);
+                    float v = fv;
+                    if (sy < p.H && sx < p.W) {
+                        const float a = (float)fa[row + sx];            // .astype(np.float32): exact for 16-bit ints
+                        v = ndvi ? ndvi_of(a, (float)fb[row + sx]) : (p.normalise ? normalised(a, m, sd) : a);
+                    }
+                    o[k] = v;
+                }
+            }
+            out[i] = make_float4(o[0], o[1], o[2], o[3]);
+        }
     }
 }
 
@@ -292,6 +460,83 @@ extern "C" int c2s_cut_windows(const float* series, float* x, int T, int C, int 
     const size_t quads = (size_t)nwin * T * C * ph * (pw / 4);
     hipLaunchKernelGGL(cut_windows_kernel, dim3(mover_blocks(quads)), dim3(256), 0, (hipStream_t)stream, p);
     C2S_CHECK_LAUNCH("cut_windows");
+    return C2S_OK;
+}
+
+extern "C" int c2s_window_frames(const void* src, int src_dtype, const long long* dates, int* nodata_px, int* slots, int* counts,
+                                 long long* win_dates, int T, int Cs, int H, int W, int ph, int pw, int stride_y, int stride_x,
+                                 int first_window, int nwin, float nodata, int max_nodata_permille, void* stream) {
+    C2S_REQUIRE(src && dates && nodata_px && slots && counts && win_dates, "window_frames: null pointer");
+    C2S_REQUIRE(src_dtype == C2S_SRC_F32 || src_dtype == C2S_SRC_I16 || src_dtype == C2S_SRC_U16, "window_frames: unknown src_dtype %d", src_dtype);
+    C2S_REQUIRE(((uintptr_t)src & (src_dtype == C2S_SRC_F32 ? 3 : 1)) == 0, "window_frames: src is not aligned to its element size");
+    C2S_REQUIRE(T > 0 && Cs > 0 && H > 0 && W > 0, "window_frames: bad shape (T, Cs, H, W >= 1)");
+    C2S_REQUIRE(ph >= 16 && pw >= 16 && ph % 8 == 0 && pw % 8 == 0 && (long long)ph * pw < (1LL << 30),
+                "window_frames: window sides must be multiples of 8, >= 16");
+    C2S_REQUIRE(stride_y >= 1 && stride_y <= ph && stride_x >= 1 && stride_x <= pw, "window_frames: need 1 <= stride <= patch");
+    C2S_REQUIRE(max_nodata_permille >= 0 && max_nodata_permille <= 1000, "window_frames: max_nodata_permille is in 0 .. 1000, got %d", max_nodata_permille);
+    const int ny = win_count(H, ph, stride_y), nx = win_count(W, pw, stride_x);
+    C2S_REQUIRE(first_window >= 0 && nwin > 0 && (long long)first_window + nwin <= (long long)ny * nx,
+                "window_frames: windows [%d, %d + %d) outside the %d x %d grid", first_window, first_window, nwin, ny, nx);
+    C2S_REQUIRE((long long)nwin * T < (1LL << 31), "window_frames: nwin * T must stay below 2^31 for one launch");
+    FramesParams p = {};
+    p.src = src; p.dates = dates; p.nodata_px = nodata_px; p.slots = slots; p.counts = counts; p.win_dates = win_dates;
+    p.T = T; p.Cs = Cs; p.H = H; p.W = W; p.ph = ph; p.pw = pw; p.sy = stride_y; p.sx = stride_x; p.nx = nx;
+    p.first = first_window; p.nwin = nwin; p.permille = max_nodata_permille; p.nodata = nodata;
+    const dim3 grid((unsigned)((long long)nwin * T)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    switch (src_dtype) {
+        case C2S_SRC_F32: hipLaunchKernelGGL(count_nodata_kernel<float>, grid, block, 0, st, p); break;
+        case C2S_SRC_I16: hipLaunchKernelGGL(count_nodata_kernel<short>, grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL(count_nodata_kernel<unsigned short>, grid, block, 0, st, p); break;
+    }
+    C2S_CHECK_LAUNCH("window_frames (count)");
+    hipLaunchKernelGGL(compact_frames_kernel, dim3(nwin), dim3(64), 0, st, p);
+    C2S_CHECK_LAUNCH("window_frames (compact)");
+    return C2S_OK;
+}
+
+extern "C" int c2s_cut_windows_raw(const void* src, int src_dtype, float* x, const int* slots, int T, int C, int Cs, int H, int W,
+                                   int ph, int pw, int stride_y, int stride_x, int first_window, int nwin, int flip,
+                                   const int* host_channel_order, const float* host_mean, const float* host_std,
+                                   const float* host_fill, float pad_value, int ndvi_a, int ndvi_b, void* stream) {
+    C2S_REQUIRE(src && x, "cut_windows_raw: null pointer");
+    C2S_REQUIRE(src_dtype == C2S_SRC_F32 || src_dtype == C2S_SRC_I16 || src_dtype == C2S_SRC_U16, "cut_windows_raw: unknown src_dtype %d", src_dtype);
+    C2S_REQUIRE(((uintptr_t)src & (src_dtype == C2S_SRC_F32 ? 3 : 1)) == 0, "cut_windows_raw: src is not aligned to its element size");
+    const bool ndvi = ndvi_a >= 0 || ndvi_b >= 0;
+    C2S_REQUIRE(T > 0 && C > 0 && C <= 16 && Cs > 0 && H > 0 && W > 0, "cut_windows_raw: bad shape (T, Cs, H, W >= 1, 1 <= C <= 16)");
+    C2S_REQUIRE(!ndvi || (ndvi_a >= 0 && ndvi_a < Cs && ndvi_b >= 0 && ndvi_b < Cs && C >= 2), "cut_windows_raw: NDVI source channels out of range");
+    C2S_REQUIRE(ph >= 16 && pw >= 16 && ph % 8 == 0 && pw % 8 == 0 && (long long)ph * pw < (1LL << 30),
+                "cut_windows_raw: window sides must be multiples of 8, >= 16");
+    C2S_REQUIRE(stride_y >= 1 && stride_y <= ph && stride_x >= 1 && stride_x <= pw, "cut_windows_raw: need 1 <= stride <= patch");
+    C2S_REQUIRE(flip >= 0 && flip <= 3, "cut_windows_raw: flip is a mask of 1 (x) and 2 (y)");
+    C2S_REQUIRE((host_mean == nullptr) == (host_std == nullptr), "cut_windows_raw: mean and std come together");
+    const int ny = win_count(H, ph, stride_y), nx = win_count(W, pw, stride_x);
+    C2S_REQUIRE(first_window >= 0 && nwin > 0 && (long long)first_window + nwin <= (long long)ny * nx,
+                "cut_windows_raw: windows [%d, %d + %d) outside the %d x %d grid", first_window, first_window, nwin, ny, nx);
+    C2S_REQUIRE((long long)nwin * T < (1LL << 31), "cut_windows_raw: nwin * T must stay below 2^31 for one launch");
+    CutRawParams p = {};
+    p.src = src; p.x = x; p.slots = slots; p.T = T; p.C = C; p.Cs = Cs; p.H = H; p.W = W; p.ph = ph; p.pw = pw;
+    p.sy = stride_y; p.sx = stride_x; p.nx = nx; p.first = first_window; p.nwin = nwin; p.flip = flip;
+    p.normalise = host_mean != nullptr; p.pad_value = pad_value;
+    p.ndvi_a = ndvi ? ndvi_a : -1; p.ndvi_b = ndvi ? ndvi_b : -1;
+    for (int c = 0; c < C; ++c) {
+        p.fill[c] = host_fill ? host_fill[c] : 0.f;
+        p.stdv[c] = 1.f;
+        if (ndvi && c == C - 1) continue;                               // the NDVI channel has no order / mean / std entry
+        p.order[c] = host_channel_order ? host_channel_order[c] : c;
+        C2S_REQUIRE(p.order[c] >= 0 && p.order[c] < Cs, "cut_windows_raw: channel_order entry out of range (0 .. Cs - 1)");
+        p.mean[c] = host_mean ? host_mean[c] : 0.f;
+        p.stdv[c] = host_std ? host_std[c] : 1.f;
+    }
+    const int frames = nwin * T, xblocks = cdiv(ph * (pw / 4), 256);
+    const dim3 grid(xblocks > 4 ? 4 : xblocks, C, frames > 65535 ? 65535 : frames), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    switch (src_dtype) {
+        case C2S_SRC_F32: hipLaunchKernelGGL(cut_windows_raw_kernel<float>, grid, block, 0, st, p); break;
+        case C2S_SRC_I16: hipLaunchKernelGGL(cut_windows_raw_kernel<short>, grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL(cut_windows_raw_kernel<unsigned short>, grid, block, 0, st, p); break;
+    }
+    C2S_CHECK_LAUNCH("cut_windows_raw");
     return C2S_OK;
 }
 

@@ -805,11 +805,40 @@ int c2s_softmax_stitch(const float* logits, float* proba, long long* top1, int f
  *     batch size.  acc and wsum start at 0 (c2s_fill); pixels no window of the batch covers are not written.  K <= 32.
  *   c2s_blend_finish: in place proba_k = acc_k / wsum (IEEE divide); top1 [H,W] int64 = first maximum of the
  *     probabilities (may be NULL).
+ *   The same windows from the STORED series: src [T,Cs,H,W] in C2S_SRC_F32 / _I16 / _U16, device or host-pinned memory as
+ *   for c2s_collate_series; every per-window array is indexed relative to first_window, as x is; size_t indexing.
+ *   c2s_window_frames: which frames each window keeps (all integer, all exact).  For window w at (oy, ox):
+ *     inside(w) = min(ph, H - oy) * min(pw, W - ox) (pixels beyond a raster smaller than the window do not count);
+ *     nodata_px[w,t] = inside pixels where src[t,cs,y,x] == nodata for EVERY cs (float(v) == nodata: exact for the 16-bit
+ *     types, so the comparison is the integer one; a NaN nodata matches nothing).  Frame t is kept iff
+ *     1000 * nodata_px[w,t] <= max_nodata_permille * inside(w) (64-bit products, permille in 0 .. 1000); a window that
+ *     would keep none keeps exactly one, the t with the smallest nodata_px, lowest t on a tie.  counts[w] = kept frames;
+ *     slots[w,j] = the j-th kept t ascending for j < counts[w], -1 after; win_dates[w,j] = dates[slots[w,j]] or 0
+ *     (pad_collate's layout; dates int64 [T], device-accessible).  nodata_px, slots [nwin,T] int32, counts [nwin] int32,
+ *     win_dates [nwin,T] int64.  Two launches, no atomics: a block-reduced count per (w, t), then one wave per window
+ *     compacting T in chunks of 64 lanes (any T >= 1).  ph, pw as c2s_cut_windows; nwin * T < 2^31.
+ *   c2s_cut_windows_raw: cut + convert + re-order + normalise (+ NDVI) + compact in one pass: x [nwin,T,C,ph,pw];
+ *     output frame j of window w is source frame s = slots[w,j] (slots NULL: s = j), read at the (optionally mirrored)
+ *     position of c2s_cut_windows; x = (float(src[s,order[c]]) - mean[c]) / std[c], the arithmetic of c2s_collate_series
+ *     (mean / std both NULL: no normalisation); with ndvi_a >= 0 the LAST output channel is the NDVI of the raw channels
+ *     (ndvi_a, ndvi_b) by c2s_collate_series_ndvi's rule, and channel_order / mean / std describe the first C - 1.  A
+ *     position outside the raster takes host_fill[c] (output space, NULL = 0); a frame with s = -1 is pad_value everywhere,
+ *     outside the raster too, so that the model's frame flags drop it.  C <= 16; order entries and NDVI channels in
+ *     0 .. Cs - 1; ph, pw multiples of 8, >= 16; nwin * T < 2^31.  One 16-byte store per thread; a 16-bit raster row starts
+ *     at any 2-byte boundary, so the four source elements come from two dword loads where their address is 4-byte aligned
+ *     and from element, dword, element where it is not (the address decides; never a byte outside the four elements).
  * ------------------------------------------------------------------------------------------------ */
 int c2s_window_count(int size, int patch, int stride);
 int c2s_window_origin(int i, int size, int patch, int stride);
 int c2s_cut_windows(const float* series, float* x, int T, int C, int H, int W, int ph, int pw, int stride_y, int stride_x,
                     int first_window, int nwin, int flip, const float* host_fill, void* stream);
+int c2s_window_frames(const void* src, int src_dtype, const long long* dates, int* nodata_px, int* slots, int* counts,
+                      long long* win_dates, int T, int Cs, int H, int W, int ph, int pw, int stride_y, int stride_x,
+                      int first_window, int nwin, float nodata, int max_nodata_permille, void* stream);
+int c2s_cut_windows_raw(const void* src, int src_dtype, float* x, const int* slots, int T, int C, int Cs, int H, int W, int ph,
+                        int pw, int stride_y, int stride_x, int first_window, int nwin, int flip,
+                        const int* host_channel_order, const float* host_mean, const float* host_std,
+                        const float* host_fill, float pad_value, int ndvi_a, int ndvi_b, void* stream);
 int c2s_softmax_blend(const float* logits, float* acc, float* wsum, const float* wy, const float* wx, int first_window,
                       int nwin, int K, int ph, int pw, int H, int W, int stride_y, int stride_x, int flip, void* stream);
 int c2s_blend_finish(float* acc_proba, const float* wsum, long long* top1, int K, int H, int W, void* stream);

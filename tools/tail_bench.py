@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the kernels either side of the hot path at the sizes the reference uses:
 HIP-event time per call and algorithmic bytes / time against the 8 TB/s HBM peak.
-Usage (GPU box): python tools/tail_bench.py [--reps 20]"""
+Usage (GPU box): python tools/tail_bench.py [--reps 20] [--only raster_raw]"""
 import argparse
 import math
 import os
@@ -38,10 +38,105 @@ def line(name, ms, nbytes, note=""):
     print(f"{name:44s} {ms * 1e3:9.1f} us  {nbytes / 1e6:9.1f} MB  {tb:5.2f} TB/s ({100 * tb / 8:4.1f} % of 8 TB/s) {note}")
 
 
+def spread(fn, reps):
+    """(median, min, max) of `reps` device-timed calls after one warm-up, and the peak of torch's allocator over them."""
+    fn()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1], torch.cuda.max_memory_allocated()
+
+
+def raster_raw(reps):
+    """N3 on the STORED series: 1098^2, T = 60, 10 uint16 bands, 144 windows of 128 every 96 pixels, batches of 24.
+    (i) what a caller had to do before c2s_cut_windows_raw: normalise the whole raster to fp32 on the device (the collate
+    kernel, the raster as one series), then the fp32 predict_raster; (ii) the raw path; (iii) the raw path with nodata = 0."""
+    import ctypes as C
+    import crop2seg_amd as C2S
+    from crop2seg_amd.inference import predict_raster, window_frames, window_origins
+    L = _lib.lib()
+    dev = torch.device("cuda")
+    R, T, Kr, P, S, BS = 1098, 60, 20, 128, 96, 24
+    rng = np.random.default_rng(1)
+    mean = rng.uniform(500, 3000, 10).astype(np.float32)
+    std = rng.uniform(300, 2000, 10).astype(np.float32)
+    raw = torch.from_numpy(rng.integers(1, 10000, size=(T, 10, R, R), dtype=np.uint16)).to(dev)
+    dates = 5 * torch.arange(T, device=dev)
+    net = C2S.TimeUNet_v1(input_dim=10, out_conv=[32, Kr]).cuda()
+    net.apply(C2S.weight_init)
+    net.eval()
+    stream = torch.cuda.current_stream().cuda_stream
+    order_a = (C.c_int * 10)(*CHANNELS_LIKE_PASTIS)
+    mean_a, std_a = mean.ctypes.data_as(C.POINTER(C.c_float)), std.ctypes.data_as(C.POINTER(C.c_float))
+    offsets = torch.tensor([0, T], dtype=torch.int64, device=dev)
+    base = torch.cuda.memory_allocated()
+    copy = T * 10 * R * R * 4
+    print(f"N3 raw: stored uint16 raster {raw.numel() * 2 / 1e6:.0f} MB, its fp32 copy {copy / 1e6:.0f} MB; allocated before the rows "
+          f"{base / 1e6:.0f} MB (the stored raster, the model)")
+
+    def normalise():
+        x = torch.empty(T, 10, R, R, device=dev)
+        _lib.check(L.c2s_collate_series(raw.data_ptr(), _lib.SRC_U16, offsets.data_ptr(), None, x.data_ptr(), None, None, 1, T, 10,
+                                        10, R * R, order_a, mean_a, std_a, 0.0, stream), "collate_series")
+        return x
+
+    kw = dict(patch=P, stride=S, batch_size=BS)
+    raw_kw = dict(channel_order=CHANNELS_LIKE_PASTIS, mean=mean, std=std, **kw)
+    ms_n = timed(normalise, reps)
+    x32 = normalise()
+    part = spread(lambda: predict_raster(net, x32, dates, **kw), reps)
+    del x32
+    rows = [("(i) normalise to fp32 + fp32 predict_raster", spread(lambda: predict_raster(net, normalise(), dates, **kw), reps)),
+            ("(ii) raw predict_raster", spread(lambda: predict_raster(net, raw, dates, **raw_kw), reps)),
+            ("(iii) raw predict_raster, nodata=0", spread(lambda: predict_raster(net, raw, dates, nodata=0, **raw_kw), reps))]
+    print(f"{'    normalise alone (c2s_collate_series)':48s} {ms_n:8.2f} ms")
+    print(f"{'    fp32 predict_raster alone':48s} {part[0]:8.2f} ms  (min {part[1]:.2f}, max {part[2]:.2f} of {reps})")
+    for name, (med, lo, hi, peak) in rows:
+        print(f"{'N3 raw ' + name:48s} {med:8.2f} ms  (min {lo:.2f}, max {hi:.2f} of {reps})  peak {peak / 1e6:8.0f} MB "
+              f"({(peak - base) / 1e6:6.0f} MB above the stored raster and the model)")
+    print(f"    peak (i) - peak (ii) = {(rows[0][1][3] - rows[1][1][3]) / 1e6:.0f} MB; the fp32 copy is {copy / 1e6:.0f} MB")
+
+    # the kernels alone, all 144 windows in batches of 24
+    nwin = len(window_origins(R, P, S)) ** 2
+    xb = torch.empty(BS, T, 10, P, P, device=dev)
+    x32 = normalise()
+
+    def cut32():
+        for first in range(0, nwin, BS):
+            _lib.check(L.c2s_cut_windows(x32.data_ptr(), xb.data_ptr(), T, 10, R, R, P, P, S, S, first, min(BS, nwin - first), 0,
+                                         None, stream), "cut_windows")
+
+    def cut16(slots=None):
+        for first in range(0, nwin, BS):
+            _lib.check(L.c2s_cut_windows_raw(raw.data_ptr(), _lib.SRC_U16, xb.data_ptr(), None if slots is None else slots[first:].data_ptr(),
+                                             T, 10, 10, R, R, P, P, S, S, first, min(BS, nwin - first), 0, order_a, mean_a, std_a,
+                                             None, 0.0, -1, -1, stream), "cut_windows_raw")
+    out_b = nwin * xb[0].numel() * 4
+    note = "(raster read once + windows written)"
+    line(f"N3 c2s_cut_windows (fp32 raster), {nwin} windows", timed(cut32, reps), x32.numel() * 4 + out_b, note)
+    line(f"N3 c2s_cut_windows_raw (uint16), {nwin} windows", timed(cut16, reps), raw.numel() * 2 + out_b, note)
+    slots = window_frames(raw, dates, P, S, 0, 0)[0]
+    line(f"N3 c2s_cut_windows_raw with slots, {nwin} windows", timed(lambda: cut16(slots), reps), raw.numel() * 2 + out_b, note)
+    line("N3 c2s_window_frames, all windows", timed(lambda: window_frames(raw, dates, P, S, 0, 0), reps), R * R * T * 2,
+         "(channel 0 of the raster read once; the call allocates its 4 small outputs)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--only", choices=["all", "raster_raw"], default="all", help="raster_raw: only the rows on the stored series")
     a = ap.parse_args()
+    if a.only == "raster_raw":
+        raster_raw(max(3, a.reps // 4))
+        return
     dev = torch.device("cuda")
     rng = np.random.default_rng(0)
     K, H = 15, 128
@@ -165,6 +260,8 @@ def main():
     # batches of 20 leave a last batch of 4 windows; 24 divides 144
     ms_24 = timed(lambda: predict_raster(net, series, dates1, patch=P, stride=S, batch_size=24), 3)
     print(f"{'N3 predict_raster, batch_size 24 (6 full batches)':44s} {ms_24:9.1f} ms   ratio {ms_24 / ms_t:5.2f}")
+    del net, series, tiles
+    raster_raw(max(3, a.reps // 4))
 
 
 if __name__ == "__main__":
