@@ -163,6 +163,8 @@ SIGNATURES = {
     "c2s_smooth_ce_workspace_floats": (SZ, []),
     "c2s_smooth_ce": (I, [P, P, P, P, P, P, I, I, I, I, F, C.c_longlong, I, P, SZ, P]),
     "c2s_smooth_ce_ex": (I, [P, P, P, P, P, P, P, I, I, I, I, F, C.c_longlong, I, I, P, SZ, P]),
+    "c2s_recall_ce_workspace_floats": (SZ, [I, I]),
+    "c2s_recall_ce": (I, [P, P, P, P, P, P, I, I, I, C.c_longlong, I, P, SZ, P]),
     "c2s_parcel_seeds": (I, [P, P, P, P, I, I, I, I, I, I, F, P]),
     "c2s_label_components_workspace_bytes": (SZ, [I, I, I]),
     "c2s_label_components": (I, [P, P, P, I, I, I, I, P, SZ, P, P]),

@@ -1,8 +1,11 @@
 """Boundary-loss pieces of the reference's training loop as HIP kernels.
 
 Reference: src/learning/utils.py:198-222 (get_dilated), :283-285 (y_b), :318-324 (loss = CE + focal on the boundary
-head), src/learning/focal_loss.py:7-44 (FocalCELoss), src/learning/smooth_loss.py:18-84 (SmoothCrossEntropy2D).  No autograd graph: `focal_ce` returns the loss and, on request,
-dL/dlogits -- the train step feeds that into the engine's tape.
+head), src/learning/focal_loss.py:7-44 (FocalCELoss), src/learning/smooth_loss.py:18-84 (SmoothCrossEntropy2D),
+src/learning/recall_loss.py:8-50 (RecallCrossEntropy).  No autograd graph: `focal_ce` returns the loss and, on request,
+dL/dlogits -- the train step feeds that into the engine's tape.  The three classes share one protocol,
+criterion(logits, target, want_grad=False) -> device scalar and grad() -> dL/dlogits of the last call with want_grad=True,
+which is what TrainStep(criterion=...) takes as its main loss (learning/utils.py).
 """
 from __future__ import annotations
 
@@ -59,8 +62,8 @@ def focal_ce(logits: Tensor, target: Tensor, gamma: float = 1.0, ignore_index: i
 
 class FocalCELoss:
     """Call-compatible with the reference's module (focal_loss.py:7-45: gamma, size_average, ignore_index, weight); the value
-    carries no autograd graph -- `grad()` returns dL/dlogits of the last call with want_grad=True, and
-    TrainStep(add_boundary_loss=True) is the training route."""
+    carries no autograd graph -- `grad()` returns dL/dlogits of the last call with want_grad=True; the training routes are a
+    model built with add_boundary_loss=True (the boundary head) and TrainStep(criterion=FocalCELoss(...)) (the main loss)."""
 
     def __init__(self, gamma: float = 1.0, size_average: bool = True, ignore_index: int = -100, weight: Optional[Tensor] = None):
         self.gamma, self.size_average, self.ignore_index, self.weight = gamma, bool(size_average), ignore_index, weight
@@ -170,3 +173,88 @@ class SmoothCrossEntropy2D:
     def check_targets(self) -> None:
         if self._last is not None and float(self._last[1][1]) != 0.0:
             raise ValueError(f"SmoothCrossEntropy2D: {int(float(self._last[1][1]))} target labels outside [0, n_classes)")
+
+
+RECALL_MAX_CLASSES = 32                                                      # csrc/recall.hip: MAXK
+
+
+def recall_ce(logits: Tensor, target: Tensor, ignore_index: int = 255, want_grad: bool = False,
+              ws: Optional[E.Workspace] = None, loss_out: Optional[Tensor] = None
+              ) -> Tuple[Tensor, Optional[Tensor], Tensor, Tensor]:
+    """RecallCrossEntropy(K, ignore_index)(logits [B,K,H,W], target [B,H,W]) (recall_loss.py:8-50): cross entropy weighted per
+    class by the batch's false-negative share, w_c = max(fn_c, 1) / max(gt_c, 1), mean over ALL B*H*W pixels.  Returns
+    (loss[1], dlogits | None, weights[K], counts[2,K] int64: gt and fn before the floor).  With `loss_out` the value is ADDED to
+    that tensor.  Stream-ordered, no host synchronisation; the statement of the rule and the deviations from the reference are in
+    include/c2s_hip.h and DESIGN.md section 7."""
+    if not logits.is_cuda:
+        raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
+    logits = logits.contiguous()
+    target = target.to(torch.int64).contiguous()
+    B, K = logits.shape[:2]
+    if not 1 <= K <= RECALL_MAX_CLASSES:
+        raise ValueError(f"recall_ce: {K} classes, the kernels take 1 to {RECALL_MAX_CLASSES}")
+    HW = logits[0, 0].numel()
+    ws = ws or E.Workspace(logits.device)
+    w = ws.get("recall", lib().c2s_recall_ce_workspace_floats(B, HW))
+    loss = loss_out if loss_out is not None else torch.empty(1, device=logits.device, dtype=torch.float32)
+    gl = torch.empty_like(logits) if want_grad else None
+    weights = torch.empty(K, device=logits.device, dtype=torch.float32)
+    counts = torch.empty(2, K, device=logits.device, dtype=torch.int64)
+    check(lib().c2s_recall_ce(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), E._ptr(gl), weights.data_ptr(),
+                              counts.data_ptr(), B, K, HW, int(ignore_index), 1 if loss_out is not None else 0, w.data_ptr(),
+                              w.numel(), E._stream()), "recall_ce")
+    return loss, gl, weights, counts
+
+
+def recall_bad_targets(ws: E.Workspace, B: int, HW: int) -> Tensor:
+    """The bad-label counter of the last recall_ce call of this shape on `ws` (a device value: reading it synchronises)."""
+    n = lib().c2s_recall_ce_workspace_floats(B, HW)
+    return ws.bufs["recall"][n - 1:n]
+
+
+class RecallCrossEntropy:
+    """Call-compatible with the reference's criterion (recall_loss.py:8-50; n_classes, ignore_index): cross entropy weighted
+    per class by the false-negative share of the batch at hand, the criterion for rare classes.  Same protocol as FocalCELoss
+    and SmoothCrossEntropy2D: the value carries no autograd graph, `grad()` returns dL/dlogits of the last call with
+    want_grad=True, and TrainStep(criterion=RecallCrossEntropy(...)) is the training route.  `class_weights()` and `counts()`
+    are the last call's w[K] and (gt, fn)[2,K] on the device; `bad_target_count()` / `check_targets()` read the number of labels
+    outside [0, n_classes) other than ignore_index (host synchronisation).  Every batch has a value, any ignore_index works
+    and class 1 is a class like the others: where the reference differs, see DESIGN.md section 7.  Under data parallelism each
+    rank weighs by the recall of its own batch, as the reference does under torch DDP."""
+
+    def __init__(self, n_classes: int = 19, ignore_index: int = 255):
+        if not 1 <= int(n_classes) <= RECALL_MAX_CLASSES:
+            raise ValueError(f"RecallCrossEntropy: n_classes = {n_classes}, the kernels take 1 to {RECALL_MAX_CLASSES} classes")
+        self.n_classes, self.ignore_index = int(n_classes), int(ignore_index)
+        self._ws: Optional[E.Workspace] = None
+        self._last = None
+
+    def __call__(self, input: Tensor, target: Tensor, want_grad: bool = False) -> Tensor:
+        if input.dim() < 2 or input.shape[1] != self.n_classes:
+            raise ValueError(f"RecallCrossEntropy: built for {self.n_classes} classes, the logits have shape {tuple(input.shape)}")
+        if self._ws is None or self._ws.device != input.device:
+            self._ws = E.Workspace(input.device)
+        loss, gl, weights, counts = recall_ce(input, target, self.ignore_index, want_grad, self._ws)
+        self._last = (gl, weights, counts, input.shape[0], input[0, 0].numel())
+        return loss[0]
+
+    forward = __call__
+
+    def grad(self) -> Optional[Tensor]:
+        return None if self._last is None else self._last[0]
+
+    def class_weights(self) -> Optional[Tensor]:
+        return None if self._last is None else self._last[1]
+
+    def counts(self) -> Optional[Tensor]:
+        return None if self._last is None else self._last[2]
+
+    def bad_target_count(self) -> int:
+        if self._last is None:
+            return 0
+        return int(float(recall_bad_targets(self._ws, self._last[3], self._last[4])))
+
+    def check_targets(self) -> None:
+        n = self.bad_target_count()
+        if n:
+            raise ValueError(f"RecallCrossEntropy: {n} target labels outside [0, n_classes) other than ignore_index")

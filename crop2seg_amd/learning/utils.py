@@ -144,13 +144,28 @@ class TrainStep:
     parameter is frozen does not count against it).  Nothing inside a step, eager or replayed, synchronises with the host; the
     readers do: `last_grad_norm` / `last_clip_coef` (device scalars of the last decided step), `skipped_steps()`,
     `sync_steps()`.  Until `sync_steps()` the host's `param_steps` / `step_count` count a skipped step as taken.
+
+    `criterion` (the reference's iterate(..., criterion=criterion), train.py:466-474,488).  None: the weighted, label-smoothed
+    cross entropy above, launch for launch what the step ran before the argument existed.  Otherwise any object with
+    criterion(logits, y, want_grad=True) -> scalar float32 device tensor and grad() -> dL/dlogits: FocalCELoss,
+    SmoothCrossEntropy2D (not with reduction='none') and RecallCrossEntropy of learning/losses.py as they are.  The criterion
+    then decides about ignored labels and class weights; num_classes / ignore_index / label_smoothing of this constructor
+    belong to the default loss only.  It runs eagerly and inside capture() / replay() (it must not synchronise with the
+    host).  Data parallel: every rank evaluates the criterion on its own batch -- RecallCrossEntropy weighs by the recall of
+    the rank's batch, which is what the reference does under torch DDP; the gradients are averaged as always.
     """
 
     def __init__(self, model, num_classes: int = 15, ignore_index: int = -1, lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, process_group=None,
                  distributed: bool = False, label_smoothing: float = 0.0, boundary_gamma: float = 2.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, criterion=None):
         self.model = model
+        if criterion is not None:
+            if not callable(criterion) or not callable(getattr(criterion, "grad", None)):
+                raise TypeError("TrainStep: criterion must be callable as criterion(logits, y, want_grad=True) and have grad()")
+            if getattr(criterion, "reduction", "mean") == "none":
+                raise ValueError("TrainStep: a criterion with reduction='none' has no scalar loss to train on")
+        self.criterion = criterion
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError(f"TrainStep: max_grad_norm must be positive or None, got {max_grad_norm!r}")
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -320,7 +335,10 @@ class TrainStep:
             ctx.early_hook = early_exchange
         out = Fn.FORWARDS[model.spec.model](ctx, model.spec, x, dates, drop)
         logits = out.logits
-        loss, glogits = E.cross_entropy(logits, y, self.class_w, self.ws, want_grad=True, label_smoothing=self.label_smoothing)
+        if self.criterion is None:
+            loss, glogits = E.cross_entropy(logits, y, self.class_w, self.ws, want_grad=True, label_smoothing=self.label_smoothing)
+        else:
+            loss, glogits = self._criterion_loss(logits, y)
         tape.grads[logits.data_ptr()] = glogits
         if out.boundary is not None:
             # src/learning/utils.py:283-285,318-324: y_b from the dilated one-hot labels, loss = CE + FocalCE(out_b, y_b)
@@ -337,11 +355,27 @@ class TrainStep:
                 self.grads[n].zero_()
         return loss, logits
 
+    def _criterion_loss(self, logits: Tensor, y: Tensor) -> Tuple[Tensor, Tensor]:
+        """The main loss from `self.criterion` (iterate(..., criterion=criterion), train.py:466-474,488): the value as a [1]
+        view of the criterion's own device scalar -- the boundary head's focal_ce(loss_out=loss) adds onto it -- and
+        dL/dlogits from grad().  A criterion that hands back no gradient is an error, never a reason to fall back."""
+        value = self.criterion(logits, y, want_grad=True)
+        glogits = self.criterion.grad()
+        if not torch.is_tensor(value) or value.numel() != 1 or value.device != logits.device or value.dtype != torch.float32:
+            raise RuntimeError("TrainStep: criterion(logits, y, want_grad=True) must return one float32 value on the logits' device")
+        if glogits is None or glogits.shape != logits.shape or glogits.dtype != torch.float32 or not glogits.is_contiguous():
+            raise RuntimeError("TrainStep: criterion.grad() must return a contiguous float32 dL/dlogits of the logits' shape")
+        return value.reshape(1), glogits
+
     def bad_targets(self) -> int:
         """Labels outside [0, num_classes) (other than ignore_index) in the last step's batch: torch's CrossEntropyLoss raises on
         them, the loss kernel skips and counts them -- call this every display_step to surface a mislabelled dataset
-        (host synchronisation).  Also the place where a failed one-pass normalisation wait surfaces (`check_health`)."""
-        n = E.bad_target_count(self.ws)
+        (host synchronisation).  With a criterion that has bad_target_count() the count is the criterion's.  Also the place
+        where a failed one-pass normalisation wait surfaces (`check_health`)."""
+        if self.criterion is not None and hasattr(self.criterion, "bad_target_count"):
+            n = int(self.criterion.bad_target_count())
+        else:
+            n = E.bad_target_count(self.ws)
         self.check_health()
         return n
 

@@ -681,6 +681,22 @@ int c2s_smooth_ce(const float* logits, const long long* target, const float* cla
 int c2s_smooth_ce_ex(const float* logits, const long long* target, const float* class_w, const float* bg_distrib, float* loss,
                      float* glogits, float* pixel_loss, int B, int K, int H, int W, float label_smoothing, long long bg_index,
                      int reduction, int accumulate_loss, float* workspace, size_t ws_floats, void* stream);
+/* RecallCrossEntropy (recall_loss.py:8-50): cross entropy weighted per class by the batch's false-negative share.  A pixel
+ * is valid when its target lies in [0, K) and is not ignore_index (any value; a class in [0, K) is then simply not valid);
+ * pred = the first maximum over the classes, NaN counting as the maximum (c2s_metrics_update's rule);
+ *   gt_c = valid pixels with t = c, fn_c = those of them with pred != c, w_c = (float)((double)max(fn_c,1) / (double)max(gt_c,1))
+ *   loss = (1 / (B*HW)) sum over the valid pixels of w_t (lse(z) - z_t): the mean runs over ALL B*HW pixels (:48-50)
+ *   glogits (may be NULL) = (w_t / (B*HW)) (p_k - [k = t]) on valid pixels, 0 elsewhere (the weights are constants).
+ * accumulate_loss != 0 adds the value to *loss.  weights_out [K] and counts_out [2][K] (int64: gt, fn, before the floor at 1)
+ * may be NULL.  Targets outside [0, K) other than ignore_index are skipped and COUNTED: the last float of the
+ * c2s_recall_ce_workspace_floats(B, HW) floats holds their number after the call, the one before it the sum of w_t nll.  With
+ * no valid pixel the loss and the gradient are 0.  K <= 32.  Integer atomics only (LDS histograms, 64-bit global
+ * counters zeroed by a kernel of the call): bit-exact, order independent, reproducible from run to run, and legal inside a
+ * hipGraph capture.  Deviations from the reference's behaviour: DESIGN.md section 7. */
+size_t c2s_recall_ce_workspace_floats(int B, int HW);
+int c2s_recall_ce(const float* logits, const long long* target, float* loss, float* glogits, float* weights_out,
+                  long long* counts_out, int B, int K, int HW, long long ignore_index, int accumulate_loss,
+                  float* workspace, size_t ws_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Parcel homogenisation of predictions: the raster restatement of src/helpers/postprocess.py:377-604 (homogenize,
