@@ -44,6 +44,12 @@ int c2s_cus();   // compute units of the current device (256 when no device is p
     } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of 256 threads for a grid-stride loop over n elements, at most `cap`.  No default: a cap is behaviour (the number
+// of block partials fixes the bits of a loss), so every call site states its own.
+static inline int grid_for(long n, int cap) {
+    long b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -73,6 +79,9 @@ __device__ __forceinline__ void adam_element(float* __restrict__ p, const float*
 }
 // taps of the largest packed kernel (the 6x6 stride-2 convolutions): tap tables of the weight packs and slice sums
 constexpr int C2S_MAX_TAPS = 36;
+// classes of the kernels that keep a per-class table on chip (the reference uses 15; PASTIS 20): the confusion matrices of
+// metrics.hip, the class mask and the registers of loss.hip, the votes of parcels.hip
+constexpr int C2S_MAX_CLASSES = 32;
 
 // Packed Winograd layouts: written by pack.hip, read by the convolution kernels named
 constexpr int WN_CK = 8;                            // conv_winograd.hip: input channels per chunk

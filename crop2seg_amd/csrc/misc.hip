@@ -1,5 +1,5 @@
-// Small kernels of the hot path: frame flags, depthwise convolution (W-TAE), cross-entropy, flat Adam,
-// fill / add.  All HBM- or latency-bound; see DESIGN.md for the per-kernel roofline notes.
+// Small kernels of the hot path: frame flags, depthwise convolution (W-TAE), flat Adam, fill / add.  All HBM- or
+// latency-bound; see DESIGN.md for the per-kernel roofline notes.
 #include <stdarg.h>
 #include <atomic>
 #include <mutex>
@@ -387,97 +387,6 @@ __global__ __launch_bounds__(64) void dw_wgrad_reduce_kernel(const float* __rest
     if (threadIdx.x == 0) gw[i] = (float)s;
 }
 
-// ---------------------------------------------------------------- cross entropy (train.py:463-468)
-// nn.CrossEntropyLoss(weight=w, label_smoothing=eps), reduction "mean" (torch semantics with class weights):
-//   loss_i = (1-eps) w[y_i] (-log p_i[y_i]) + (eps/K) sum_k w[k] (-log p_i[k]);  loss = sum_i loss_i / sum_i w[y_i]
-// Pixels whose target equals ignore_index (torch default -100) contribute to neither sum.  A target outside [0,K) that is
-// not ignore_index makes torch raise (device assert); here it is treated like ignore_index -- no out-of-bounds read.
-// per block partial (sum loss_i, sum w) -> ws[2*blocks]; finalize -> ws_tot[2]; grad kernel uses ws_tot[1]
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                     const float* __restrict__ cw, float* __restrict__ part, int B, int K,
-                                                     int HW, float eps, long long ignore_index) {
-    __shared__ float red[4][3];
-    const long total = (long)B * HW;
-    float num = 0.f, den = 0.f, bad = 0.f;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const long long yy = target[e];
-        if (yy == ignore_index) continue;
-        if (yy < 0 || yy >= K) { bad += 1.f; continue; }     // torch raises (device assert); here: skipped and counted
-        const int y = (int)yy;
-        const int pix = (int)(e % HW), b = (int)(e / HW);
-        const float* lp = logits + (size_t)b * K * HW + pix;
-        float mx = lp[0];
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, lp[(size_t)k * HW]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += __expf(lp[(size_t)k * HW] - mx);
-        const float w = cw[y];
-        const float lse = mx + __logf(s);
-        float li = w * (lse - lp[(size_t)y * HW]);
-        if (eps > 0.f) {
-            float sm = 0.f;
-            for (int k = 0; k < K; ++k) sm += cw[k] * (lse - lp[(size_t)k * HW]);
-            li = (1.f - eps) * li + (eps / (float)K) * sm;
-        }
-        num += li;
-        den += w;
-    }
-    num = wave_sum(num); den = wave_sum(den); bad = wave_sum(bad);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = num; red[threadIdx.x >> 6][1] = den; red[threadIdx.x >> 6][2] = bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[blockIdx.x * 3] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        part[blockIdx.x * 3 + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        part[blockIdx.x * 3 + 2] = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
-    }
-}
-
-__global__ void ce_finalize_kernel(const float* __restrict__ part, float* __restrict__ tot, float* __restrict__ loss,
-                                   int blocks) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double num = 0, den = 0, bad = 0;
-    for (int i = 0; i < blocks; ++i) { num += part[i * 3]; den += part[i * 3 + 1]; bad += part[i * 3 + 2]; }
-    tot[0] = (float)num; tot[1] = (float)den; tot[2] = (float)bad;
-    *loss = (float)(num / den);
-}
-
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                     const float* __restrict__ cw, const float* __restrict__ tot,
-                                                     float* __restrict__ glogits, int B, int K, int HW, float eps,
-                                                     long long ignore_index) {
-    const long total = (long)B * HW;
-    const float inv_den = 1.f / tot[1];
-    float wsum = 0.f;
-    if (eps > 0.f)
-        for (int k = 0; k < K; ++k) wsum += cw[k];
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int pix = (int)(e % HW), b = (int)(e / HW);
-        const float* lp = logits + (size_t)b * K * HW + pix;
-        float* gp = glogits + (size_t)b * K * HW + pix;
-        const long long yy = target[e];
-        if (yy == ignore_index || yy < 0 || yy >= K) {
-            for (int k = 0; k < K; ++k) gp[(size_t)k * HW] = 0.f;
-            continue;
-        }
-        const int y = (int)yy;
-        float mx = lp[0];
-        for (int k = 1; k < K; ++k) mx = fmaxf(mx, lp[(size_t)k * HW]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += __expf(lp[(size_t)k * HW] - mx);
-        const float w = cw[y] * inv_den, inv_s = 1.f / s;
-        if (eps > 0.f) {
-            // (1-eps) w_y (p_k - delta_ky) + (eps/K) (W p_k - w_k), all over sum_i w[y_i]
-            const float a = (1.f - eps) * w, c = eps / (float)K * inv_den;
-            for (int k = 0; k < K; ++k) {
-                const float pk = __expf(lp[(size_t)k * HW] - mx) * inv_s;
-                gp[(size_t)k * HW] = a * (pk - (k == y ? 1.f : 0.f)) + c * (wsum * pk - cw[k]);
-            }
-        } else {
-            for (int k = 0; k < K; ++k)
-                gp[(size_t)k * HW] = w * (__expf(lp[(size_t)k * HW] - mx) * inv_s - (k == y ? 1.f : 0.f));
-        }
-    }
-}
-
 // ---------------------------------------------------------------- Adam (train.py:454, torch defaults)
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n, float lr, float b1, float b2, float eps, int step,
@@ -496,12 +405,6 @@ __global__ void fill_kernel(float* p, long n, float v) {
 __global__ void add_kernel(float* __restrict__ d, const float* __restrict__ s, long n) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) d[i] += s[i];
 }
-
-inline int grid_for(long n, int cap = 4096) {
-    long b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-constexpr int CE_BLOCKS = 512;
 
 }  // namespace
 
@@ -619,33 +522,6 @@ extern "C" int c2s_dwconv_wgrad(const float* in, const float* gout, float* parti
     return C2S_OK;
 }
 
-extern "C" size_t c2s_cross_entropy_workspace_floats(int B, int HW) {
-    (void)B; (void)HW;
-    return 3 * CE_BLOCKS + 3;
-}
-
-extern "C" int c2s_cross_entropy(const float* logits, const int64_t* target, const float* class_w, float* loss,
-                                 float* glogits, int B, int K, int HW, float label_smoothing, long long ignore_index,
-                                 float* workspace, size_t ws_floats, void* stream) {
-    C2S_REQUIRE(logits && target && class_w && loss && workspace, "cross_entropy: null pointer");
-    C2S_REQUIRE(ws_floats >= 3 * CE_BLOCKS + 3 && B > 0 && K > 0 && HW > 0, "cross_entropy: bad args");
-    C2S_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, "cross_entropy: label_smoothing must be in [0, 1]");
-    hipStream_t st = (hipStream_t)stream;
-    const int blocks = grid_for((long)B * HW, CE_BLOCKS);
-    float* tot = workspace + 3 * CE_BLOCKS;      // (sum, weight sum, targets outside [0,K) other than ignore_index)
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(blocks), dim3(256), 0, st, logits, target, class_w, workspace, B, K, HW,
-                       label_smoothing, ignore_index);
-    C2S_CHECK_LAUNCH("ce_fwd");
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, tot, loss, blocks);
-    C2S_CHECK_LAUNCH("ce_finalize");
-    if (glogits != nullptr) {
-        hipLaunchKernelGGL(ce_bwd_kernel, dim3(blocks), dim3(256), 0, st, logits, target, class_w, tot, glogits, B, K, HW,
-                           label_smoothing, ignore_index);
-        C2S_CHECK_LAUNCH("ce_bwd");
-    }
-    return C2S_OK;
-}
-
 extern "C" int c2s_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
                              float eps, int step, const int* step_dev, float grad_scale, void* stream) {
     C2S_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_dev != nullptr), "adam: bad args");
@@ -658,7 +534,7 @@ extern "C" int c2s_adam_flat(float* p, const float* g, float* m, float* v, long 
 extern "C" int c2s_fill(float* p, long n, float v, void* stream) {
     C2S_REQUIRE(p && n >= 0, "fill: bad args");
     if (n == 0) return C2S_OK;
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, n, v);
+    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n, 4096)), dim3(256), 0, (hipStream_t)stream, p, n, v);
     C2S_CHECK_LAUNCH("fill");
     return C2S_OK;
 }
@@ -666,7 +542,7 @@ extern "C" int c2s_fill(float* p, long n, float v, void* stream) {
 extern "C" int c2s_add_inplace(float* dst, const float* src, long n, void* stream) {
     C2S_REQUIRE(dst && src && n >= 0, "add: bad args");
     if (n == 0) return C2S_OK;
-    hipLaunchKernelGGL(add_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
+    hipLaunchKernelGGL(add_kernel, dim3(grid_for(n, 4096)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
     C2S_CHECK_LAUNCH("add");
     return C2S_OK;
 }

@@ -20,14 +20,9 @@
 
 namespace {
 
-constexpr int MAXK = 32;        // classes, as in metrics.hip
 constexpr int PC_SCAN = 256;    // pixels one workgroup of the numbering scan covers (one per lane)
-constexpr long PC_MAX_PIXELS = INT_MAX - 4096L * 256;       // a grid-stride step past the last pixel still fits an int
-
-inline int grid_for(long n, int cap = 4096) {
-    long b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr int PC_BLOCKS = 4096; // grid cap of the grid-stride kernels
+constexpr long PC_MAX_PIXELS = INT_MAX - (long)PC_BLOCKS * 256;       // a grid-stride step past the last pixel still fits an int
 
 // base[key] += number of active lanes of the wave that hold `key`: one atomic per distinct key and wave.  Called by whole
 // waves (the callers' loops have wave-uniform trip counts).
@@ -469,10 +464,10 @@ extern "C" int c2s_parcel_seeds(const float* scores, const float* boundary_score
                                 void* stream) {
     C2S_REQUIRE(scores && mask, "parcel_seeds: null pointer");
     C2S_REQUIRE(B > 0 && H > 0 && W > 0 && (long)H * W <= INT_MAX, "parcel_seeds: bad shape");
-    C2S_REQUIRE(K >= 2 && K <= MAXK, "parcel_seeds: 2 <= K <= 32 classes");
+    C2S_REQUIRE(K >= 2 && K <= C2S_MAX_CLASSES, "parcel_seeds: 2 <= K <= 32 classes");
     C2S_REQUIRE(from_logits == 0 || from_logits == 1, "parcel_seeds: from_logits is 0 or 1");
     C2S_REQUIRE(!(second_threshold != second_threshold), "parcel_seeds: second_threshold is NaN");
-    hipLaunchKernelGGL(parcel_seeds_kernel, dim3(grid_for((long)B * H * W)), dim3(256), 0, (hipStream_t)stream, scores,
+    hipLaunchKernelGGL(parcel_seeds_kernel, dim3(grid_for((long)B * H * W, PC_BLOCKS)), dim3(256), 0, (hipStream_t)stream, scores,
                        boundary_scores, mask, (int64_t*)t1, B, K, H * W, from_logits, boundary_code, second_threshold);
     C2S_CHECK_LAUNCH("parcel_seeds");
     return C2S_OK;
@@ -500,7 +495,7 @@ extern "C" int c2s_label_components(const unsigned char* mask, int* labels, int*
     int* size = parent + n;
     int* sums = size + n;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 g(grid_for(n)), t(256), gs(nblk, B);
+    const dim3 g(grid_for(n, PC_BLOCKS)), t(256), gs(nblk, B);
     hipLaunchKernelGGL(cc_init_kernel, g, t, 0, st, parent, size, n);
     C2S_CHECK_LAUNCH("cc_init");
     hipLaunchKernelGGL(cc_unite_kernel, g, t, 0, st, parent, mask, n, H, W, error);
@@ -530,7 +525,7 @@ extern "C" int c2s_parcel_vote(const long long* pred, const int* labels, long lo
                                void* stream) {
     C2S_REQUIRE(pred && labels && out && parcel_class && workspace && error, "parcel_vote: null pointer");
     C2S_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W <= PC_MAX_PIXELS, "parcel_vote: bad shape (B * H * W <= %ld)", PC_MAX_PIXELS);
-    C2S_REQUIRE(K >= 2 && K <= MAXK, "parcel_vote: 2 <= K <= 32 classes");
+    C2S_REQUIRE(K >= 2 && K <= C2S_MAX_CLASSES, "parcel_vote: 2 <= K <= 32 classes");
     C2S_REQUIRE(cap >= 1, "parcel_vote: cap %d < 1", cap);
     C2S_REQUIRE(outside == 0 || outside == 1, "parcel_vote: outside is 0 (zero) or 1 (keep)");
     C2S_REQUIRE(!(bg_share != bg_share), "parcel_vote: bg_share is NaN");
@@ -541,12 +536,12 @@ extern "C" int c2s_parcel_vote(const long long* pred, const int* labels, long lo
     const int n = B * H * W, HW = H * W, nh = B * cap * K;
     int* hist = (int*)workspace;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 g(grid_for(n)), t(256);
-    hipLaunchKernelGGL(vote_zero_kernel, dim3(grid_for(nh)), t, 0, st, hist, nh);
+    const dim3 g(grid_for(n, PC_BLOCKS)), t(256);
+    hipLaunchKernelGGL(vote_zero_kernel, dim3(grid_for(nh, PC_BLOCKS)), t, 0, st, hist, nh);
     C2S_CHECK_LAUNCH("vote_zero");
     hipLaunchKernelGGL(vote_hist_kernel, g, t, 0, st, (const int64_t*)pred, labels, hist, n, HW, K, cap, error);
     C2S_CHECK_LAUNCH("vote_hist");
-    hipLaunchKernelGGL(vote_winner_kernel, dim3(grid_for((long)B * cap)), t, 0, st, hist, parcel_class, B * cap, K, bg_share);
+    hipLaunchKernelGGL(vote_winner_kernel, dim3(grid_for((long)B * cap, PC_BLOCKS)), t, 0, st, hist, parcel_class, B * cap, K, bg_share);
     C2S_CHECK_LAUNCH("vote_winner");
     hipLaunchKernelGGL(vote_write_kernel, g, t, 0, st, (const int64_t*)pred, labels, parcel_class, (int64_t*)out, n, HW, K, cap,
                        outside);
@@ -569,7 +564,7 @@ extern "C" int c2s_parcel_soft_vote(const float* scores, const int* labels, long
     C2S_REQUIRE(scores && labels && out && parcel_label && parcel_top2 && parcel_mean && parcel_pixels && workspace && error,
                 "parcel_soft_vote: null pointer");
     C2S_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W <= PC_MAX_PIXELS, "parcel_soft_vote: bad shape (B * H * W <= %ld)", PC_MAX_PIXELS);
-    C2S_REQUIRE(K >= 2 && K <= MAXK, "parcel_soft_vote: 2 <= K <= 32 classes");
+    C2S_REQUIRE(K >= 2 && K <= C2S_MAX_CLASSES, "parcel_soft_vote: 2 <= K <= 32 classes");
     C2S_REQUIRE(cap >= 1, "parcel_soft_vote: cap %d < 1", cap);
     C2S_REQUIRE(from_logits == 0 || from_logits == 1, "parcel_soft_vote: from_logits is 0 or 1");
     C2S_REQUIRE(outside == 0 || outside == 1, "parcel_soft_vote: outside is 0 (zero) or 1 (keep)");
@@ -583,7 +578,7 @@ extern "C" int c2s_parcel_soft_vote(const float* scores, const int* labels, long
     int* cnt = (int*)(S + (size_t)np * K);
     hipStream_t st = (hipStream_t)stream;
     const dim3 t(256), gsum((unsigned)((n + 256L * PS_ITER - 1) / (256L * PS_ITER)));
-    hipLaunchKernelGGL(soft_zero_kernel, dim3(grid_for((long)(need / 4))), t, 0, st, (unsigned*)workspace, need / 4);
+    hipLaunchKernelGGL(soft_zero_kernel, dim3(grid_for((long)(need / 4), PC_BLOCKS)), t, 0, st, (unsigned*)workspace, need / 4);
     C2S_CHECK_LAUNCH("soft_zero");
     if (K <= 4)
         hipLaunchKernelGGL(soft_sum_kernel<4>, gsum, t, 0, st, scores, labels, S, cnt, (long)n, HW, K, cap, from_logits, error);
@@ -594,10 +589,10 @@ extern "C" int c2s_parcel_soft_vote(const float* scores, const int* labels, long
     else
         hipLaunchKernelGGL(soft_sum_kernel<32>, gsum, t, 0, st, scores, labels, S, cnt, (long)n, HW, K, cap, from_logits, error);
     C2S_CHECK_LAUNCH("soft_sum");
-    hipLaunchKernelGGL(soft_winner_kernel, dim3(grid_for(np)), t, 0, st, S, cnt, parcel_label, parcel_top2, parcel_mean,
+    hipLaunchKernelGGL(soft_winner_kernel, dim3(grid_for(np, PC_BLOCKS)), t, 0, st, S, cnt, parcel_label, parcel_top2, parcel_mean,
                        parcel_pixels, np, K, bg_mean);
     C2S_CHECK_LAUNCH("soft_winner");
-    hipLaunchKernelGGL(soft_write_kernel, dim3(grid_for(n)), t, 0, st, scores, labels, parcel_label, (int64_t*)out, n, HW, K, cap,
+    hipLaunchKernelGGL(soft_write_kernel, dim3(grid_for(n, PC_BLOCKS)), t, 0, st, scores, labels, parcel_label, (int64_t*)out, n, HW, K, cap,
                        outside);
     C2S_CHECK_LAUNCH("soft_write");
     return C2S_OK;

@@ -32,23 +32,33 @@ def boundary_target(y: Tensor) -> Tensor:
     return yb
 
 
+def _prologue(logits: Tensor, target: Tensor, ws: Optional[E.Workspace], key: str, ws_floats, loss_out: Optional[Tensor],
+              want_grad: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
+    """What a call of any criterion starts with: logits on the device and contiguous, int64 targets, the workspace buffer `key`
+    of ws_floats(logits) floats, the loss tensor (`loss_out`, to which the value is then ADDED, or a new one) and the gradient
+    buffer.  Returns (logits, target, workspace buffer, loss, dlogits | None)."""
+    if not logits.is_cuda:
+        raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
+    logits = logits.contiguous()
+    target = target.to(torch.int64).contiguous()
+    ws = ws or E.Workspace(logits.device)
+    w = ws.get(key, ws_floats(logits))
+    loss = loss_out if loss_out is not None else torch.empty(1, device=logits.device, dtype=torch.float32)
+    gl = torch.empty_like(logits) if want_grad else None
+    return logits, target, w, loss, gl
+
+
 def focal_ce(logits: Tensor, target: Tensor, gamma: float = 1.0, ignore_index: int = -100, want_grad: bool = False,
              ws: Optional[E.Workspace] = None, loss_out: Optional[Tensor] = None, class_w: Optional[Tensor] = None,
              size_average: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
     """FocalCELoss(gamma, size_average, ignore_index, weight)(logits [B,K,H,W], target [B,H,W]) (focal_loss.py:12-45).
     Returns (loss[1], dlogits | None).  With `loss_out` the value is ADDED to that tensor (utils.py:324).  With class weights the
     value is the reference's: mean(w[target]) * mean(focal terms) (sums for size_average=False) -- its [N,1] x [N] broadcast, see
-    csrc/metrics.hip."""
-    if not logits.is_cuda:
-        raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
-    logits = logits.contiguous()
-    target = target.to(torch.int64).contiguous()
+    focal_fwd_kernel in csrc/loss.hip."""
+    logits, target, w, loss, gl = _prologue(logits, target, ws, "focal", lambda z: lib().c2s_focal_ce_workspace_floats(),
+                                            loss_out, want_grad)
     B, K = logits.shape[:2]
     HW = logits[0, 0].numel()
-    ws = ws or E.Workspace(logits.device)
-    w = ws.get("focal", lib().c2s_focal_ce_workspace_floats())
-    loss = loss_out if loss_out is not None else torch.empty(1, device=logits.device, dtype=torch.float32)
-    gl = torch.empty_like(logits) if want_grad else None
     if class_w is not None:
         class_w = class_w.detach().to(logits.device, torch.float32).contiguous()
         if class_w.numel() != K:
@@ -93,15 +103,9 @@ def smooth_ce(logits: Tensor, target: Tensor, label_smoothing: float = 0.1, clas
     """One pass of c2s_smooth_ce_ex: returns (loss[1], dlogits | None, counters[2]) -- counters[1] is the number of labels
     outside [0, K) the pass met (a device value: reading it synchronises).  reduction 'mean' | 'sum' | 'none' (the per-pixel
     terms go to `pixel_loss` [B,H,W]; loss[0] is then their sum and dlogits the gradient of that sum)."""
-    if not logits.is_cuda:
-        raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
-    logits = logits.contiguous()
-    target = target.to(torch.int64).contiguous()
+    logits, target, w, loss, gl = _prologue(logits, target, ws, "smooth_ce", lambda z: lib().c2s_smooth_ce_workspace_floats(),
+                                            loss_out, want_grad)
     B, K, H, W = logits.shape
-    ws = ws or E.Workspace(logits.device)
-    w = ws.get("smooth_ce", lib().c2s_smooth_ce_workspace_floats())
-    loss = loss_out if loss_out is not None else torch.empty(1, device=logits.device, dtype=torch.float32)
-    gl = torch.empty_like(logits) if want_grad else None
     red = {"mean": 0, "sum": 1, "none": 2}[reduction]
     if red == 2 and pixel_loss is None:
         raise ValueError("smooth_ce: reduction='none' needs a pixel_loss tensor")
@@ -175,7 +179,7 @@ class SmoothCrossEntropy2D:
             raise ValueError(f"SmoothCrossEntropy2D: {int(float(self._last[1][1]))} target labels outside [0, n_classes)")
 
 
-RECALL_MAX_CLASSES = 32                                                      # csrc/recall.hip: MAXK
+RECALL_MAX_CLASSES = 32                                                      # csrc/common.h: C2S_MAX_CLASSES
 
 
 def recall_ce(logits: Tensor, target: Tensor, ignore_index: int = 255, want_grad: bool = False,
@@ -186,18 +190,13 @@ def recall_ce(logits: Tensor, target: Tensor, ignore_index: int = 255, want_grad
     (loss[1], dlogits | None, weights[K], counts[2,K] int64: gt and fn before the floor).  With `loss_out` the value is ADDED to
     that tensor.  Stream-ordered, no host synchronisation; the statement of the rule and the deviations from the reference are in
     include/c2s_hip.h and DESIGN.md section 7."""
-    if not logits.is_cuda:
-        raise RuntimeError("crop2seg_amd runs on MI355X only (no CPU fallback)")
-    logits = logits.contiguous()
-    target = target.to(torch.int64).contiguous()
+    logits, target, w, loss, gl = _prologue(
+        logits, target, ws, "recall", lambda z: lib().c2s_recall_ce_workspace_floats(z.shape[0], z[0, 0].numel()), loss_out,
+        want_grad)
     B, K = logits.shape[:2]
     if not 1 <= K <= RECALL_MAX_CLASSES:
         raise ValueError(f"recall_ce: {K} classes, the kernels take 1 to {RECALL_MAX_CLASSES}")
     HW = logits[0, 0].numel()
-    ws = ws or E.Workspace(logits.device)
-    w = ws.get("recall", lib().c2s_recall_ce_workspace_floats(B, HW))
-    loss = loss_out if loss_out is not None else torch.empty(1, device=logits.device, dtype=torch.float32)
-    gl = torch.empty_like(logits) if want_grad else None
     weights = torch.empty(K, device=logits.device, dtype=torch.float32)
     counts = torch.empty(2, K, device=logits.device, dtype=torch.int64)
     check(lib().c2s_recall_ce(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), E._ptr(gl), weights.data_ptr(),

@@ -1,4 +1,4 @@
-"""Independent float64 reference of RecallCrossEntropy (csrc/recall.hip) with per-element error bounds (CPU only), in the
+"""Independent float64 reference of RecallCrossEntropy (csrc/loss.hip) with per-element error bounds (CPU only), in the
 conventions of tests/tail_ref.py: explicit formulas, forward and backward, each line next to its bound; a kernel result must
 satisfy |got - ref64| <= C_BOUND * u * A + 1e-30 element by element, with tail_ref's C_BOUND = 2 and EXP_ULPS = LOG_ULPS = 2 and
 no constant of its own.  The softmax pieces, the total of the pixel terms and the comparison are tail_ref's (_softmax, _total,

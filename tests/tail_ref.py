@@ -1,6 +1,6 @@
 """Independent float64 references of the training tail, each with a per-element error bound (CPU only): cross entropy
-and flat Adam of csrc/misc.hip, focal CE, smooth CE, the metrics pass, confusion_add, boundary_target and region_relabel of
-csrc/metrics.hip.
+focal CE and smooth CE of csrc/loss.hip, flat Adam of csrc/misc.hip, the metrics pass, confusion_add, boundary_target and
+region_relabel of csrc/metrics.hip.
 
 Every floating-point reference is written out as explicit formulas (forward and backward, no autograd, no
 F.cross_entropy; tests/test_tail_reference.py ties them to those), each line next to its bound.  A reference returns
@@ -205,7 +205,7 @@ def _pow_interval(om, A_om, expo, floor):
 
 def focal_ref(logits, target, gamma=1.0, ignore_index=-100, class_w=None, size_average=True, prior=None,
               dtype=torch.float64, bounds=True, fault=None):
-    """FocalCELoss(gamma, size_average, ignore_index, weight) as csrc/metrics.hip states it: unweighted the mean / sum over the
+    """FocalCELoss(gamma, size_average, ignore_index, weight) as csrc/loss.hip states it: unweighted the mean / sum over the
     kept pixels of f = -(1 - pt)^gamma log pt, weighted the product of the mean / sum of w[target] and the mean / sum of f;
     `prior`: the loss the value is added to.  Returns loss [1], glogits, tot [3] = (sum f, #kept, d loss / d sum f).
 

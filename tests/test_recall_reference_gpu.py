@@ -1,4 +1,4 @@
-"""RecallCrossEntropy on the device (csrc/recall.hip) against the float64 reference of tests/recall_ref.py, through the public
+"""RecallCrossEntropy on the device (csrc/loss.hip) against the float64 reference of tests/recall_ref.py, through the public
 entry points losses.recall_ce / losses.RecallCrossEntropy, and TrainStep(criterion=...) with each of the three criteria of
 learning/losses.py.
 

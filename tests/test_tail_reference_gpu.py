@@ -1,4 +1,4 @@
-"""The loss, Adam and metrics kernels (ce_* / adam_kernel of csrc/misc.hip; focal_*, smooth_ce_*, metrics_update,
+"""The loss, Adam and metrics kernels (ce_*, focal_*, smooth_ce_* of csrc/loss.hip; adam_kernel of csrc/misc.hip; metrics_update,
 confusion_add, boundary_target, region_relabel of csrc/metrics.hip) against the float64 references of tests/tail_ref.py,
 element by element, through the public entry points: engine.cross_entropy / adam_flat, losses.focal_ce / smooth_ce /
 boundary_target, metrics.StepMeters / IoU.

@@ -6,7 +6,7 @@ Needs the reference sources on PYTHONPATH:
 Writes tests/golden/tail_recall_*.npz (the tail_ prefix keeps them out of conftest.golden_names()): float64 logits, target,
 ignore_index, and the loss and the autograd gradient of the reference's criterion.  A few hundred pixels each.
 
-The cases are chosen so that the reference runs and means what csrc/recall.hip computes (the
+The cases are chosen so that the reference runs and means what csrc/loss.hip computes (the
 RecallCrossEntropy deviations): at least two distinct labels, at least two of them misclassified; ignored pixels only with
 ignore_index = -1 and then class 1 present with a false negative.  Each condition is asserted here, and so is the agreement
 with tests/recall_ref.py.

@@ -1,13 +1,13 @@
 """RecallCrossEntropy on the device against the default cross entropy: the loss call alone, and one U-TAE train step.
 
-    python tools/recall_bench.py [--pairs P] [--calls N] [--steps K] [--warmup W] [--T T] [--graph] [--out FILE]
+    python tools/recall_bench.py [--case loss|step] [--pairs P] [--calls N] [--steps K] [--warmup W] [--T T] [--graph] [--out FILE]
 
 At B = 4, K = 15, 128 x 128 and at B = 8, 256 x 256:
-  loss   losses.recall_ce with gradient against engine.cross_entropy with gradient, microseconds per call (device events
-         around N back-to-back calls);
+  loss   losses.recall_ce, focal_ce (gamma 2) and smooth_ce against engine.cross_entropy, all with gradient, microseconds
+         per call (device events around N back-to-back calls);
   step   TrainStep(criterion=RecallCrossEntropy(15)) against TrainStep() on two U-TAE of the same seed, ms per step, eager
          and (--graph) replayed.
-Both as alternating pairs in one session: P windows of each, A B A B ..., so that drift of the machine hits both alike.  Per
+Both as alternating windows in one session: P windows of each, A B A B ..., so that drift of the machine hits all alike.  Per
 case one JSON line with the median of the windows and their spread (min, max): a difference inside the spread of the
 default's own windows is no difference."""
 import argparse
@@ -35,16 +35,16 @@ def window(fn, n):
     return e0.elapsed_time(e1) / n
 
 
-def pairs(fa, fb, n, npairs, warmup):
+def pairs(fns, n, npairs, warmup):
     for _ in range(warmup):
-        fa()
-        fb()
+        for f in fns:
+            f()
     torch.cuda.synchronize()
-    a, b = [], []
+    out = [[] for _ in fns]
     for _ in range(npairs):
-        a.append(window(fa, n))
-        b.append(window(fb, n))
-    return a, b
+        for f, v in zip(fns, out):
+            v.append(window(f, n))
+    return out
 
 
 def stats(v, scale=1.0, digits=3):
@@ -52,18 +52,27 @@ def stats(v, scale=1.0, digits=3):
             "max": round(max(v) * scale, digits)}
 
 
-def loss_case(B, hw, a):
-    from crop2seg_amd import engine as E
-    from crop2seg_amd.learning import losses
+def loss_inputs(B, hw):
+    """Seeded normal logits [B,K,hw,hw], labels in [0, K) and unit class weights, on the device (tools/loss_ab.py dumps these too)."""
     g = torch.Generator().manual_seed(B * 1000 + hw)
     z = torch.randn(B, K, hw, hw, generator=g).cuda()
     y = torch.randint(0, K, (B, hw, hw), generator=g).cuda()
-    cw = torch.ones(K, device="cuda")
+    return z, y, torch.ones(K, device="cuda")
+
+
+def loss_case(B, hw, a):
+    from crop2seg_amd import engine as E
+    from crop2seg_amd.learning import losses
+    z, y, cw = loss_inputs(B, hw)
     ws = E.Workspace(z.device)
-    default, recall = pairs(lambda: E.cross_entropy(z, y, cw, ws, True), lambda: losses.recall_ce(z, y, 255, True, ws),
-                           a.calls, a.pairs, a.warmup)
+    default, recall, focal, smooth = pairs([lambda: E.cross_entropy(z, y, cw, ws, True),
+                                           lambda: losses.recall_ce(z, y, 255, True, ws),
+                                           lambda: losses.focal_ce(z, y, 2.0, 255, True, ws),
+                                           lambda: losses.smooth_ce(z, y, 0.1, want_grad=True, ws=ws)],
+                                          a.calls, a.pairs, a.warmup)
     return {"case": "loss", "B": B, "K": K, "hw": hw, "calls_per_window": a.calls, "windows": a.pairs,
-            "cross_entropy_us": stats(default, 1e3, 1), "recall_ce_us": stats(recall, 1e3, 1)}
+            "cross_entropy_us": stats(default, 1e3, 1), "recall_ce_us": stats(recall, 1e3, 1),
+            "focal_ce_us": stats(focal, 1e3, 1), "smooth_ce_us": stats(smooth, 1e3, 1)}
 
 
 def build(B, T, hw, criterion):
@@ -82,13 +91,13 @@ def step_case(B, hw, a):
     from crop2seg_amd.learning import losses
     sd, x, dates, y = build(B, a.T, hw, None)
     sr, _, _, _ = build(B, a.T, hw, losses.RecallCrossEntropy(K, ignore_index=255))
-    default, recall = pairs(lambda: sd(x, dates, y), lambda: sr(x, dates, y), a.steps, a.pairs, a.warmup)
+    default, recall = pairs([lambda: sd(x, dates, y), lambda: sr(x, dates, y)], a.steps, a.pairs, a.warmup)
     rec = {"case": "step", "model": "utae", "B": B, "T": a.T, "hw": hw, "steps_per_window": a.steps, "windows": a.pairs,
            "default_eager_ms": stats(default), "recall_eager_ms": stats(recall)}
     if a.graph:
         sd.capture(x, dates, y)
         sr.capture(x, dates, y)
-        default, recall = pairs(sd.replay, sr.replay, a.steps, a.pairs, a.warmup)
+        default, recall = pairs([sd.replay, sr.replay], a.steps, a.pairs, a.warmup)
         rec.update(default_graph_ms=stats(default), recall_graph_ms=stats(recall))
     return rec
 
@@ -101,12 +110,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--T", type=int, default=32, help="acquisitions per series")
     ap.add_argument("--graph", action="store_true", help="also time hipGraph replays of the step")
+    ap.add_argument("--case", choices=("all", "loss", "step"), default="all", help="which of the two cases to time")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("recall_bench: needs an MI355X (no CPU fallback)")
     lines = []
-    for fn in (loss_case, step_case):
+    for fn in [f for name, f in (("loss", loss_case), ("step", step_case)) if a.case in ("all", name)]:
         for B, hw in SHAPES:
             rec = fn(B, hw, a)
             print(json.dumps(rec), flush=True)
