@@ -428,10 +428,12 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
     } else if (d->reflect_adjoint) {
         C2S_REQUIRE(d->pad_mode == C2S_PAD_ZEROS && d->S == 1 && (d->KH == 3 || d->KH == 2),
                     "conv_igemm: reflect_adjoint applies to the zero-padded 3x3 / 2x2-parity data-gradient launches");
-        C2S_REQUIRE(d->Hin >= 2 && d->Win >= 2 && d->Hin != 3 && d->Win != 3, "conv_igemm: reflect_adjoint needs planes of 2 or >= 4");
+        C2S_REQUIRE(d->Hin >= 2 && d->Win >= 2, "conv_igemm: reflect_adjoint needs planes of at least 2");
         if (d->KH == 3) {
             // dgrad of conv3x3(reflect pad 1): g_x[1] += w[0] g_y[0] ; g_x[H-2] += w[2] g_y[H-1]
             // (flipped taps: position 1 / tap 2 reads input 0 = tap position - 2; position H-2 / tap 0 reads H-1 = +2)
+            // On a 3-pixel axis lo == hi == 1: the two rules sit on different taps of that position (tap 2 reads row 2 and
+            // adds row 0, tap 0 reads row 0 and adds row 2), and the kernel keeps one mask per rule, so both apply.
             C2S_REQUIRE(d->pad_y == 1 && d->pad_x == 1 && d->Hin == d->Hout && d->Win == d->Wout, "conv_igemm: bad 3x3 adjoint geometry");
             p.ay_lo = 1; p.ay_hi = d->Hout - 2;
             p.ax_lo = 1; p.ax_hi = d->Wout - 2;

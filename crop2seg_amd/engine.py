@@ -612,7 +612,9 @@ def _family_3x3(N: int, chans: Sequence[int], cout: int, H: int, W: int, K: int,
     if _use_winograd(K, S, pad, chans, cout, H, W):
         wide = _wide_winograd(H, W, chans) and N <= 65536       # the 8-wave kernel's frame limit
         return ("wino16", 2, "wino") if wide else ("wino4", 1, "wino")
-    return ("bf16x3", 0, "bx") if _use_bf16x3(K, S, pad, chans) else None
+    # (3-pixel planes stay on the implicit GEMM: the bf16x3 kernel's reflect adjoint keeps one border rule per position, and
+    # on a 3-pixel axis both reflected rows fold onto position 1)
+    return ("bf16x3", 0, "bx") if _use_bf16x3(K, S, pad, chans) and H != 3 and W != 3 else None
 
 
 def conv_plan(op: str, N: int, chans: Sequence[int], Cout: int, Hin: int, Win: int, K: int, S: int, pad: int, pad_mode: int,
@@ -1175,6 +1177,59 @@ def ltae_attention(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor],
                    d_model: int, period: float, dropout_p: float, with_embedding: bool, seed: int,
                    keep: Optional[Tensor], seed_dev: Optional[Tensor] = None, pe_mode: str = "rel",
                    need_attn: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """_ltae_attention_quads on any map.  The kernels walk the pixels of a sample four at a time (h * w a multiple of 4);
+    every pixel is a series of its own, so a map of another size (3 x 3, 2 x 3, 3 x 5: a side of 24 or 40 input pixels at the
+    fourth level) runs as the row of its pixels followed by one to three zero pixels.  Those get zero gradients on the way
+    back, hence add nothing to a parameter's gradient, and their outputs and input gradients are dropped."""
+    B, T, Cc, h, w = x5.shape
+    HW = h * w
+    rest = (prefix, n_head, d_k, d_model, period, dropout_p, with_embedding, seed, keep, seed_dev, pe_mode, need_attn)
+    if HW % 4 == 0:
+        return _ltae_attention_quads(ctx, x5, dates, valid, *rest)
+    if keep is not None and ctx.training and dropout_p > 0:
+        raise NotImplementedError("crop2seg_amd: an explicit attention keep mask needs an L-TAE map of h * w % 4 == 0 pixels; "
+                                  f"got {h} x {w}")
+    HWp = (HW + 3) // 4 * 4
+    tape = ctx.tape
+    xp = torch.zeros(B, T, Cc, 1, HWp, device=x5.device, dtype=torch.float32)
+    xp[..., :HW].copy_(x5.reshape(B, T, Cc, 1, HW))
+    if tape is not None and ctx.needs(x5):
+        tape.track(xp)
+        if ctx.trainable is not None:
+            ctx._needs.add(xp.data_ptr())
+
+        def bwd_in():
+            g = tape.pop_grad(xp)
+            if g is not None:
+                tape.add_grad(x5, g[..., :HW].reshape(x5.shape).contiguous())
+
+        tape.record(bwd_in)
+    nops = len(tape.ops) if tape is not None else 0
+    outs_p = _ltae_attention_quads(ctx, xp, dates, valid, *rest)
+    outs = tuple(None if o is None else o[..., :HW].reshape(*o.shape[:-2], h, w).contiguous() for o in outs_p)
+    if tape is not None and len(tape.ops) > nops:       # the kernels recorded their backward: the outputs carry gradients
+        pairs = [(o, op) for o, op in zip(outs, outs_p) if o is not None]
+        for o, _ in pairs:
+            tape.track(o)
+        if ctx.trainable is not None:
+            ctx._needs.update(o.data_ptr() for o, _ in pairs)
+
+        def bwd_out():
+            for o, op in pairs:
+                g = tape.pop_grad(o)
+                if g is not None:
+                    gp = torch.zeros_like(op)
+                    gp[..., :HW].copy_(g.reshape(*op.shape[:-2], 1, HW))
+                    tape.add_grad(op, gp)
+
+        tape.record(bwd_out)
+    return outs
+
+
+def _ltae_attention_quads(ctx: Ctx, x5: Tensor, dates: Tensor, valid: Optional[Tensor], prefix: str, n_head: int, d_k: int,
+                          d_model: int, period: float, dropout_p: float, with_embedding: bool, seed: int,
+                          keep: Optional[Tensor], seed_dev: Optional[Tensor] = None, pe_mode: str = "rel",
+                          need_attn: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """L-TAE steps 1-6 (reference tae.py:451-481, 738-847).  Returns (emb [B,d_model,h,w] | None, attn [H,B,T,h,w]).
     pe_mode: "rel" = the default sinusoid of the relative dates; "doy" / "abs_rel" / "linear" = the learnable encoders of
     use_doy / use_abs_rel_enc (dates [B,T,2]) / add_linear (tae.py:404-430): the attention kernels then run with a zero

@@ -15,6 +15,9 @@ Wrapped rows and the boundary each one puts inside a tensor:
                                  tile), igemm-4x4-acc (plane smaller than a tile), igemm-1x1-acc, s2-ragged-acc (F(2x2,2x2)
                                  on 12 x 40 outputs, 8 -> 72 channels), xpair-acc (16-wide output rows)
     TRANSPOSE_SHAPES             (2,128,64,4,4), (2,64,32,16,16): the parity launches at the narrowest planes
+    test_conv_rect_gpu           wino4-2x8 (one row of Winograd tiles), igemm-8x2-acc, xpair-16x4-acc (2-wide output of the
+                                 data gradient's source plane), 3px-64ch-3x3-acc, the K = 6 transposed convolution on 2 x 8:
+                                 thin planes, where an access outside the plane shows first
     DEPTHWISE                    hw 6 (one output per thread) and 40 x 48 (float4 spans), (K,S) = (3,1) and (4,2)
     test_strided_geometry DOWN   (72,40,24,1) and (64,64,4,1), reflect, geometries (2,2,0) and (6,2,2): ragged channels both
                                  ways; a 2 x 2 output plane
@@ -155,6 +158,7 @@ def _conv_cases():
     import dw_ref as D
     import test_conv_modes_gpu as CM
     import test_conv_paths_gpu as CP
+    import test_conv_rect_gpu as CR
     import test_conv_split_gpu as CS
     import test_dw_reference_gpu as DW
     import test_strided_geometry_gpu as SG
@@ -168,6 +172,12 @@ def _conv_cases():
     for shape in ((2, 128, 64, 4, 4), (2, 64, 32, 16, 16)):
         assert shape in CP.TRANSPOSE_SHAPES
         case(f"transpose/{'x'.join(map(str, shape))}", lambda mp, shape=shape: CP._run_transpose(shape))
+    # one thin-plane row per family of test_conv_rect_gpu.py, and the 3 x 3 plane whose two reflected rows fold onto one
+    for rid in ("rect-wino4-2x8", "rect-igemm-8x2-acc", "rect-xpair-16x4-acc", "rect-3px-64ch-3x3-acc"):
+        row = next(r for r in CR.ROWS + CR.ROWS_3PX if r.id == rid)
+        case(f"conv/{rid}", lambda mp, row=row: CR._run(row))
+    assert (6, 2, 128, 64, 2, 8, 1) in CR.UP
+    case("up/rect-k6-128-64-2x8", lambda mp: CR.test_conv_transpose_rect(6, 2, 128, 64, 2, 8, 1))
     for K, S, hw in CP.DEPTHWISE:
         if hw in (6, 40):
             case(f"depthwise/k{K}s{S}-{hw}", lambda mp, a=(K, S, hw): CP._run_depthwise(*a))
