@@ -17,6 +17,7 @@ c_int_p = C.c_void_p
 PAD_ZEROS, PAD_REFLECT = 0, 1
 SRC_F32, SRC_I16, SRC_U16 = 0, 1, 2
 NORM_GROUP, NORM_BATCH = 0, 1
+CONV_MAX_FRAMES = 65535        # C2S_CONV_MAX_FRAMES of include/c2s_hip.h: frames per launch of the gridDim.z families
 
 
 class ConvDesc(C.Structure):

@@ -238,12 +238,14 @@ int check(const c2s_agg_desc* d) {
 
 extern "C" int c2s_attn_head_mean(const float* attn, float* v, int n_head, long n, void* stream) {
     C2S_REQUIRE(attn && v && n_head > 0 && n > 0, "attn_head_mean: bad args");
+    C2S_REQUIRE_ITEMS(n, 256, "attn_head_mean");
     hipLaunchKernelGGL(head_mean_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attn, v, n_head, n);
     C2S_CHECK_LAUNCH("attn_head_mean");
     return C2S_OK;
 }
 extern "C" int c2s_attn_head_mean_bwd(const float* gv, float* gattn, int n_head, long n, int accumulate, void* stream) {
     C2S_REQUIRE(gv && gattn && n_head > 0 && n > 0, "attn_head_mean_bwd: bad args");
+    C2S_REQUIRE_ITEMS(n, 256, "attn_head_mean_bwd");
     hipLaunchKernelGGL(head_mean_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, gv, gattn, n_head, n, accumulate);
     C2S_CHECK_LAUNCH("attn_head_mean_bwd");
     return C2S_OK;
@@ -260,6 +262,7 @@ extern "C" int c2s_temporal_aggregate_fwd(const c2s_agg_desc* d, const float* x,
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(x && attn && out, "aggregate_fwd: null pointer");
     const long total = (long)d->B * d->n_head * d->H * d->W;
+    C2S_REQUIRE_ITEMS(total, 256, "aggregate_fwd");
     dim3 grid(cdiv(total, 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
     switch (d->C / d->n_head) {
@@ -295,6 +298,7 @@ int aggregate_bwd(const c2s_agg_desc* d, const float* x, const float* attn, cons
         C2S_REQUIRE(tiles <= 0x7fffffffL, "aggregate_bwd: too many planes for the upsample adjoint");
     }
     const long total = (long)d->B * d->n_head * d->H * d->W;
+    C2S_REQUIRE_ITEMS(total, 256, "aggregate_bwd");
     dim3 grid(cdiv(total, 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define C2S_AGG_BWD(CPG_)                                                                                                    \
@@ -354,7 +358,7 @@ extern "C" int c2s_agg_skip_term(const c2s_agg_desc* d, const float* a_up, const
     if (int rc = check(d)) return rc;
     C2S_REQUIRE(a_up && gskip && gx, "agg_skip_term: null pointer");
     const size_t n = (size_t)d->B * d->T * d->C * d->H * d->W;
-    C2S_REQUIRE(n <= 0x7fffffffUL * 256, "agg_skip_term: too many elements");
+    C2S_REQUIRE_ITEMS(n, 256, "agg_skip_term");       // one thread per element of x
     hipLaunchKernelGGL(agg_skip_term_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a_up, gskip,
                        valid, gx, *d);
     C2S_CHECK_LAUNCH("agg_skip_term");

@@ -44,6 +44,13 @@ int c2s_cus();   // compute units of the current device (256 when no device is p
     } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// A launch with one thread per item and no grid-stride loop: gridDim.x x blockDim.x, the work-items of ONE grid dimension, must
+// fit 32 bits.  HIP takes a larger one without an error and does not run all of it (measured on an MI355X: the items past 2^32
+// were never written).  The limit is per dimension: the product over x, y and z may be far larger (the folded depthwise
+// launch), and folding over y / z does not lift the limit of x.  `total` = the work-items along x.
+#define C2S_REQUIRE_ITEMS(total, block, what)                                                              \
+    C2S_REQUIRE(((long)(total) + (block) - 1) / (block) * (long)(block) < (1L << 32),                      \
+                what ": %ld work-items in one launch, the limit is 2^32 - 1", (long)(total))
 // blocks of 256 threads for a grid-stride loop over n elements, at most `cap`.  No default: a cap is behaviour (the number
 // of block partials fixes the bits of a loss), so every call site states its own.
 static inline int grid_for(long n, int cap) {

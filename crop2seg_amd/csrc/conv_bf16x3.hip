@@ -404,6 +404,7 @@ extern "C" int c2s_conv3x3_bf16x3(const c2s_conv_desc* d, const float* src0, con
                     d->osx == 1 && d->ooy == 0 && d->oox == 0, "conv3x3_bf16x3: dense same-size output only");
     C2S_REQUIRE(d->C0 % 8 == 0 && d->C1 % 8 == 0 && (d->C1 == 0 || src1), "conv3x3_bf16x3: channel counts must be multiples of 8");
     C2S_REQUIRE(d->CoutP % 32 == 0 && d->CoutP >= d->Cout, "conv3x3_bf16x3: CoutP must be a multiple of 32");
+    C2S_REQUIRE(d->N <= C2S_CONV_MAX_FRAMES, "conv3x3_bf16x3: more than 65535 frames in one launch (N = %d): the frame index is gridDim.z", d->N);
     C2S_REQUIRE((long)(d->C0 > d->C1 ? d->C0 : d->C1) * d->Hin * d->Win * 4 < (1L << 31), "conv3x3_bf16x3: frame too large");
     if (d->pad_mode == C2S_PAD_REFLECT) C2S_REQUIRE(d->Hin >= 2 && d->Win >= 2, "conv3x3_bf16x3: reflect needs planes >= 2");
     BxParams p;

@@ -395,6 +395,7 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
     C2S_REQUIRE(d->N > 0 && d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv_igemm: bad channels");
     C2S_REQUIRE(d->CoutP % 32 == 0 && d->CoutP >= d->Cout && d->Cout > 0, "conv_igemm: CoutP must be a multiple of 32");
     C2S_REQUIRE(d->KH == d->KW, "conv_igemm: square kernels only");
+    C2S_REQUIRE(d->N <= C2S_CONV_MAX_FRAMES, "conv_igemm: more than 65535 frames in one launch (N = %d): the frame index is gridDim.z", d->N);
     C2S_REQUIRE(d->C1 == 0 || d->C0 % 16 == 0, "conv_igemm: with two sources C0 must be a multiple of 16");
     C2S_REQUIRE((long)(d->C0 > d->C1 ? d->C0 : d->C1) * d->Hin * d->Win * 4 < (1L << 31), "conv_igemm: frame too large");
     C2S_REQUIRE((long)d->Hin * d->Win < (1 << 20), "conv_igemm: input plane too large");

@@ -330,8 +330,9 @@ extern "C" int c2s_conv4x4s2_winograd_supported(const c2s_conv_desc* d) {
 extern "C" int c2s_conv4x4s2_winograd(const c2s_conv_desc* d, const float* src, const float* upk, const float* bias,
                                       float* out, const int* valid, void* stream) {
     C2S_REQUIRE(d && src && upk && out, "conv4x4s2_winograd: null pointer");
+    C2S_REQUIRE(d->N > 0 && d->N <= 65536, "conv4x4s2_winograd: more than 65536 frames in one launch (N = %d)", d->N);   // (the predicate holds the same limit)
     C2S_REQUIRE(c2s_conv4x4s2_winograd_supported(d), "conv4x4s2_winograd: 4x4 stride 2 pad 1, one source with an even number (>= 8) of channels, even output planes at least 32 wide and 8 high, CoutP %% 64");
-    C2S_REQUIRE(d->N > 0 && d->N <= 65536 && d->Cout > 0 && d->CoutP >= d->Cout, "conv4x4s2_winograd: bad N / Cout");
+    C2S_REQUIRE(d->Cout > 0 && d->CoutP >= d->Cout, "conv4x4s2_winograd: bad Cout");
     C2S_REQUIRE(d->OutH == d->Hout && d->OutW == d->Wout && d->osy == 1 && d->osx == 1 && d->ooy == 0 && d->oox == 0,
                 "conv4x4s2_winograd: dense output only");
     C2S_REQUIRE((long)d->C0 * d->Hin * d->Win * 4 < 0x7FFF0000L && (long)d->CoutP * d->Hout * d->Wout * 4 < 0x7FFF0000L,

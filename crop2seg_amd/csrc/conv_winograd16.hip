@@ -508,8 +508,9 @@ extern "C" int c2s_conv3x3_winograd16_supported(const c2s_conv_desc* d) {
 extern "C" int c2s_conv3x3_winograd16(const c2s_conv_desc* d, const float* src0, const float* src1, const float* upk,
                                       const float* bias, float* out, const int* valid, void* stream) {
     C2S_REQUIRE(d && src0 && upk && out, "conv3x3_winograd16: null pointer");
+    C2S_REQUIRE(d->N > 0 && d->N <= 65536, "conv3x3_winograd16: more than 65536 frames in one launch (N = %d)", d->N);   // (the predicate holds the same limit)
     C2S_REQUIRE(c2s_conv3x3_winograd16_supported(d), "conv3x3_winograd16: 3x3 stride 1 pad 1, even planes at least 32 wide and 8 high, CoutP %% 64, channels of each source a multiple of 8");
-    C2S_REQUIRE(d->N > 0 && d->N <= 65536 && d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv3x3_winograd16: bad channels / more than 65536 frames");
+    C2S_REQUIRE(d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv3x3_winograd16: bad channels");
     C2S_REQUIRE(d->Hout == d->Hin && d->Wout == d->Win && d->OutH == d->Hout && d->OutW == d->Wout && d->osy == 1 &&
                 d->osx == 1 && d->ooy == 0 && d->oox == 0, "conv3x3_winograd16: dense same-size output only");
     C2S_REQUIRE(d->CoutP >= d->Cout && d->Cout > 0, "conv3x3_winograd16: bad CoutP");

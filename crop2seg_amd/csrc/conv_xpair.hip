@@ -264,6 +264,7 @@ extern "C" int c2s_conv_xpair(const c2s_conv_desc* d, const float* src, const fl
     C2S_REQUIRE(d && src && wpk && out, "conv_xpair: null pointer");
     C2S_REQUIRE(d->N > 0 && d->C0 > 0 && d->C1 == 0 && d->Cout > 0, "conv_xpair: bad channels (single source only)");
     C2S_REQUIRE(d->CoutP % 32 == 0 && d->CoutP >= d->Cout, "conv_xpair: CoutP must be a multiple of 32");
+    C2S_REQUIRE(d->N <= C2S_CONV_MAX_FRAMES, "conv_xpair: more than 65535 frames in one launch (N = %d): the frame index is gridDim.z", d->N);
     C2S_REQUIRE(d->KH == 2 && d->KW == 2 && d->S == 1 && d->pad_mode == C2S_PAD_ZEROS, "conv_xpair: 2x2 zero-padded sub-kernels only");
     C2S_REQUIRE(d->pad_y == 0 || d->pad_y == 1, "conv_xpair: pad_y = 1 - py");
     C2S_REQUIRE(d->osy == 2 && d->osx == 2 && d->ooy == 1 - d->pad_y, "conv_xpair: output rows 2*i + py, columns 2*j + {0,1}");

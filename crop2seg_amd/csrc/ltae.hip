@@ -3992,6 +3992,7 @@ extern "C" int c2s_pixel_gn_fwd(const float* x, const float* gamma, const float*
                                 int C, int HW, int groups, float eps, void* stream) {
     C2S_REQUIRE(x && gamma && beta && y && stats && groups > 0 && C % groups == 0 && C / groups <= 16, "pixel_gn_fwd: bad args");
     const long total = (long)B * groups * HW;
+    C2S_REQUIRE_ITEMS(total, 256, "pixel_gn_fwd");
     hipLaunchKernelGGL(pixel_gn_fwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
                        stats, B, C, HW, groups, eps);
     C2S_CHECK_LAUNCH("pixel_gn_fwd");

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void frame_flags_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------- depthwise conv (conv.py:18-24)
-// HBM-bound.  grid = (pixel blocks, N*C planes); (K,S) are template parameters so the tap loops unroll and the
+// HBM-bound.  grid = (pixel blocks, N*C planes over y and z: dw_grid); (K,S) are template parameters so the tap loops unroll and the
 // K*K weights of the plane sit in registers.  A thread owns PX adjacent outputs of a row: per input row they read one
 // span of (PX-1)*S + K columns starting at ox0*S - pad, which (pad == 1, PX == 4) is one scalar, one or two aligned
 // float4s and one scalar instead of PX*K dwords.
@@ -134,9 +134,11 @@ __device__ __forceinline__ void dw_load_span(const float* __restrict__ row, int 
 template <int K, int S, int PX>
 __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ in, const float* __restrict__ w,
                                                      float* __restrict__ out, const int* __restrict__ valid, int C,
-                                                     int Hin, int Win, int pad, int reflect) {
+                                                     int Hin, int Win, int pad, int reflect, int planes) {
     constexpr int SP = (PX - 1) * S + K;
-    const int plane = blockIdx.y, c = plane % C, n = plane / C;
+    const unsigned up = blockIdx.z * gridDim.y + blockIdx.y;        // dw_grid: z == 0 up to 65535 planes; below 2^32 in all
+    if (up >= (unsigned)planes) return;
+    const int plane = (int)up, c = plane % C, n = plane / C;
     if (valid != nullptr && valid[n] == 0) return;
     const int Ho = (Hin + 2 * pad - K) / S + 1, Wo = (Win + 2 * pad - K) / S + 1;
     const int W4 = Wo / PX;                                          // PX = 4 needs Wo % 4 == 0, Win % 4 == 0 (dw_span4)
@@ -215,9 +217,12 @@ __device__ __forceinline__ void dw_pairs(int j, int n_in, int n_out, int pad, bo
 template <int K, int S, int PX>
 __global__ __launch_bounds__(256) void dw_dgrad_kernel(const float* __restrict__ gout, const float* __restrict__ w,
                                                        float* __restrict__ gin, const int* __restrict__ valid, int C,
-                                                       int Hin, int Win, int pad, int reflect, int accumulate) {
+                                                       int Hin, int Win, int pad, int reflect, int accumulate,
+                                                       int planes) {
     __shared__ float ws[K * K + 1];
-    const int plane = blockIdx.y, c = plane % C, n = plane / C;
+    const unsigned up = blockIdx.z * gridDim.y + blockIdx.y;        // dw_grid: z == 0 up to 65535 planes; below 2^32 in all
+    if (up >= (unsigned)planes) return;                              // whole workgroup: before the barrier
+    const int plane = (int)up, c = plane % C, n = plane / C;
     if (threadIdx.x < K * K) ws[threadIdx.x] = w[(size_t)c * K * K + threadIdx.x];
     if (threadIdx.x == K * K) ws[K * K] = 0.f;                      // weight of an empty slot
     __syncthreads();
@@ -414,6 +419,7 @@ extern "C" int c2s_frame_flags(const float* x, int* valid, int N, long frame_ele
     hipMemsetAsync(valid, 0, (size_t)N * sizeof(int), st);
     int chunks = (int)((frame_elems + 16383) / 16384);
     if (chunks > 64) chunks = 64;
+    C2S_REQUIRE_ITEMS((long)N * chunks * 256, 256, "frame_flags");
     hipLaunchKernelGGL(frame_flags_kernel, dim3(N * chunks), dim3(256), 0, st, x, valid, frame_elems, pad_value, chunks);
     C2S_CHECK_LAUNCH("frame_flags");
     return C2S_OK;
@@ -424,7 +430,16 @@ static int dw_check(int N, int C, int Hin, int Win, int K, int S, int pad, int p
     C2S_REQUIRE((K == 3 && S == 1 && pad == 1) || (K == 4 && S == 2 && pad == 1) || (K == 2 && S == 2 && pad == 0) ||
                 (K == 6 && S == 2 && pad == 2), "dwconv: built for (K,S,pad) = (3,1,1), (4,2,1), (2,2,0) and (6,2,2)");
     if (pad_mode == C2S_PAD_REFLECT) C2S_REQUIRE(Hin > pad && Win > pad && Hin >= 2 && Win >= 2, "dwconv: reflect needs pad < plane");
+    C2S_REQUIRE((long)N * C <= 0x7FFFFFFFL, "dwconv: more than 2^31 - 1 planes (N * C = %ld)", (long)N * C);
     return C2S_OK;
+}
+
+// Grid of the forward and data-gradient kernels: pixel blocks in x, the plane index in (y, z).  Up to 65535 planes z is 1 and
+// the plane is blockIdx.y, as it always was; above, z = ceil(planes / 65535) rows of ceil(planes / z) planes (fewer than z
+// workgroup columns past the last plane return at once).  x stays the fastest index, so the launch order does not change.
+static dim3 dw_grid(int pixel_blocks, int planes) {
+    const int gz = cdiv(planes, 65535);
+    return dim3(pixel_blocks, cdiv(planes, gz), gz);
 }
 
 // Pixels per thread of the three exports (the table at c2s_dwconv_paths in include/c2s_hip.h).  The launchers and the query
@@ -458,19 +473,20 @@ extern "C" int c2s_dwconv_fwd(const float* in, const float* w, float* out, const
     C2S_REQUIRE(in && w && out, "dwconv_fwd: null pointer");
     const int Ho = (Hin + 2 * pad - K) / S + 1, Wo = (Win + 2 * pad - K) / S + 1;
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
+    const int planes = N * C;
     hipStream_t st = (hipStream_t)stream;
     if (K == 2 || K == 6) {         // one output per thread (dw_span4 is false)
-        const dim3 grid(cdiv(Ho * Wo, 256), N * C);
-        if (K == 2) hipLaunchKernelGGL((dw_fwd_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
-        else hipLaunchKernelGGL((dw_fwd_kernel<6, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
+        const dim3 grid = dw_grid(cdiv(Ho * Wo, 256), planes);
+        if (K == 2) hipLaunchKernelGGL((dw_fwd_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect, planes);
+        else hipLaunchKernelGGL((dw_fwd_kernel<6, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect, planes);
     } else if (dw_span4(Win, K, S, pad)) {
-        const dim3 grid(cdiv(Ho * (Wo / 4), 256), N * C);
-        if (K == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 1, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
-        else hipLaunchKernelGGL((dw_fwd_kernel<4, 2, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
+        const dim3 grid = dw_grid(cdiv(Ho * (Wo / 4), 256), planes);
+        if (K == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 1, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect, planes);
+        else hipLaunchKernelGGL((dw_fwd_kernel<4, 2, 4>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect, planes);
     } else {
-        const dim3 grid(cdiv(Ho * Wo, 256), N * C);
-        if (K == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 1, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
-        else hipLaunchKernelGGL((dw_fwd_kernel<4, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect);
+        const dim3 grid = dw_grid(cdiv(Ho * Wo, 256), planes);
+        if (K == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 1, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect, planes);
+        else hipLaunchKernelGGL((dw_fwd_kernel<4, 2, 1>), grid, dim3(256), 0, st, in, w, out, valid, C, Hin, Win, pad, reflect, planes);
     }
     C2S_CHECK_LAUNCH("dwconv_fwd");
     return C2S_OK;
@@ -481,19 +497,20 @@ extern "C" int c2s_dwconv_dgrad(const float* gout, const float* w, float* gin, c
     if (int rc = dw_check(N, C, Hin, Win, K, S, pad, pad_mode)) return rc;
     C2S_REQUIRE(gout && w && gin, "dwconv_dgrad: null pointer");
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
+    const int planes = N * C;
     hipStream_t st = (hipStream_t)stream;
     if (K == 2 || K == 6) {         // the gather form (dw_stencil4 is false)
-        const dim3 grid(cdiv(Hin * Win, 256), N * C);
-        if (K == 2) hipLaunchKernelGGL((dw_dgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
-        else hipLaunchKernelGGL((dw_dgrad_kernel<6, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
+        const dim3 grid = dw_grid(cdiv(Hin * Win, 256), planes);
+        if (K == 2) hipLaunchKernelGGL((dw_dgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate, planes);
+        else hipLaunchKernelGGL((dw_dgrad_kernel<6, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate, planes);
     } else if (dw_stencil4(Hin, Win, K)) {
-        const dim3 grid(cdiv(Hin * (Win / 4), 256), N * C);
-        if (K == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
-        else hipLaunchKernelGGL((dw_dgrad_kernel<4, 2, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
+        const dim3 grid = dw_grid(cdiv(Hin * (Win / 4), 256), planes);
+        if (K == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate, planes);
+        else hipLaunchKernelGGL((dw_dgrad_kernel<4, 2, 4>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate, planes);
     } else {
-        const dim3 grid(cdiv(Hin * Win, 256), N * C);
-        if (K == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
-        else hipLaunchKernelGGL((dw_dgrad_kernel<4, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate);
+        const dim3 grid = dw_grid(cdiv(Hin * Win, 256), planes);
+        if (K == 3) hipLaunchKernelGGL((dw_dgrad_kernel<3, 1, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate, planes);
+        else hipLaunchKernelGGL((dw_dgrad_kernel<4, 2, 1>), grid, dim3(256), 0, st, gout, w, gin, valid, C, Hin, Win, pad, reflect, accumulate, planes);
     }
     C2S_CHECK_LAUNCH("dwconv_dgrad");
     return C2S_OK;
@@ -505,6 +522,7 @@ extern "C" int c2s_dwconv_wgrad(const float* in, const float* gout, float* parti
     C2S_REQUIRE(in && gout && partial && gw, "dwconv_wgrad: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const bool reflect = pad_mode == C2S_PAD_REFLECT;
+    C2S_REQUIRE_ITEMS((long)N * C * 256, 256, "dwconv_wgrad");       // one workgroup of 256 per plane: below 2^24 planes
     const dim3 grid(N * C);
     if (K == 2 || K == 6) {
         if (K == 2) hipLaunchKernelGGL((dw_wgrad_kernel<2, 2, 1>), grid, dim3(256), 0, st, in, gout, partial, valid, C, Hin, Win, pad, reflect);

@@ -869,6 +869,7 @@ extern "C" int c2s_norm_fwd(const c2s_norm_desc* d, const float* x, const float*
     const int segs = n_segs(d->HW);
     const long rows = (long)d->N * d->C;
     const long nitems = rows * segs;
+    C2S_REQUIRE_ITEMS(nitems * 64, 256, "norm_fwd");                 // one wave per (row, segment)
     hipStream_t st = (hipStream_t)stream;
     const bool eval_bn = d->kind == C2S_NORM_BATCH && !d->training;
     if (eval_bn) C2S_REQUIRE(running_mean && running_var, "norm_fwd: eval BatchNorm needs running stats");
@@ -896,6 +897,7 @@ extern "C" int c2s_norm_bwd(const c2s_norm_desc* d, const float* x, const float*
     const int segs = n_segs(d->HW);
     const long rows = (long)d->N * d->C;
     const long nitems = rows * segs;
+    C2S_REQUIRE_ITEMS(nitems * 64, 256, "norm_bwd");
     float* part = workspace;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(norm_bwd_sums_kernel, dim3(cdiv(nitems, 4)), dim3(256), 0, st, x, g, row_ab, group_stats, part,

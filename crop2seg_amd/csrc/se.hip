@@ -205,6 +205,7 @@ extern "C" int c2s_se_fwd(const float* x, const float* W1, const float* W2, floa
     C2S_REQUIRE(ws_floats >= c2s_se_workspace_floats(N, C, HW), "se_fwd: workspace too small");
     const int R = C / 16, segs = n_segs(HW);
     const long nitems = (long)N * C * segs;
+    C2S_REQUIRE_ITEMS(nitems * 64, 256, "se_fwd");                   // one wave per (row, segment)
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(se_row_sums_kernel, dim3(cdiv(nitems, 4)), dim3(256), 0, st, x, (const float*)nullptr, workspace, valid, C,
                        HW, segs, nitems);
@@ -225,6 +226,7 @@ extern "C" int c2s_se_bwd(const float* x, const float* g, const float* W1, const
     C2S_REQUIRE(ws_floats >= c2s_se_workspace_floats(N, C, HW), "se_bwd: workspace too small");
     const int R = C / 16, segs = n_segs(HW);
     const long nitems = (long)N * C * segs;
+    C2S_REQUIRE_ITEMS(nitems * 64, 256, "se_bwd");
     float* part = workspace;
     float* pw = part + (size_t)N * C * segs;
     float* dpool = pw + (size_t)N * 2 * R * C;

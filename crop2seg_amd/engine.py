@@ -13,7 +13,7 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import AggDesc, ConvDesc, LtaeDesc, NormDesc, WgradDesc, check, lib
+from ._lib import AggDesc, C2SError, ConvDesc, LtaeDesc, NormDesc, WgradDesc, check, lib
 
 Tensor = torch.Tensor
 
@@ -617,8 +617,23 @@ def _family_3x3(N: int, chans: Sequence[int], cout: int, H: int, W: int, K: int,
     return ("bf16x3", 0, "bx") if _use_bf16x3(K, S, pad, chans) and H != 3 and W != 3 else None
 
 
+# families whose kernels take the frame index from gridDim.z: their launchers refuse N > C2S_CONV_MAX_FRAMES (include/c2s_hip.h)
+Z_FRAME_FAMILIES = ("igemm", "xpair", "parity", "bf16x3")
+
+
 def conv_plan(op: str, N: int, chans: Sequence[int], Cout: int, Hin: int, Win: int, K: int, S: int, pad: int, pad_mode: int,
               si: int = 0, accumulate: int = 0) -> ConvPlan:
+    """_conv_plan, refusing at planning time what the planned family's launcher would refuse for its frame count: a plan
+    that comes back launches."""
+    plan = _conv_plan(op, N, chans, Cout, Hin, Win, K, S, pad, pad_mode, si, accumulate)
+    if N > _lib.CONV_MAX_FRAMES and plan.family in Z_FRAME_FAMILIES:
+        raise C2SError(f"conv_plan({op!r}): {CONV_FAMILIES[plan.family][0][4:]}: more than {_lib.CONV_MAX_FRAMES} frames in one "
+                       f"launch (N = {N}): the frame index is gridDim.z")
+    return plan
+
+
+def _conv_plan(op: str, N: int, chans: Sequence[int], Cout: int, Hin: int, Win: int, K: int, S: int, pad: int, pad_mode: int,
+               si: int = 0, accumulate: int = 0) -> ConvPlan:
     """The kernel family of one convolution and its launches: descriptors and pack requests, host integers only (no tensor,
     no Ctx, no stream; the library is asked for its host-side *_supported predicates).  _run_conv executes a plan.
     op "fwd": nn.Conv2d(K, S, pad, pad_mode) of N frames of Hin x Win over the channel concatenation of sources with `chans`

@@ -97,6 +97,14 @@ typedef struct c2s_conv_desc {
                              reflection_pad2d_backward of conv.py:72-79) is applied inside the kernel */
 } c2s_conv_desc;
 
+/* Frames in one launch.  c2s_conv_igemm, c2s_conv_xpair and c2s_conv3x3_bf16x3 index the frame with gridDim.z and refuse
+ * N > C2S_CONV_MAX_FRAMES up front (C2S_EINVAL, "more than 65535 frames in one launch"; nothing is launched): no layer
+ * of the models folds that many frames into one convolution, so they refuse rather than fold the index.  The Winograd
+ * families state their own limits (65536; 32768 for the stride-2 data gradient) in their *_supported predicates;
+ * c2s_conv3x3_winograd and c2s_conv3x3_smallcin carry the frame in gridDim.x and take any N whose tile count fits an
+ * int.  The engine's conv_plan raises the refusal when it plans, before any launch. */
+#define C2S_CONV_MAX_FRAMES 65535
+
 int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const float* src1, const float* wpk,
                    const float* bias, float* out, const int* valid, void* stream);
 /* The tile split c2s_conv_igemm gives this launch: 1, 2 or 4 (host arithmetic only, no device call; cus <= 0: the compute
@@ -275,6 +283,10 @@ int c2s_wgrad_reduce_batch(const void* device_table, int njobs, int total_blocks
 /* ------------------------------------------------------------------------------------------------
  * Depthwise convolution (groups = C, no bias) forward / data gradient / weight gradient.
  * Replaces DepthwiseSeparableConv2D.depthwise (conv.py:18-20,24), used by W-TAE (wtae.py:148-162).
+ * Forward and data gradient take any N * C up to 2^31 - 1 planes (C2S_EINVAL above): they carry the plane index in gridDim.y up
+ * to 65535 planes and fold it over (y, z) above that.  The weight gradient carries it in gridDim.x, one workgroup of 256 per
+ * plane, and takes N * C < 2^24 (gridDim.x x blockDim.x below 2^32; C2S_EINVAL above).  A plane's bits do not depend on how
+ * many planes the launch has.
  * ------------------------------------------------------------------------------------------------ */
 int c2s_dwconv_fwd(const float* in, const float* w, float* out, const int* valid, int N, int C, int Hin, int Win,
                    int K, int S, int pad, int pad_mode, void* stream);
@@ -548,6 +560,10 @@ typedef struct c2s_agg_desc {
  *   c2s_attn_head_mean     : v[g][i] = mean_h attn[h][i] for every g < n_head (n = B*T*h*w entries per head)
  *   c2s_attn_head_mean_bwd : gattn[h][i] (+)= (1/n_head) sum_g gv[g][i]
  *   c2s_frame_mean_weights : v[g][b][t] = valid[b,t] / #valid frames of b   (a 1x1 "attention map" per frame; valid may be NULL) */
+/* The launches of this group with one thread per item -- c2s_temporal_aggregate_fwd / _bwd (B * n_head * H * W items),
+ * c2s_attn_head_mean / _bwd (n), c2s_agg_skip_term (B * T * C * H * W: TimeUNet at 256 x 256, B = 17, T = 61 is past it) -- and
+ * c2s_pixel_gn_fwd (B * groups * HW) refuse gridDim.x x blockDim.x of 2^32 work-items or more (C2S_EINVAL, "work-items in one
+ * launch"): HIP accepts such a launch without an error and does not run all of it.  The limit is per grid dimension. */
 int c2s_attn_head_mean(const float* attn, float* v, int n_head, long n, void* stream);
 int c2s_attn_head_mean_bwd(const float* gv, float* gattn, int n_head, long n, int accumulate, void* stream);
 int c2s_frame_mean_weights(const int* valid, float* v, int n_head, int B, int T, void* stream);
@@ -862,6 +878,22 @@ int c2s_blend_finish(float* acc_proba, const float* wsum, long long* top1, int K
 /* elementwise helpers */
 int c2s_fill(float* p, long n, float v, void* stream);
 int c2s_add_inplace(float* dst, const float* src, long n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The size queries in closed form (all in size_t; tests/size_rows.py holds them against the library in Python integers).
+ * segs(HW) = ceil(HW / min(HW, 2048)): the 2048-float wave segments of a plane.
+ *   c2s_norm_workspace_floats            3 N C segs(HW) + 6 N C + 64                      (either kind)
+ *   c2s_norm_onepass_sync_bytes          64 + 16 N C segs(HW) where the one-pass form takes the shape, else 0
+ *   c2s_se_workspace_floats              N C segs(HW) + 2 N (C / 16) C + N C
+ *   c2s_wgrad_workspace_floats           nslices KH KW ceil32(C0 + C1) ceil64(Cout)       (ceilK: rounded up to a multiple of K)
+ *   c2s_temporal_aggregate_bwd_workspace_floats   n_head B T H W
+ *   c2s_pixel_gn_bwd_workspace_floats    2 B ceil(HW / 256) C + 2 C
+ *   c2s_cross_entropy_workspace_floats   3 * 512 + 3                                       (512: the grid cap of the loss kernels)
+ *   c2s_recall_ce_workspace_floats       B HW + 512 + (2 (2 C2S_MAX_CLASSES + 1) + 1) + C2S_MAX_CLASSES + 2
+ * One thread (or one wave) per item, gridDim.x x blockDim.x below 2^32 -- the exports refuse more, "work-items in one launch":
+ * c2s_norm_fwd / _bwd and c2s_se_fwd / _bwd run one wave per (row, segment): N C segs(HW) < 2^26; c2s_dwconv_wgrad one workgroup
+ * of 256 per plane: N C < 2^24; c2s_frame_flags N min(64, ceil(frame_elems / 16384)) workgroups of 256.
+ * ------------------------------------------------------------------------------------------------ */
 
 #ifdef __cplusplus
 }
