@@ -190,6 +190,12 @@ SIGNATURES = {
     "c2s_step_decide": (I, [P, F, F, I, P, P, I, P, P]),
     "c2s_adam_slots": (I, [P, P, P, P, P, P, P, I, L, F, F, F, F, P, P]),
     "c2s_restore_if_skipped": (I, [P, P, L, P, P]),
+    "c2s_snapshot_job_bytes": (SZ, []),
+    "c2s_snapshot_job_blocks": (L, [L]),
+    "c2s_snapshot_job_fill": (I, [P, P, L, L, L]),
+    "c2s_snapshot_gather": (I, [P, I, P, L, P]),
+    "c2s_snapshot_verify": (I, [P, L, I, P, P]),
+    "c2s_snapshot_scatter": (I, [P, I, P, L, P, P]),
     "c2s_fill": (I, [P, L, F, P]),
     "c2s_add_inplace": (I, [P, P, L, P]),
 }

@@ -197,7 +197,8 @@ class Workspace:
         which need no residency assumption.  Whether the caller may catch the error and repeat the step depends on what the
         lost step did to the optimiser state: under TrainStep(skip_nonfinite=True) the device skipped it and nothing changed;
         without that guard (or in a loop of the caller's own that ran an optimiser on the NaN gradient) the parameters, Adam
-        moments and BatchNorm running statistics are NaN by now and the last checkpoint has to be restored."""
+        moments and BatchNorm running statistics are NaN by now and the last checkpoint has to be restored
+        (`TrainStep.load(path)`, or `TrainStep.load_state_dict(snapshot.state_dict())` for a snapshot kept in memory)."""
         if self.sync_error() == 0:
             return
         global ONEPASS_NORM
@@ -209,7 +210,8 @@ class Workspace:
             "shared or masked GPU, profiler serialisation?).  The affected outputs are NaN.  The sync area has been "
             "reset and this process now uses the two-pass normalisation kernels.  Repeat the step if it was a forward pass or "
             "a TrainStep(skip_nonfinite=True) step (the device skipped the update); otherwise the NaN has reached the "
-            "parameters, the Adam moments and the BatchNorm running statistics: restore the last checkpoint.")
+            "parameters, the Adam moments and the BatchNorm running statistics: restore the last checkpoint with "
+            "TrainStep.load(path) (written by TrainStep.snapshot().save(path)).")
 
     def get(self, name: str, nfloats: int) -> Tensor:
         b = self.bufs.get(name)
@@ -1570,3 +1572,49 @@ def restore_if_skipped(dst: Tensor, saved: Tensor, status: Tensor) -> None:
     """dst = saved where the step was skipped (status.ok == 0); untouched otherwise."""
     check(lib().c2s_restore_if_skipped(dst.data_ptr(), saved.data_ptr(), dst.numel(), status.data_ptr(), _stream()),
           "restore_if_skipped")
+
+
+# Training-state snapshots (csrc/snapshot.hip; blob and status layouts: include/c2s_hip.h).  All stream-ordered.  The layout is
+# planned by checkpoint.plan_layout (pure host code); `snapshot_table` turns it into the device table.
+SNAPSHOT_HEADER_BYTES = 64
+SNAPSHOT_STATUS_BYTES = 32
+SNAPSHOT_SPAN_BYTES = 8192
+SNAPSHOT_MAX_BLOCKS = 1024
+SNAPSHOT_MAGIC = 0x53533243
+SNAPSHOT_VERSION = 1
+
+
+def snapshot_table(ptrs: Sequence[int], nbytes: Sequence[int], offsets: Sequence[int], device) -> Tensor:
+    """The region table of c2s_snapshot_gather / c2s_snapshot_scatter: filled on the host, uploaded once (host -> device
+    copy: call outside hipGraph capture)."""
+    L_ = lib()
+    rec = L_.c2s_snapshot_job_bytes()
+    table = torch.zeros(max(len(ptrs), 1) * rec, dtype=torch.uint8)
+    block = 0
+    for i, (p, n, o) in enumerate(zip(ptrs, nbytes, offsets)):
+        check(L_.c2s_snapshot_job_fill(table.data_ptr() + i * rec, p if n else None, n, o, block), "snapshot_job_fill")
+        block += L_.c2s_snapshot_job_blocks(n)
+    return table.to(device)
+
+
+def snapshot_status(device) -> Tensor:
+    """A zeroed status block as int64[4]: ok = int32 word 0, reason = int32 word 1, the recomputed sums = words 1 and 2."""
+    return torch.zeros(SNAPSHOT_STATUS_BYTES // 8, device=device, dtype=torch.int64)
+
+
+def snapshot_gather(table: Tensor, nregions: int, blob: Tensor) -> None:
+    """Every live region into `blob` (uint8, header + payload), the header's sums from the same reads."""
+    check(lib().c2s_snapshot_gather(table.data_ptr(), nregions, blob.data_ptr(), blob.numel() * blob.element_size(), _stream()),
+          "snapshot_gather")
+
+
+def snapshot_verify(blob: Tensor, nregions: int, status: Tensor) -> None:
+    """status.ok = 1 iff the blob's header fits `nregions` and the blob's size and both sums agree with the payload."""
+    check(lib().c2s_snapshot_verify(blob.data_ptr(), blob.numel() * blob.element_size(), nregions, status.data_ptr(), _stream()),
+          "snapshot_verify")
+
+
+def snapshot_scatter(table: Tensor, nregions: int, blob: Tensor, status: Tensor) -> None:
+    """`blob` back into the live regions where status.ok == 1; nothing is written otherwise."""
+    check(lib().c2s_snapshot_scatter(table.data_ptr(), nregions, blob.data_ptr(), blob.numel() * blob.element_size(),
+                                     status.data_ptr(), _stream()), "snapshot_scatter")

@@ -386,19 +386,32 @@ class TrainStep:
         dropped and has to be captured again.  The step that hit the failed wait produced NaN: with skip_nonfinite=True it
         changed nothing (the device skipped it: `skipped_steps()`), so the caller may catch the error and repeat the step; without
         it the NaN has gone through Adam into the parameters, the moments and the BatchNorm running statistics, and the
-        way back is the last checkpoint."""
+        way back is the last checkpoint: `TrainStep.load(path)` for a file written by `snapshot().save(path)`, or
+        `load_state_dict(snap.state_dict())` for a snapshot kept in memory (capture() again afterwards: the graphs are
+        dropped here)."""
         try:
             self.ws.check_sync()
         except RuntimeError:
             self.graph_fb = self.graph_opt = None
             raise
 
+    def _seed_root_value(self) -> int:
+        """Root of the dropout seed sequence: torch.initial_seed(), or the root of the state that was loaded."""
+        root = getattr(self, "_seed_root", None)
+        return torch.initial_seed() if root is None else root
+
+    def _rank(self) -> int:
+        return self.dp.rank if self.dp is not None else 0
+
+    @staticmethod
+    def _dropout_base(root: int, calls: int, rank: int) -> int:
+        return (root * 0x9E3779B1 + calls * 2 + rank * 0x51ED27) & ((1 << 62) - 1)
+
     def _fresh_dropout(self) -> Fn.DropoutState:
         drop = Fn.DropoutState()
         if self.model.training:
             self._seed_calls = getattr(self, "_seed_calls", 0) + 1
-            rank = self.dp.rank if self.dp is not None else 0
-            base = (torch.initial_seed() * 0x9E3779B1 + self._seed_calls * 2 + rank * 0x51ED27) & ((1 << 62) - 1)
+            base = self._dropout_base(self._seed_root_value(), self._seed_calls, self._rank())
             drop.attn_seed, drop.mlp_seed = base, base + 1
         return drop
 
@@ -461,8 +474,22 @@ class TrainStep:
         else:
             runs = self._adam_runs(flags)               # one device step counter per Adam launch
             self.step_dev = torch.tensor([st for _, _, st in runs], device=dev, dtype=torch.int32)
-        self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        drop = self._fresh_dropout()
+        pending = getattr(self, "_pending_capture", None)
+        if pending is not None:
+            # a loaded state was saved by a captured step: the graph bakes the dropout base in by value, so the continuation
+            # takes the recorded base (its place in the seed sequence) and replay counter instead of drawing a fresh one
+            drop = Fn.DropoutState()
+            if self.model.training:
+                base = self._dropout_base(self._seed_root_value(), pending["calls"], self._rank())
+                drop.attn_seed, drop.mlp_seed = base, base + 1
+            self.seed_dev = torch.tensor([pending["seed_dev"]], device=dev, dtype=torch.int64)
+            self._cap_calls = pending["calls"]
+            self._pending_capture = None
+        else:
+            self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
+            drop = self._fresh_dropout()
+            self._cap_calls = getattr(self, "_seed_calls", 0)
+        self._cap_base = drop.attn_seed
         drop.seed_dev = self.seed_dev
         saved = {k: v.clone() for k, v in self.model.named_buffers()}     # the warm-up pass must not count as a step
         # the captured step runs on one stream: all slice sums of the weight gradients go into ONE launch at its end
@@ -501,6 +528,7 @@ class TrainStep:
                     E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], 0, self.lr,
                                 self.betas[0], self.betas[1], self.eps, grad_scale=scale, step_dev=self.step_dev[k:k + 1])
         self._cap_flags = flags
+        self._cap_runs = None if self.guarded else runs
 
     @torch.no_grad()
     def replay(self, x: Optional[Tensor] = None, dates: Optional[Tensor] = None, y: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -523,3 +551,241 @@ class TrainStep:
             self._attempts += 1
         self.param_steps = [s + 1 if f else s for s, f in zip(self.param_steps, flags)]
         return self.static_loss, self.static_logits
+
+    # ------------------------------------------------------------------------------------------------
+    # Snapshots and checkpoints (csrc/snapshot.hip, checkpoint.py; DESIGN.md, checkpoints): the whole training state as one
+    # device blob per snapshot, gathered by one launch and copied to the host behind the step.
+    def _captured(self) -> bool:
+        return getattr(self, "graph_fb", None) is not None
+
+    def release_capture(self) -> None:
+        """Drop the captured graphs (before loading a state they do not fit; capture() again afterwards)."""
+        self.graph_fb = self.graph_opt = None
+
+    def _snapshot_regions(self) -> List[Tuple[str, Tensor]]:
+        """The live device tensors that make up the state, in blob order."""
+        flat_buf = getattr(self, "flat_buf", None)
+        regs = [("flat_param", self.flat_param), ("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)]
+        if flat_buf is not None:
+            regs.append(("flat_buf", flat_buf))             # every floating-point buffer is a view of it
+        for k, b in self.model.named_buffers():
+            if flat_buf is None or not b.is_floating_point():
+                regs.append(("buffer:" + k, b))
+        if self.guarded:
+            regs += [("slot_steps_dev", self.slot_steps_dev), ("_skip_dev", self._skip_dev)]
+        if self._captured():
+            if not self.guarded:
+                regs.append(("step_dev", self.step_dev))
+            regs.append(("seed_dev", self.seed_dev))
+        return regs
+
+    def _snapshot_plan(self) -> dict:
+        """Layout, device table, the two staging blobs and the status block: planned once and kept while the regions stay
+        where they are (capture() adds two)."""
+        from .. import checkpoint as CK
+        regs = self._snapshot_regions()
+        key = tuple((n, t.data_ptr(), t.numel() * t.element_size()) for n, t in regs)
+        plan = getattr(self, "_snap_plan", None)
+        if plan is not None and plan["key"] == key:
+            return plan
+        for n, t in regs:
+            if not t.is_contiguous() or (t.numel() * t.element_size()) % 4:
+                raise ValueError(f"TrainStep.snapshot: {n} must be contiguous and a multiple of 4 bytes long")
+        dev = self.flat_param.device
+        cur = torch.cuda.current_stream()
+        if plan is not None:
+            for ev in plan["done"]:                         # the old staging blobs go back to the allocator of this stream
+                if ev is not None:
+                    cur.wait_event(ev)
+        nbytes = [k[2] for k in key]
+        offs, payload, _ = CK.plan_layout(nbytes)
+        flat_buf = getattr(self, "flat_buf", None)
+        named_b = list(self.model.named_buffers())
+        static = {
+            "keys": list(self.model.state_dict().keys()), "names": list(self.names),
+            "shapes": [tuple(p.shape) for _, p in self._named], "offsets": list(self.offsets),
+            "flat_buf_views": [(k, tuple(b.shape)) for k, b in named_b if flat_buf is not None and b.is_floating_point()],
+            "buffers": [(k, tuple(b.shape), b.dtype) for k, b in named_b if flat_buf is None or not b.is_floating_point()],
+        }
+        total = E.SNAPSHOT_HEADER_BYTES + payload
+        plan = self._snap_plan = {
+            "key": key, "regions": [(n, nb, o) for (n, _, nb), o in zip(key, offs)], "payload": payload, "n": len(regs),
+            "table": E.snapshot_table([k[1] for k in key], nbytes, offs, dev),
+            "blobs": [torch.empty(total, device=dev, dtype=torch.uint8) for _ in range(2)], "done": [None, None], "count": 0,
+            "status": E.snapshot_status(dev), "stream": plan["stream"] if plan is not None else torch.cuda.Stream(),
+            "static": static,
+        }
+        return plan
+
+    def _staging(self, plan: dict) -> Tuple[int, Tensor]:
+        """The staging blob whose turn it is; the current stream waits for the copy that still reads it."""
+        k = plan["count"] % 2
+        plan["count"] += 1
+        if plan["done"][k] is not None:
+            torch.cuda.current_stream().wait_event(plan["done"][k])
+        return k, plan["blobs"][k]
+
+    @torch.no_grad()
+    def snapshot(self):
+        """The training state at this point of the current stream, as a checkpoint.Snapshot: one gather launch into one of two
+        device staging blobs, then a copy to a pinned host blob on a side stream behind an event.  No host synchronisation:
+        the next step may be launched at once; a third snapshot while both staging blobs are in flight makes the stream (not
+        the host) wait for the older copy.  The host-side scalars are read now; in a guarded step they may lag the device
+        (`sync_steps`), and Snapshot.state_dict() takes the step and skip counts from the blob instead."""
+        from .. import checkpoint as CK
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TrainStep.snapshot(): not inside a hipGraph capture (the copy to the host is not part of a step)")
+        plan = self._snapshot_plan()
+        k, blob = self._staging(plan)
+        cur, side = torch.cuda.current_stream(), plan["stream"]
+        E.snapshot_gather(plan["table"], plan["n"], blob)
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        host = torch.empty(blob.numel(), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(side):
+            side.wait_event(ready)
+            host.copy_(blob, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(side)
+        plan["done"][k] = done
+        meta = dict(plan["static"])
+        meta.update(
+            param_steps=list(self.param_steps), step_count=self.step_count, attempts=getattr(self, "_attempts", 0),
+            seed_calls=getattr(self, "_seed_calls", 0), seed_root=self._seed_root_value(), rank=self._rank(),
+            guard={"max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite} if self.guarded else None,
+            capture={"calls": self._cap_calls, "base": self._cap_base, "flags": list(self._cap_flags)} if self._captured() else None,
+            trainable=dict(zip(self.names, self.trainable_flags())), lr=self.lr, betas=tuple(self.betas), eps=self.eps)
+        return CK.Snapshot(host, done, plan["regions"], meta)
+
+    def _check_state(self, state: dict, exact: bool) -> None:
+        """ValueError listing every difference in names, shapes or guard mode between `state` and this step."""
+        from .. import checkpoint as CK
+        diffs = []
+        if not isinstance(state, dict) or "state_dict" not in state:
+            raise ValueError("TrainStep.load_state_dict: a dict with a 'state_dict' entry is needed")
+        extra = state.get(CK.EXTRA_KEY)
+        if extra is not None and not exact:
+            raise ValueError(f"TrainStep.load_state_dict: '{CK.EXTRA_KEY}' has layout version "
+                             f"{extra.get('layout_version') if isinstance(extra, dict) else extra!r}, this build reads {CK.LAYOUT_VERSION}")
+        sd = state["state_dict"]
+        mine = self.model.state_dict()
+        for k, v in mine.items():
+            if k not in sd:
+                diffs.append(f"{k}: missing in the state")
+            elif tuple(sd[k].shape) != tuple(v.shape):
+                diffs.append(f"{k}: shape {tuple(sd[k].shape)} in the state, {tuple(v.shape)} in the model")
+        diffs += [f"{k}: not in the model" for k in sd if k not in mine]
+        if exact:
+            g = extra["guard"]
+            theirs = (g is not None, bool(g["skip_nonfinite"]) if g is not None else False)
+            if theirs != (self.guarded, self.skip_nonfinite):
+                diffs.append(f"guard mode: the state has (guarded, skip_nonfinite) = {theirs}, this step "
+                             f"{(self.guarded, self.skip_nonfinite)}")
+            if len(extra["param_steps"]) != len(self.names):
+                diffs.append(f"step counts: {len(extra['param_steps'])} in the state, {len(self.names)} parameters")
+        if diffs:
+            raise ValueError("TrainStep.load_state_dict: the state does not fit this step; nothing was loaded:\n  " + "\n  ".join(diffs))
+
+    @torch.no_grad()
+    def load_state_dict(self, state: dict) -> dict:
+        """Put a state of Snapshot.state_dict() / TrainStep.load() back, in place: one blob is uploaded, verified on the device
+        and scattered into the live tensors, so parameters stay views of `flat_param`, buffers of `flat_buf`, and a captured
+        graph stays valid.  Then the host-side scalars follow (step counts, seed root and call count, the trainable flags by
+        name).  lr / betas / eps stay the constructor's.  One host synchronisation (the verdict is read back).
+
+        ValueError (with the list of differences) when names, shapes or guard mode differ; RuntimeError when the device refused
+        the blob (its sums do not match the state's record) or when a captured step is given a state that does not carry its
+        dropout base.  In all three cases nothing has been written.  A state with only the reference's keys loads parameters,
+        buffers, moments and step counts; the return value's "bit_exact" is False then, and a warning says so."""
+        from .. import checkpoint as CK
+        import numpy as np
+        exact = CK.is_bit_exact(state)
+        self._check_state(state, exact)
+        extra = state[CK.EXTRA_KEY] if exact else None
+        shapes = [tuple(p.shape) for _, p in self._named]
+        flat_p, flat_m, flat_v, steps, bufs = CK.torch_to_flat(state, self.names, shapes, self.offsets, self.total)
+        if exact:
+            steps = [int(s) for s in extra["param_steps"]]
+            bufs.update(extra.get("extra_buffers", {}))
+        cap = extra.get("capture") if exact else None
+        values: Dict[str, Tensor] = {}
+        if self._captured():
+            fits = cap is not None and list(cap["flags"]) == list(self._cap_flags) and \
+                self._dropout_base(extra["seed_root"], cap["calls"], self._rank()) == self._cap_base
+            if fits and not self.guarded:
+                first = {o: i for i, o in reversed(list(enumerate(self.offsets)))}
+                ends = list(self.offsets[1:]) + [self.total]
+                for b, e, _ in self._cap_runs:
+                    run = {steps[i] for i, o in enumerate(self.offsets) if b <= o < e and ends[i] > o}
+                    fits = fits and len(run) <= 1
+                values["step_dev"] = torch.tensor([steps[first[b]] for b, _, _ in self._cap_runs], dtype=torch.int32)
+            if not fits:
+                raise RuntimeError("TrainStep.load_state_dict: the captured graphs have their dropout base and parameter runs baked "
+                                   "in and this state does not carry them; nothing was loaded.  Call release_capture(), load, "
+                                   "then capture() again")
+            values["seed_dev"] = torch.tensor([cap["seed_dev"]], dtype=torch.int64)
+        plan = self._snapshot_plan()
+        st = plan["static"]
+        values.update(flat_param=flat_p, exp_avg=flat_m, exp_avg_sq=flat_v)
+        if st["flat_buf_views"] or getattr(self, "flat_buf", None) is not None:
+            fb = torch.zeros(self.flat_buf.numel(), dtype=torch.float32)
+            o = 0
+            for k, shp in st["flat_buf_views"]:
+                n = bufs[k].numel()
+                fb[o:o + n] = bufs[k].to(torch.float32).reshape(-1)
+                o += (n + 3) // 4 * 4
+            values["flat_buf"] = fb
+        for k, shp, dt in st["buffers"]:
+            if k not in bufs:
+                raise ValueError(f"TrainStep.load_state_dict: buffer {k} is not in the state; nothing was loaded")
+            values["buffer:" + k] = bufs[k].to(dt).reshape(shp)
+        if self.guarded:
+            values["slot_steps_dev"] = torch.tensor(steps, dtype=torch.int32)
+            values["_skip_dev"] = torch.tensor([extra["guard"]["skipped"] if exact else 0], dtype=torch.int32)
+        # the blob, in this step's layout; its header carries the sums the state recorded, region by region
+        host = torch.zeros(E.SNAPSHOT_HEADER_BYTES + plan["payload"], dtype=torch.uint8, pin_memory=True)
+        arr = host.numpy()
+        recorded = {n: (nb, a, b) for n, nb, a, b in extra["regions"]} if exact else {}
+        parts = []
+        for n, nb, off in plan["regions"]:
+            raw = values[n].contiguous().numpy().reshape(-1).view(np.uint8)
+            if raw.size != nb:
+                raise ValueError(f"TrainStep.load_state_dict: {n} has {raw.size} bytes in the state, {nb} in this step; nothing was loaded")
+            a0 = E.SNAPSHOT_HEADER_BYTES + off
+            arr[a0:a0 + nb] = raw
+            if n in recorded and recorded[n][0] == nb:
+                parts.append((off, recorded[n][1], recorded[n][2]))
+            else:
+                parts.append((off,) + CK.word_sums(arr[a0:a0 + nb]))
+        s1, s2 = CK.compose_sums(parts)
+        arr[:E.SNAPSHOT_HEADER_BYTES] = np.frombuffer(CK.blob_header(plan["n"], plan["payload"], s1, s2), dtype=np.uint8)
+        _, blob = self._staging(plan)
+        blob.copy_(host, non_blocking=True)
+        E.snapshot_verify(blob, plan["n"], plan["status"])
+        E.snapshot_scatter(plan["table"], plan["n"], blob, plan["status"])
+        ok, reason = (int(v) for v in plan["status"].view(torch.int32)[:2].tolist())       # load is a host-side operation
+        if ok != 1:
+            why = {1: "magic", 2: "version", 3: "region count", 4: "payload size", 5: "checksum"}.get(reason, str(reason))
+            raise RuntimeError(f"TrainStep.load_state_dict: the device refused the blob ({why} mismatch: the state's tensors are not "
+                               "the ones its checksums were taken from); the live state is untouched")
+        self.param_steps = list(steps)
+        if exact:
+            self.step_count = int(extra["step_count"])
+            self._seed_calls, self._seed_root = int(extra["seed_calls"]), int(extra["seed_root"])
+            if self.guarded:
+                self._attempts = int(extra["guard"]["attempts"])
+            for n, p in self._named:
+                if n in extra["trainable"]:
+                    p.requires_grad_(bool(extra["trainable"][n]))
+        else:
+            self.step_count = max(steps) if steps else 0
+            if self.guarded:
+                self._attempts = self.step_count
+            CK.warn_not_bit_exact()
+        if not self._captured():
+            self._pending_capture = None if cap is None else {"calls": int(cap["calls"]), "seed_dev": int(cap["seed_dev"])}
+        return {"bit_exact": exact, "epoch": state.get("epoch"), "best_mIoU": state.get("best_mIoU")}
+
+    def load(self, path) -> dict:
+        """load_state_dict of a file written by Snapshot.save() -- or by the reference's train.py (model.pth.tar)."""
+        return self.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))

@@ -645,6 +645,54 @@ int c2s_adam_slots(float* p, const float* g, float* m, float* v, const long* slo
 int c2s_restore_if_skipped(float* dst, const float* saved, long n, const void* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training-state snapshots (csrc/snapshot.hip): many live device regions <-> one contiguous device blob, in the job-table
+ * idiom of c2s_pack_batch.  Nothing is read back, allocated or synchronised: every call is legal inside a hipGraph capture.
+ *
+ * Blob (16-byte aligned, C2S_SNAPSHOT_HEADER_BYTES + payload bytes, little endian):
+ *     byte 0  uint32 magic           C2S_SNAPSHOT_MAGIC
+ *     byte 4  uint32 version         C2S_SNAPSHOT_VERSION
+ *     byte 8  uint32 nregions
+ *     byte 12 uint32 0
+ *     byte 16 uint64 payload_bytes   a multiple of 16
+ *     byte 24 uint64 s1              sum of the payload's 32-bit words w_i                  mod 2^64
+ *     byte 32 uint64 s2              sum of (i + 1) * w_i, i counted from 0                 mod 2^64
+ *     byte 40 24 zero bytes
+ *     byte 64 payload: region r at blob_offset[r] (from the payload's start, a multiple of 16), `bytes` of it (a multiple of 4,
+ *             zero allowed), then zero words up to the next multiple of 16.
+ *   Both sums run over the padding as well.  s2 weighs a word by its position, so two swapped unequal words change it although
+ *   s1 stays.  They are accumulated with one 64-bit integer atomic per workgroup and sum; integer sums mod 2^64 do not depend
+ *   on the order of the additions, so the header is the same bits on every run.
+ *
+ * Region table: records of c2s_snapshot_job_bytes() bytes, filled on the host by c2s_snapshot_job_fill, uploaded once.  A
+ *   region padded to 16 bytes is cut into spans of C2S_SNAPSHOT_SPAN_BYTES; block_start of region r = the sum of
+ *   c2s_snapshot_job_blocks(bytes) over the regions before it.  At most C2S_SNAPSHOT_MAX_BLOCKS workgroups walk the spans with
+ *   a grid stride.  16-byte loads and stores where the live address is 16-byte aligned, dwords otherwise and in a ragged tail.
+ *
+ *   c2s_snapshot_gather: a one-workgroup launch writes the header (sums zero), one launch copies every region into the blob,
+ *     writes the padding as 0 and adds the sums of what it copied into the header.  blob_bytes = header + payload; a table
+ *     that points past the payload is not followed there.
+ *   c2s_snapshot_verify: recomputes both sums and writes the status block (C2S_SNAPSHOT_STATUS_BYTES, 8-byte aligned):
+ *         byte 0  int    ok      1: the blob is whole
+ *         byte 4  int    reason  0 fine, 1 magic, 2 version, 3 region count, 4 payload size, 5 a sum differs
+ *         byte 8  uint64 s1, byte 16 uint64 s2: the recomputed sums
+ *   c2s_snapshot_scatter: copies the blob back into the live regions if status.ok == 1 (and the header still agrees with
+ *     nregions and blob_bytes); otherwise it writes nothing (the status.ok pattern of c2s_adam_slots).
+ * ------------------------------------------------------------------------------------------------ */
+#define C2S_SNAPSHOT_MAGIC 0x53533243u /* "C2SS" */
+#define C2S_SNAPSHOT_VERSION 1u
+#define C2S_SNAPSHOT_HEADER_BYTES 64
+#define C2S_SNAPSHOT_STATUS_BYTES 32
+#define C2S_SNAPSHOT_SPAN_BYTES 8192
+#define C2S_SNAPSHOT_MAX_BLOCKS 1024
+size_t c2s_snapshot_job_bytes(void);
+long c2s_snapshot_job_blocks(long bytes);
+int c2s_snapshot_job_fill(void* host_record, const void* live, long bytes, long blob_offset, long block_start);
+int c2s_snapshot_gather(const void* device_table, int nregions, void* blob, long blob_bytes, void* stream);
+int c2s_snapshot_verify(const void* blob, long blob_bytes, int nregions, void* status, void* stream);
+int c2s_snapshot_scatter(const void* device_table, int nregions, const void* blob, long blob_bytes, const void* status,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Metrics tail of iterate() (src/learning/utils.py:332-336,377-380; src/learning/miou.py:55-117).
  *   c2s_metrics_update: one pass over logits [B,K,HW] and target int64 [B,HW]:
  *       pred      = argmax_k logits (first maximum, = torch.argmax)
