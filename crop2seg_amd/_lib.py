@@ -190,6 +190,8 @@ SIGNATURES = {
     "c2s_step_decide": (I, [P, F, F, I, P, P, I, P, P]),
     "c2s_adam_slots": (I, [P, P, P, P, P, P, P, I, L, F, F, F, F, P, P]),
     "c2s_restore_if_skipped": (I, [P, P, L, P, P]),
+    "c2s_lr_advance": (I, [P, P, I, P, P, I, P, P]),
+    "c2s_adam_slots_hp": (I, [P, P, P, P, P, P, P, P, I, L, P, F, F, F, I, F, P, P]),
     "c2s_snapshot_job_bytes": (SZ, []),
     "c2s_snapshot_job_blocks": (L, [L]),
     "c2s_snapshot_job_fill": (I, [P, P, L, L, L]),

@@ -201,6 +201,15 @@ class Snapshot:
             param_steps = [int(v) for v in self._tensor("slot_steps_dev", torch.int32)]
             skipped = int(self._tensor("_skip_dev", torch.int32)[0])
             step_count = m["attempts"] - skipped
+        optim, lr = m.get("optim"), m["lr"]
+        if optim is not None:
+            # schedule path: the step counts and the schedule block are the device's own bytes at the snapshot's place in the
+            # stream; the optimizer entry's lr is the rate at that position
+            param_steps = [int(v) for v in self._tensor("slot_steps_dev", torch.int32)]
+            words = self._tensor("sched_dev", torch.int32)
+            t, scale = int(words[0]), float(words.view(torch.float32)[1])
+            table = optim["table"]
+            lr = float(np.float32(np.float64(np.float32(table[min(max(t, 0), len(table) - 1)])) * np.float64(scale)))
         buffers: Dict[str, Tensor] = {}
         if "flat_buf" in have:
             fb, o = self._tensor("flat_buf", torch.float32), 0
@@ -212,7 +221,10 @@ class Snapshot:
             buffers[k] = self._tensor("buffer:" + k, dt).reshape(tuple(shp))
         state = flat_to_torch([k for k in m["keys"]], m["names"], m["shapes"], m["offsets"],
                               self._tensor("flat_param", torch.float32), self._tensor("exp_avg", torch.float32),
-                              self._tensor("exp_avg_sq", torch.float32), param_steps, buffers, m["lr"], m["betas"], m["eps"])
+                              self._tensor("exp_avg_sq", torch.float32), param_steps, buffers, lr, m["betas"], m["eps"])
+        if optim is not None:
+            for grp in state["optimizer"]["param_groups"]:
+                grp["weight_decay"] = optim["weight_decay"]
         capture = None
         if m["capture"] is not None:
             capture = dict(m["capture"])
@@ -227,6 +239,10 @@ class Snapshot:
             "hyper": {"lr": m["lr"], "betas": list(m["betas"]), "eps": m["eps"]},
             "extra_buffers": {k: buffers[k] for k in buffers if k not in state["state_dict"]},
         }
+        if optim is not None:               # only then: a state of a step without the schedule path keeps its bytes
+            state[EXTRA_KEY]["optim"] = {
+                "table_len": optim["table_len"], "table_digest": optim["table_digest"], "groups": dict(optim["groups"]),
+                "decoupled": optim["decoupled"], "weight_decay": optim["weight_decay"], "sched_words": [int(w) for w in words]}
         self._state = state
         return state
 

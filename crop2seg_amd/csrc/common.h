@@ -74,15 +74,27 @@ __device__ __forceinline__ void adam_bias(float b1, float b2, int st, float& bc1
     bc1 = 1.f - powf(b1, (float)st);
     bc2s = sqrtf(1.f - powf(b2, (float)st));
 }
+// The statements behind gg, the gradient Adam sees, are a macro so that adam_element keeps its text and adam_element_wd
+// (coupled weight decay folded into gg: adam_slots_hp_kernel, guard.hip) states no arithmetic of its own.
+#define C2S_ADAM_ELEMENT_FROM_GG                                  \
+    const float mm = b1 * m[i] + (1.f - b1) * gg;                 \
+    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;            \
+    m[i] = mm; v[i] = vv;                                         \
+    const float denom = sqrtf(vv) / bc2s + eps;                   \
+    p[i] -= (lr / bc1) * (mm / denom);
 __device__ __forceinline__ void adam_element(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                              float* __restrict__ v, long i, float lr, float b1, float b2, float eps,
                                              float bc1, float bc2s, float gscale) {
     const float gg = g[i] * gscale;
-    const float mm = b1 * m[i] + (1.f - b1) * gg;
-    const float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    m[i] = mm; v[i] = vv;
-    const float denom = sqrtf(vv) / bc2s + eps;
-    p[i] -= (lr / bc1) * (mm / denom);
+    C2S_ADAM_ELEMENT_FROM_GG
+}
+// torch.optim.Adam(weight_decay=wd): the decay joins the scaled (clipped) gradient, gg = g gscale + wd p
+__device__ __forceinline__ void adam_element_wd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, long i, float lr, float b1, float b2, float eps,
+                                                float bc1, float bc2s, float gscale, float wd) {
+    float gg = g[i] * gscale;
+    gg = gg + wd * p[i];
+    C2S_ADAM_ELEMENT_FROM_GG
 }
 // taps of the largest packed kernel (the 6x6 stride-2 convolutions): tap tables of the weight packs and slice sums
 constexpr int C2S_MAX_TAPS = 36;

@@ -4,8 +4,11 @@
 //
 // Slot table: long[nslots][2] = (offset, length) in floats, offsets ascending, slots disjoint; whatever lies between the end of
 // a slot and the next offset is padding and is neither read nor written.  mask: int[nslots], non-zero = trainable.
-// All four kernels are HBM- or latency-bound passes over at most a few MB (4.3 MB for U-TAE): one dword per lane and access,
+// All kernels are HBM- or latency-bound passes over at most a few MB (4.3 MB for U-TAE): one dword per lane and access,
 // coalesced, as adam_kernel (misc.hip) does it.
+//
+// Also here, on the same slot table: the learning-rate schedule (a device table read at a device position, c2s_lr_advance) and
+// Adam with a per-slot rate multiplier and weight decay (c2s_adam_slots_hp), so that a captured step replays a schedule.
 #include <limits.h>
 #include "common.h"
 
@@ -164,6 +167,78 @@ __global__ __launch_bounds__(256) void adam_slots_kernel(float* __restrict__ p, 
     }
 }
 
+// ---------------------------------------------------------------- learning-rate schedule and per-slot hyper-parameters
+// the schedule state block (16 bytes): c2s_hip.h documents the layout
+struct SchedState {
+    int t;
+    float scale;
+    float lr_now;
+    int zero;
+};
+static_assert(sizeof(SchedState) == C2S_SCHED_STATE_BYTES, "schedule state block layout");
+
+// One workgroup.  Applied step: lr_now = table[min(t, n - 1)] * scale (in double, rounded once), t += 1; a skipped step leaves the
+// block alone.  Without a status block nobody has counted the step yet: the trainable slots' counts advance here.
+__global__ __launch_bounds__(256) void lr_advance_kernel(SchedState* __restrict__ sc, const float* __restrict__ table, int n,
+                                                         const int* __restrict__ mask, int* __restrict__ slot_steps, int nslots,
+                                                         const GuardStatus* __restrict__ st) {
+    if (st != nullptr) {
+        if (st->ok == 0) return;
+    } else {
+        for (int s = threadIdx.x; s < nslots; s += blockDim.x)
+            if (mask[s] != 0) slot_steps[s] += 1;
+    }
+    if (threadIdx.x == 0) {
+        const int t = sc->t;
+        int k = t < n - 1 ? t : n - 1;
+        k = k < 0 ? 0 : k;
+        sc->lr_now = (float)((double)table[k] * (double)sc->scale);
+        sc->t = t < INT_MAX ? t + 1 : t;
+    }
+}
+
+// adam_slots_kernel with the rate from the schedule block and (lr multiplier, weight decay) per slot: hp is float[nslots][2],
+// read where the bias corrections are read.  A slot without decay runs adam_element as adam_slots_kernel does.
+__global__ __launch_bounds__(256) void adam_slots_hp_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            const long* __restrict__ slots, const int* __restrict__ mask,
+                                                            const int* __restrict__ slot_steps, const float* __restrict__ hp,
+                                                            int nslots, long total, const SchedState* __restrict__ sc, float b1,
+                                                            float b2, float eps, int decoupled, float grad_scale,
+                                                            const GuardStatus* __restrict__ st) {
+    float gscale = grad_scale;
+    if (st != nullptr) {
+        if (st->ok == 0) return;                                // a skipped step writes nothing
+        gscale = st->scale;
+    }
+    const float lr_now = sc->lr_now;
+    const long base = (long)blockIdx.x * GD_CHUNK;
+    SlotCursor cur;
+    cur.start(slots, mask, nslots, base, total);
+    int bs = -1;                                                // the slot bc1 / bc2s / lr / wd belong to
+    float bc1 = 1.f, bc2s = 1.f, lr = 0.f, wd = 0.f;
+    for (int k = 0; k < GD_CHUNK / 256; ++k) {
+        const long i = base + k * 256 + threadIdx.x;
+        if (i >= total) break;
+        cur.seek(i, total);
+        if (!cur.live(i)) continue;
+        if (cur.s != bs) {
+            bs = cur.s;
+            adam_bias(b1, b2, slot_steps[bs], bc1, bc2s);
+            lr = lr_now * hp[2 * bs];
+            wd = hp[2 * bs + 1];
+        }
+        if (wd == 0.f) {
+            adam_element(p, g, m, v, i, lr, b1, b2, eps, bc1, bc2s, gscale);
+        } else if (decoupled != 0) {                            // torch.optim.AdamW: p *= 1 - lr wd, then the step
+            p[i] = p[i] * (1.f - lr * wd);
+            adam_element(p, g, m, v, i, lr, b1, b2, eps, bc1, bc2s, gscale);
+        } else {                                                // torch.optim.Adam(weight_decay=): g += wd p, after the clip
+            adam_element_wd(p, g, m, v, i, lr, b1, b2, eps, bc1, bc2s, gscale, wd);
+        }
+    }
+}
+
 __global__ void restore_if_skipped_kernel(float* __restrict__ dst, const float* __restrict__ saved, long n,
                                           const GuardStatus* __restrict__ st) {
     if (st->ok != 0) return;
@@ -211,6 +286,32 @@ extern "C" int c2s_adam_slots(float* p, const float* g, float* m, float* v, cons
     hipLaunchKernelGGL(adam_slots_kernel, dim3((int)nchunks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, slots, mask,
                        slot_steps, nslots, total, lr, b1, b2, eps, (const GuardStatus*)status);
     C2S_CHECK_LAUNCH("adam_slots");
+    return C2S_OK;
+}
+
+extern "C" int c2s_lr_advance(void* sched, const float* table, int n, const int* mask, int* slot_steps, int nslots,
+                              const void* status, void* stream) {
+    C2S_REQUIRE(sched && table && mask && slot_steps && n >= 1 && nslots > 0, "lr_advance: bad args");
+    C2S_REQUIRE((uintptr_t)sched % 8 == 0 && (uintptr_t)status % 8 == 0, "lr_advance: sched / status not 8-byte aligned");
+    hipLaunchKernelGGL(lr_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (SchedState*)sched, table, n, mask,
+                       slot_steps, nslots, (const GuardStatus*)status);
+    C2S_CHECK_LAUNCH("lr_advance");
+    return C2S_OK;
+}
+
+extern "C" int c2s_adam_slots_hp(float* p, const float* g, float* m, float* v, const long* slots, const int* mask,
+                                 const int* slot_steps, const float* hp, int nslots, long total, const void* sched, float b1,
+                                 float b2, float eps, int decoupled, float grad_scale, const void* status, void* stream) {
+    C2S_REQUIRE(p && g && m && v && slots && mask && slot_steps && hp && sched && nslots > 0 && total > 0,
+                "adam_slots_hp: bad args");
+    C2S_REQUIRE((uintptr_t)sched % 8 == 0 && (uintptr_t)status % 8 == 0, "adam_slots_hp: sched / status not 8-byte aligned");
+    C2S_REQUIRE(status != nullptr || grad_scale > 0.f, "adam_slots_hp: grad_scale %g", (double)grad_scale);
+    const long nchunks = (total + GD_CHUNK - 1) / GD_CHUNK;
+    C2S_REQUIRE(nchunks <= INT_MAX, "adam_slots_hp: %ld floats are more than one grid covers", total);
+    hipLaunchKernelGGL(adam_slots_hp_kernel, dim3((int)nchunks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, slots, mask,
+                       slot_steps, hp, nslots, total, (const SchedState*)sched, b1, b2, eps, decoupled, grad_scale,
+                       (const GuardStatus*)status);
+    C2S_CHECK_LAUNCH("adam_slots_hp");
     return C2S_OK;
 }
 

@@ -1574,6 +1574,43 @@ def restore_if_skipped(dst: Tensor, saved: Tensor, status: Tensor) -> None:
           "restore_if_skipped")
 
 
+# Learning-rate schedule and per-slot hyper-parameters on the device (csrc/guard.hip; the layout of the schedule block:
+# include/c2s_hip.h).  `sched` is the int32[4] tensor of sched_state(), `table` float32 [n], `hp` float32 [nslots, 2] =
+# (lr multiplier, weight decay); `status` None = an unguarded step.
+SCHED_STATE_BYTES = 16
+
+
+def sched_state(device, t: int = 0, scale: float = 1.0) -> Tensor:
+    """A schedule block at position `t` with `scale`; `sched_views` names its fields (host -> device copy: not under capture)."""
+    host = torch.zeros(SCHED_STATE_BYTES // 4, dtype=torch.int32)
+    host[0] = int(t)
+    host.view(torch.float32)[1] = float(scale)
+    return host.to(device)
+
+
+def sched_views(sched: Tensor) -> Dict[str, Tensor]:
+    """0-dim views of the schedule block's fields (no copy, no synchronisation until a value is read)."""
+    f = sched.view(torch.float32)
+    return {"t": sched[0], "scale": f[1], "lr_now": f[2]}
+
+
+def lr_advance(sched: Tensor, table: Tensor, mask: Tensor, slot_steps: Tensor, status: Optional[Tensor] = None) -> None:
+    """On an applied step: sched.lr_now = table[min(t, n - 1)] * scale, t += 1; without `status` also the trainable slots'
+    step counts (a guarded step's step_decide has advanced them)."""
+    check(lib().c2s_lr_advance(sched.data_ptr(), table.data_ptr(), table.numel(), mask.data_ptr(), slot_steps.data_ptr(),
+                               mask.numel(), _ptr(status), _stream()), "lr_advance")
+
+
+def adam_slots_hp(p: Tensor, g: Tensor, m: Tensor, v: Tensor, slots: Tensor, mask: Tensor, slot_steps: Tensor, hp: Tensor,
+                  sched: Tensor, status: Optional[Tensor] = None, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
+                  decoupled: bool = False, grad_scale: float = 1.0) -> None:
+    """`adam_slots` with the rate sched.lr_now * hp[s, 0] and the weight decay hp[s, 1] per slot, coupled (torch.optim.Adam) or
+    decoupled (torch.optim.AdamW).  Without `status` the step is always applied, the gradient scaled by `grad_scale`."""
+    check(lib().c2s_adam_slots_hp(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), slots.data_ptr(), mask.data_ptr(),
+                                  slot_steps.data_ptr(), hp.data_ptr(), mask.numel(), p.numel(), sched.data_ptr(), b1, b2, eps,
+                                  int(bool(decoupled)), float(grad_scale), _ptr(status), _stream()), "adam_slots_hp")
+
+
 # Training-state snapshots (csrc/snapshot.hip; blob and status layouts: include/c2s_hip.h).  All stream-ordered.  The layout is
 # planned by checkpoint.plan_layout (pure host code); `snapshot_table` turns it into the device table.
 SNAPSHOT_HEADER_BYTES = 64

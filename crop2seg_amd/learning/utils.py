@@ -153,12 +153,28 @@ class TrainStep:
     belong to the default loss only.  It runs eagerly and inside capture() / replay() (it must not synchronise with the
     host).  Data parallel: every rank evaluates the criterion on its own batch -- RecallCrossEntropy weighs by the recall of
     the rank's batch, which is what the reference does under torch DDP; the gradients are averaged as always.
+
+    Schedule, groups and weight decay (with `lr_schedule`, `schedule_steps`, `weight_decay`,
+    `decoupled_weight_decay` and `param_groups` at their defaults the step launches exactly what it launched without them).
+      lr_schedule: None = the one-entry table [lr]; a sequence of floats = the table, table[t] the rate of the (t+1)-th applied
+        step, the last entry held past the end; a callable f(t), evaluated on the host for t in range(schedule_steps)
+        (learning/schedules.py: warmup_cosine, from_torch).  The table and the position live on the device, so the rate moves
+        under replay(); a skipped step does not advance it.
+      weight_decay: torch.optim.Adam(weight_decay=) -- the decay joins the clipped gradient -- or, with
+        decoupled_weight_decay=True, torch.optim.AdamW.  A frozen parameter is not decayed.
+      param_groups: [{"params": a name prefix | a list of names or prefixes | a predicate on the name, "lr_mult": 1.0,
+        "weight_decay": the global one}]; unmatched parameters take lr_mult 1 and the global decay.
+    The step then runs c2s_lr_advance and c2s_adam_slots_hp over the guarded step's slot table, guarded or not.  Readers:
+    `last_lr` (device scalar), `schedule_position()` (host synchronisation); `set_lr_scale(s)` multiplies every entry from the next
+    step on (reduce-on-plateau).  Snapshots carry the position and the scale; the table and the groups are the constructor's.
     """
 
     def __init__(self, model, num_classes: int = 15, ignore_index: int = -1, lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, process_group=None,
                  distributed: bool = False, label_smoothing: float = 0.0, boundary_gamma: float = 2.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, criterion=None):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, criterion=None,
+                 lr_schedule=None, schedule_steps: Optional[int] = None, weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False, param_groups=None):
         self.model = model
         if criterion is not None:
             if not callable(criterion) or not callable(getattr(criterion, "grad", None)):
@@ -207,8 +223,13 @@ class TrainStep:
         self.class_w = cw
         self.step_count = 0
         self.ws = E.Workspace(dev)
+        # schedule / groups / weight decay: on when any of the five arguments is non-default
+        self.hp = (lr_schedule is not None or schedule_steps is not None or float(weight_decay) != 0.0
+                   or bool(decoupled_weight_decay) or param_groups is not None)
         if self.guarded:
             self._init_guard(dev)
+        if self.hp:
+            self._init_hp(dev, lr_schedule, schedule_steps, weight_decay, decoupled_weight_decay, param_groups)
         self.dp = None
         if distributed:
             from .ddp import FlatDataParallel
@@ -220,11 +241,7 @@ class TrainStep:
     def _init_guard(self, dev) -> None:
         """Device state of the guarded step: slot table, mask, per-slot step counts, status block, skip counter; with
         skip_nonfinite also the model's floating-point buffers as views of one flat tensor, and its copy."""
-        table, _ = slot_table(self.offsets, self.total, [True] * len(self.offsets))
-        self._slots_dev = torch.tensor(table, device=dev, dtype=torch.int64)
-        self._mask_dev = torch.zeros(len(table), device=dev, dtype=torch.int32)
-        self._mask_flags: Optional[List[bool]] = None            # the flags `_mask_dev` holds
-        self.slot_steps_dev = torch.tensor(self.param_steps, device=dev, dtype=torch.int32)
+        self._init_slots(dev)
         self._status = E.guard_status(dev)
         self._skip_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         views = E.guard_views(self._status)
@@ -245,6 +262,66 @@ class TrainStep:
                 b.data = view                           # the module's buffers now alias the flat tensor
                 o += (b.numel() + 3) // 4 * 4
 
+    def _init_slots(self, dev) -> None:
+        """Slot table, mask and per-slot step counts on the device: shared by the guarded step and the schedule path."""
+        if getattr(self, "_slots_dev", None) is not None:
+            return
+        table, _ = slot_table(self.offsets, self.total, [True] * len(self.offsets))
+        self._slots_dev = torch.tensor(table, device=dev, dtype=torch.int64)
+        self._mask_dev = torch.zeros(len(table), device=dev, dtype=torch.int32)
+        self._mask_flags: Optional[List[bool]] = None            # the flags `_mask_dev` holds
+        self.slot_steps_dev = torch.tensor(self.param_steps, device=dev, dtype=torch.int32)
+
+    # ------------------------------------------------------------------- schedule, groups and weight decay (DESIGN.md 7d)
+    def _init_hp(self, dev, lr_schedule, schedule_steps, weight_decay, decoupled, param_groups) -> None:
+        """Device state of the schedule path: the rate table, the schedule block (t, scale, lr_now) and (lr multiplier, weight
+        decay) per slot; it walks the guarded step's slot table whether or not the step is guarded."""
+        from . import schedules as S
+        self.lr_table = S.schedule_table(self.lr, lr_schedule, schedule_steps)
+        self.weight_decay = float(weight_decay)
+        self.decoupled = bool(decoupled)
+        self.slot_hp = S.resolve_param_groups(self.names, param_groups, self.weight_decay)
+        self._init_slots(dev)
+        self._table_dev = torch.tensor(self.lr_table, dtype=torch.float32).to(dev)
+        self._hp_dev = torch.tensor(self.slot_hp, dtype=torch.float32).reshape(-1, 2).contiguous().to(dev)
+        self.sched_dev = E.sched_state(dev)
+        self._sched_views = E.sched_views(self.sched_dev)
+        self.last_lr = self._sched_views["lr_now"]
+
+    def _need_hp(self) -> None:
+        if not self.hp:
+            raise RuntimeError("TrainStep: built without lr_schedule / weight_decay / param_groups, there is no schedule to read")
+
+    def _hp_update(self, scale: float, status: Optional[Tensor] = None) -> None:
+        """The rate of this step, then Adam over all slots with it; `status` None: the unguarded step."""
+        E.lr_advance(self.sched_dev, self._table_dev, self._mask_dev, self.slot_steps_dev, status)
+        E.adam_slots_hp(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self._slots_dev, self._mask_dev,
+                        self.slot_steps_dev, self._hp_dev, self.sched_dev, status, self.betas[0], self.betas[1], self.eps,
+                        decoupled=self.decoupled, grad_scale=scale)
+
+    def schedule_position(self) -> int:
+        """Applied steps the schedule has seen = index of the next table entry (reads the device: host synchronisation)."""
+        self._need_hp()
+        return int(self._sched_views["t"])
+
+    def set_lr_scale(self, s: float) -> None:
+        """Multiply every table entry by `s` from the next step on (reduce-on-plateau: set_lr_scale(0.1 * current)): a
+        stream-ordered write into the schedule block, legal between replays, not inside a capture."""
+        self._need_hp()
+        s = float(s)
+        if not (s >= 0.0 and s != float("inf")):
+            raise ValueError(f"TrainStep.set_lr_scale: {s!r}, a finite scale >= 0 is needed")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TrainStep.set_lr_scale(): not inside a hipGraph capture (the graph would bake the value in)")
+        self._sched_views["scale"].fill_(s)
+
+    def _optim_record(self) -> dict:
+        """What a snapshot notes about the schedule path, for diagnosis on load."""
+        from . import schedules as S
+        return {"table_len": len(self.lr_table), "table_digest": S.table_digest(self.lr_table), "table": list(self.lr_table),
+                "groups": {n: [float(a), float(b)] for n, (a, b) in zip(self.names, self.slot_hp)},
+                "decoupled": self.decoupled, "weight_decay": self.weight_decay}
+
     def _set_mask(self, flags: List[bool]) -> None:
         """Upload the mask of trainable slots when the flags have changed (stream-ordered copy; never under capture)."""
         if flags != self._mask_flags:
@@ -261,8 +338,11 @@ class TrainStep:
         E.grad_sumsq(self.flat_grad, self._slots_dev, self._mask_dev, self.ws, self._status)
         E.step_decide(self._status, self.max_grad_norm, scale, self.skip_nonfinite, self._mask_dev, self.slot_steps_dev,
                       self._skip_dev)
-        E.adam_slots(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self._slots_dev, self._mask_dev,
-                     self.slot_steps_dev, self._status, self.lr, self.betas[0], self.betas[1], self.eps)
+        if self.hp:
+            self._hp_update(scale, self._status)
+        else:
+            E.adam_slots(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self._slots_dev, self._mask_dev,
+                         self.slot_steps_dev, self._status, self.lr, self.betas[0], self.betas[1], self.eps)
         if self.flat_buf is not None and self.flat_buf.numel():
             E.restore_if_skipped(self.flat_buf, self._buf_saved, self._status)
 
@@ -427,6 +507,8 @@ class TrainStep:
         if self.guarded and apply_update:
             self._set_mask(flags)
             self._save_buffers()                         # what a skipped step puts back
+        elif self.hp and apply_update:
+            self._set_mask(flags)
         loss, logits = self._forward_backward(x.contiguous(), dates.contiguous(), y, drop, overlap_exchange=True, flags=flags)
         xruns = self._xruns(flags)
         scale = 1.0
@@ -449,6 +531,9 @@ class TrainStep:
                 self._attempts += 1
                 self._guarded_update(scale)
                 return loss, logits
+            if self.hp:
+                self._hp_update(scale)
+                return loss, logits
             for b, e, st in self._adam_runs(flags):
                 E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], st, self.lr,
                             self.betas[0], self.betas[1], self.eps, grad_scale=scale)
@@ -469,8 +554,9 @@ class TrainStep:
         if not any(flags):
             raise ValueError("TrainStep: no parameter requires grad")
         self.static_x, self.static_dates, self.static_y = x.clone().contiguous(), dates.clone().contiguous(), y.clone()
-        if self.guarded:
-            self._set_mask(flags)                       # the guarded step keeps its step counts per slot (slot_steps_dev)
+        runs = None
+        if self.guarded or self.hp:
+            self._set_mask(flags)                       # these steps keep their step counts per slot (slot_steps_dev)
         else:
             runs = self._adam_runs(flags)               # one device step counter per Adam launch
             self.step_dev = torch.tensor([st for _, _, st in runs], device=dev, dtype=torch.int32)
@@ -522,13 +608,15 @@ class TrainStep:
         with torch.cuda.graph(self.graph_opt, capture_error_mode="thread_local"):
             if self.guarded:                            # after the exchange that sits between the two graphs
                 self._guarded_update(scale)
+            elif self.hp:                               # the rate and the step counts advance on the device: no step_dev
+                self._hp_update(scale)
             else:
                 self.step_dev.add_(1)
                 for k, (b, e, _) in enumerate(runs):
                     E.adam_flat(self.flat_param[b:e], self.flat_grad[b:e], self.exp_avg[b:e], self.exp_avg_sq[b:e], 0, self.lr,
                                 self.betas[0], self.betas[1], self.eps, grad_scale=scale, step_dev=self.step_dev[k:k + 1])
         self._cap_flags = flags
-        self._cap_runs = None if self.guarded else runs
+        self._cap_runs = runs
 
     @torch.no_grad()
     def replay(self, x: Optional[Tensor] = None, dates: Optional[Tensor] = None, y: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
@@ -573,8 +661,12 @@ class TrainStep:
                 regs.append(("buffer:" + k, b))
         if self.guarded:
             regs += [("slot_steps_dev", self.slot_steps_dev), ("_skip_dev", self._skip_dev)]
-        if self._captured():
+        if self.hp:
             if not self.guarded:
+                regs.append(("slot_steps_dev", self.slot_steps_dev))
+            regs.append(("sched_dev", self.sched_dev))
+        if self._captured():
+            if not self.guarded and not self.hp:
                 regs.append(("step_dev", self.step_dev))
             regs.append(("seed_dev", self.seed_dev))
         return regs
@@ -655,6 +747,8 @@ class TrainStep:
             guard={"max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite} if self.guarded else None,
             capture={"calls": self._cap_calls, "base": self._cap_base, "flags": list(self._cap_flags)} if self._captured() else None,
             trainable=dict(zip(self.names, self.trainable_flags())), lr=self.lr, betas=tuple(self.betas), eps=self.eps)
+        if self.hp:
+            meta["optim"] = self._optim_record()
         return CK.Snapshot(host, done, plan["regions"], meta)
 
     def _check_state(self, state: dict, exact: bool) -> None:
@@ -681,6 +775,9 @@ class TrainStep:
             if theirs != (self.guarded, self.skip_nonfinite):
                 diffs.append(f"guard mode: the state has (guarded, skip_nonfinite) = {theirs}, this step "
                              f"{(self.guarded, self.skip_nonfinite)}")
+            if extra.get("optim") is not None and not self.hp:
+                diffs.append("schedule mode: the state was written with lr_schedule / weight_decay / param_groups (its step "
+                             "counts and schedule position live on the device), this step was built without them")
             if len(extra["param_steps"]) != len(self.names):
                 diffs.append(f"step counts: {len(extra['param_steps'])} in the state, {len(self.names)} parameters")
         if diffs:
@@ -696,7 +793,13 @@ class TrainStep:
         ValueError (with the list of differences) when names, shapes or guard mode differ; RuntimeError when the device refused
         the blob (its sums do not match the state's record) or when a captured step is given a state that does not carry its
         dropout base.  In all three cases nothing has been written.  A state with only the reference's keys loads parameters,
-        buffers, moments and step counts; the return value's "bit_exact" is False then, and a warning says so."""
+        buffers, moments and step counts; the return value's "bit_exact" is False then, and a warning says so.
+
+        On the schedule path the schedule block comes back from the state's own words; the table, the groups and
+        the decay stay the constructor's, and the return value says where the state's record differs ("optim_differs":
+        {"schedule", "groups", "mode"}).  A state written without the path starts the schedule at its applied step count with
+        scale 1 ("optim_differs" None; "schedule_bit_exact" False if its per-slot counts are unequal).  A state written with the
+        path does not fit a step built without it (ValueError)."""
         from .. import checkpoint as CK
         import numpy as np
         exact = CK.is_bit_exact(state)
@@ -712,7 +815,7 @@ class TrainStep:
         if self._captured():
             fits = cap is not None and list(cap["flags"]) == list(self._cap_flags) and \
                 self._dropout_base(extra["seed_root"], cap["calls"], self._rank()) == self._cap_base
-            if fits and not self.guarded:
+            if fits and not self.guarded and not self.hp:
                 first = {o: i for i, o in reversed(list(enumerate(self.offsets)))}
                 ends = list(self.offsets[1:]) + [self.total]
                 for b, e, _ in self._cap_runs:
@@ -742,6 +845,23 @@ class TrainStep:
         if self.guarded:
             values["slot_steps_dev"] = torch.tensor(steps, dtype=torch.int32)
             values["_skip_dev"] = torch.tensor([extra["guard"]["skipped"] if exact else 0], dtype=torch.int32)
+        report = {}
+        if self.hp:
+            theirs = extra.get("optim") if exact else None
+            values["slot_steps_dev"] = torch.tensor(steps, dtype=torch.int32)
+            if theirs is not None:                      # t and scale as the device held them
+                values["sched_dev"] = torch.tensor([int(w) for w in theirs["sched_words"]], dtype=torch.int32)
+                mine = self._optim_record()
+                report["optim_differs"] = {
+                    "schedule": (theirs["table_len"], theirs["table_digest"]) != (mine["table_len"], mine["table_digest"]),
+                    "groups": {k: list(v) for k, v in theirs["groups"].items()} != mine["groups"],
+                    "mode": (bool(theirs["decoupled"]), float(theirs["weight_decay"])) != (mine["decoupled"], mine["weight_decay"])}
+                report["schedule_bit_exact"] = True
+            else:                                       # a state from a step without a schedule: t = its applied steps, scale 1
+                t0 = int(extra["step_count"]) if exact else (max(steps) if steps else 0)
+                values["sched_dev"] = E.sched_state("cpu", t0, 1.0)
+                report["optim_differs"] = None
+                report["schedule_bit_exact"] = len(set(steps)) <= 1     # unequal counts: no single position fits them all
         # the blob, in this step's layout; its header carries the sums the state recorded, region by region
         host = torch.zeros(E.SNAPSHOT_HEADER_BYTES + plan["payload"], dtype=torch.uint8, pin_memory=True)
         arr = host.numpy()
@@ -784,7 +904,7 @@ class TrainStep:
             CK.warn_not_bit_exact()
         if not self._captured():
             self._pending_capture = None if cap is None else {"calls": int(cap["calls"]), "seed_dev": int(cap["seed_dev"])}
-        return {"bit_exact": exact, "epoch": state.get("epoch"), "best_mIoU": state.get("best_mIoU")}
+        return dict({"bit_exact": exact, "epoch": state.get("epoch"), "best_mIoU": state.get("best_mIoU")}, **report)
 
     def load(self, path) -> dict:
         """load_state_dict of a file written by Snapshot.save() -- or by the reference's train.py (model.pth.tar)."""

@@ -645,6 +645,35 @@ int c2s_adam_slots(float* p, const float* g, float* m, float* v, const long* slo
 int c2s_restore_if_skipped(float* dst, const float* saved, long n, const void* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Learning-rate schedule, per-slot learning-rate multipliers and weight decay on the device (csrc/guard.hip).  The rate of a
+ * step is read from a device table at a device position, so a captured hipGraph replays a schedule; the slot table, mask and
+ * slot_steps are those of the guarded step above.  Nothing is read back, allocated or synchronised.
+ *
+ * Schedule state block (C2S_SCHED_STATE_BYTES, 8-byte aligned):
+ *     byte 0  int    t        applied steps so far = index of the next table entry
+ *     byte 4  float  scale    a factor on every table entry (the host may write it between steps; 1 at the start)
+ *     byte 8  float  lr_now   the rate of the last applied step                     (c2s_lr_advance)
+ *     byte 12 one zero word
+ *
+ *   c2s_lr_advance: one launch.  table: DEVICE float[n], n >= 1.  When the step is applied (status == NULL, or status.ok == 1):
+ *     lr_now = (float)((double)table[min(t, n - 1)] * (double)scale), then t += 1 (past its end the table holds its last
+ *     entry).  On a skipped step the block stays as it is.  status == NULL (a step without c2s_step_decide): it also does
+ *     slot_steps[s] += 1 for every trainable slot; with a status c2s_step_decide has done that already.
+ *   c2s_adam_slots_hp: c2s_adam_slots with the rate from the block and hp = DEVICE float[nslots][2] = (lr multiplier, weight
+ *     decay) per slot: lr_s = lr_now * mult_s.  status == NULL: always apply, gradient scale = grad_scale; otherwise status.ok /
+ *     status.scale decide and grad_scale is ignored.  With wd_s != 0:
+ *       decoupled == 0 (torch.optim.Adam(weight_decay=)): gg = g * gscale + wd_s * p, then the element arithmetic of Adam;
+ *       decoupled != 0 (torch.optim.AdamW):               p = p * (1 - lr_s * wd_s), then the element arithmetic on that p.
+ *     wd_s == 0: the arithmetic of c2s_adam_slots.  Frozen slots and padding are neither read nor written (nor decayed).
+ * ------------------------------------------------------------------------------------------------ */
+#define C2S_SCHED_STATE_BYTES 16
+int c2s_lr_advance(void* sched, const float* table, int n, const int* mask, int* slot_steps, int nslots, const void* status,
+                   void* stream);
+int c2s_adam_slots_hp(float* p, const float* g, float* m, float* v, const long* slots, const int* mask,
+                      const int* slot_steps, const float* hp, int nslots, long total, const void* sched, float b1, float b2,
+                      float eps, int decoupled, float grad_scale, const void* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-state snapshots (csrc/snapshot.hip): many live device regions <-> one contiguous device blob, in the job-table
  * idiom of c2s_pack_batch.  Nothing is read back, allocated or synchronised: every call is legal inside a hipGraph capture.
  *

@@ -4,8 +4,11 @@ the variants alternating from repetition to repetition so that clock and neighbo
 
     python tools/guard_timing.py [--steps 40] [--warmup 10] [--reps 5] [--tree DIR] [--variants eager,eager_guard,...]
 
---tree DIR imports crop2seg_amd from another checkout (built there), e.g. the parent commit, which knows only the unguarded
-variants; compare trees by alternating runs of this script.  Every window ends in a device synchronise and is timed with the
+The variants eager_hp, graph_hp, eager_guard_hp and graph_guard_hp add the schedule path (TrainStep(lr_schedule=, param_groups=,
+weight_decay=, decoupled_weight_decay=True)): --variants eager,eager_hp,graph,graph_hp,eager_guard,eager_guard_hp,graph_guard,graph_guard_hp.
+
+--tree DIR imports crop2seg_amd from another checkout (built there), e.g. the parent commit, which knows only the variants of
+its time; compare trees by alternating runs of this script.  Every window ends in a device synchronise and is timed with the
 host clock; per variant the script prints one JSON line with the per-repetition ms/step, their median, minimum and spread
 (max - min).  Profiling belongs in a run of its own (rocprofv3 --kernel-trace --stats -- python tools/guard_timing.py --reps 1).
 """
@@ -42,7 +45,16 @@ def main():
         net = C2S.UTAE(input_dim=10, out_conv=[32, 15]).cuda()
         net.apply(C2S.weight_init)
         net.train()
-        kw = dict(max_grad_norm=1.0, skip_nonfinite=True) if name.endswith("_guard") else {}
+        kw = dict(max_grad_norm=1.0, skip_nonfinite=True) if "_guard" in name else {}
+        if name.endswith("_hp"):
+            # the schedule path: a warm-up / cosine table, two groups (the encoder at a tenth of the rate; gains and biases
+            # undecayed) and decoupled decay
+            from crop2seg_amd.learning import schedules as S
+            nd = set(S.no_decay_names(net))
+            enc = ("in_conv.", "down_blocks.")
+            kw.update(lr_schedule=S.warmup_cosine(1e-3, 20, 2000), weight_decay=1e-2, decoupled_weight_decay=True,
+                      param_groups=[{"params": lambda n: n.startswith(enc) and n not in nd, "lr_mult": 0.1},
+                                    {"params": sorted(nd), "weight_decay": 0}])
         step = TrainStep(net, num_classes=15, **kw)
         if name.startswith("graph"):
             step(x, dates, y)
