@@ -1,6 +1,7 @@
 """Build libc2s_hip.so (gfx950) in-tree with hipcc.  No torch dependency: the library is a plain C ABI."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -31,9 +32,8 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     cc = hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ltae_drop.h"), os.path.join(CSRC, "ltae_long.h"),
-               os.path.join(CSRC, "parcels_uf.h"),
-               os.path.join(os.path.dirname(HERE), "include", "c2s_hip.h")]
+    # every object depends on every header: none can be missed by the staleness check
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "c2s_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -110,6 +110,12 @@ constexpr int W16_UP = 16;                          // floats per (c, o): the 16
 constexpr int S2_UP = 12;                           // conv_s2wino.hip: floats per (c, parity, o): 9 points + 3 zeros
 constexpr int D2_UP = 12;                           // conv_s2dgrad.hip: floats per (k, parity, c): 9 points + 3 zeros
 
+// XCD-aware order: workgroups go to the 8 XCDs round-robin in launch order, so item i of n is renumbered such that XCD k gets
+// the k-th contiguous eighth of the items (neighbours, which share halo rows or cache lines, then sit behind the same L2).
+// The identity where n does not divide by 8.  A macro, in the caller's index type (int or unsigned): as an inline function
+// the same expression came out with the other branch polarity in the persistent kernels, whose assembly is pinned.
+#define C2S_XCD_ORDER(i, n) (((n) & 7) == 0 ? ((i) & 7) * ((n) >> 3) + ((i) >> 3) : (i))
+
 __device__ __forceinline__ int reflect_idx(int i, int n) {
     // single reflection (pad < n): -1 -> 1, n -> n-2
     i = i < 0 ? -i : i;

@@ -17,24 +17,15 @@
 // Reflect adjoint (ADJ): the fold of the halo gradient is realised as extra MFMA k-steps whose B operand is the
 // shifted input for the border lanes and a zero slot for all others (no bf16 arithmetic needed); only waves that
 // own border positions execute them.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-struct BxParams {
-    const float* src0;
-    const float* src1;
+struct BxParams : TileParams {      // (wpk unused: the weights come split)
     const __bf16* whi;
     const __bf16* wlo;
-    const float* bias;
-    float* out;
-    const int* valid;
-    int C0, C1, Hin, Win, Cout, CoutP, Hout, Wout;
-    int pad_mode, accumulate;
-    int log2fc, tiles_x;
-    int adj, ay_lo, ay_hi, ax_lo, ax_hi;
     int single;            // measurement mode: activations rounded to bf16 (no lo part) -- with zeroed wlo a plain bf16 x bf16 product
 };
 
@@ -83,24 +74,16 @@ __global__ __launch_bounds__(256) void conv3x3_bf16x3_kernel(BxParams p) {
         const int e = tid + i * 256;
         int off = -1;
         if (e < plane) {
-            const int r = e / cols, cc = e - r * cols;
-            int gy = oy0 - 1 + r, gx = ox0 - 1 + cc;
-            bool ok;
-            if (p.pad_mode == C2S_PAD_REFLECT) {
-                ok = gy >= -1 && gy <= p.Hin && gx >= -1 && gx <= p.Win;
-                gy = reflect_idx(gy, p.Hin);
-                gx = reflect_idx(gx, p.Win);
-            } else {
-                ok = gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
-            }
-            if (ok) off = (gy * p.Win + gx) * 4;
+            const int r = e / cols;
+            const int px = tile_pixel_offset(oy0 - 1 + r, ox0 - 1 + e - r * cols, p.Hin, p.Win, 1, 1, p.pad_mode);
+            if (px >= 0) off = px * 4;
         }
         poff[i] = off;
     }
 
-    const int lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int fy = li >> p.log2fc, fx = li & (FC - 1);
+    const int wave = tid >> 6;
+    const TileLane ln = tile_lane(tid, p.log2fc);
+    const int li = ln.li, lh = ln.lk, fy = ln.fy, fx = ln.fx;
     int pbase[2];                     // LDS position index (tap 0,0) of the two position fragments
     int oyq[2], oxq;
 #pragma unroll
@@ -310,7 +293,8 @@ __global__ __launch_bounds__(256) void conv3x3_bf16x3_kernel(BxParams p) {
         __syncthreads();
     }
 
-    // ---- epilogue (identical to the exact-fp32 kernel): row = channel, column = position
+    // ---- epilogue: row = channel, column = position; one address per element serves the read and the store (tile_store computes
+    // it twice, which shows behind this kernel's fast bf16 loop: profiles/conv_tile_refactor.txt 4)
     const size_t outHW = (size_t)p.Hout * p.Wout;
     float* on = p.out + (size_t)n * p.Cout * outHW;
 #pragma unroll
@@ -398,33 +382,23 @@ extern "C" int c2s_pack_weights_bf16x3(const float* src, void* whi, void* wlo, i
 
 extern "C" int c2s_conv3x3_bf16x3(const c2s_conv_desc* d, const float* src0, const float* src1, const void* whi,
                                   const void* wlo, const float* bias, float* out, const int* valid, void* stream) {
-    C2S_REQUIRE(d && src0 && whi && wlo && out, "conv3x3_bf16x3: null pointer");
+    if (const int rc = tile_check("conv3x3_bf16x3", d, src0 && whi && wlo && out)) return rc;
     C2S_REQUIRE(d->KH == 3 && d->KW == 3 && d->S == 1 && d->pad_y == 1 && d->pad_x == 1, "conv3x3_bf16x3: 3x3 stride 1 pad 1 only");
     C2S_REQUIRE(d->Hin == d->Hout && d->Win == d->Wout && d->OutH == d->Hout && d->OutW == d->Wout && d->osy == 1 &&
                     d->osx == 1 && d->ooy == 0 && d->oox == 0, "conv3x3_bf16x3: dense same-size output only");
     C2S_REQUIRE(d->C0 % 8 == 0 && d->C1 % 8 == 0 && (d->C1 == 0 || src1), "conv3x3_bf16x3: channel counts must be multiples of 8");
-    C2S_REQUIRE(d->CoutP % 32 == 0 && d->CoutP >= d->Cout, "conv3x3_bf16x3: CoutP must be a multiple of 32");
-    C2S_REQUIRE(d->N <= C2S_CONV_MAX_FRAMES, "conv3x3_bf16x3: more than 65535 frames in one launch (N = %d): the frame index is gridDim.z", d->N);
-    C2S_REQUIRE((long)(d->C0 > d->C1 ? d->C0 : d->C1) * d->Hin * d->Win * 4 < (1L << 31), "conv3x3_bf16x3: frame too large");
     if (d->pad_mode == C2S_PAD_REFLECT) C2S_REQUIRE(d->Hin >= 2 && d->Win >= 2, "conv3x3_bf16x3: reflect needs planes >= 2");
     BxParams p;
-    p.src0 = src0; p.src1 = src1; p.whi = (const __bf16*)whi; p.wlo = (const __bf16*)wlo; p.bias = bias; p.out = out;
-    p.valid = valid; p.C0 = d->C0; p.C1 = d->C1; p.Hin = d->Hin; p.Win = d->Win; p.Cout = d->Cout; p.CoutP = d->CoutP;
-    p.Hout = d->Hout; p.Wout = d->Wout; p.pad_mode = d->pad_mode; p.accumulate = d->accumulate;
-    p.adj = d->reflect_adjoint;
+    tile_fill(p, d, src0, src1, nullptr, bias, out, valid);
+    p.whi = (const __bf16*)whi; p.wlo = (const __bf16*)wlo;
     p.single = g_single_product;
-    p.ay_lo = p.ay_hi = p.ax_lo = p.ax_hi = -1;
     if (d->reflect_adjoint) {
         C2S_REQUIRE(d->pad_mode == C2S_PAD_ZEROS && d->Hin != 3 && d->Win != 3, "conv3x3_bf16x3: bad adjoint geometry");
         p.ay_lo = 1; p.ay_hi = d->Hout - 2; p.ax_lo = 1; p.ax_hi = d->Wout - 2;
     }
-    int l2 = 5;
-    while (l2 > 2 && (1 << l2) > d->Wout) --l2;
-    p.log2fc = l2;
-    p.tiles_x = cdiv(d->Wout, 1 << l2);
-    const int tiles = p.tiles_x * cdiv(d->Hout, 8 * (32 >> l2));
+    const int tiles = tile_count(d->Hout, d->Wout, p.log2fc, 8);
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = d->CoutP % 64 == 0;
+    const bool wide = d->CoutP % 64 == 0;       // (no grid-size condition, unlike tile_wide)
     if (p.adj) return wide ? launch_bx<2, true>(p, d->N, tiles, st) : launch_bx<1, true>(p, d->N, tiles, st);
     return wide ? launch_bx<2, false>(p, d->N, tiles, st) : launch_bx<1, false>(p, d->N, tiles, st);
 }

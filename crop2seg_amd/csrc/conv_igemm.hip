@@ -24,27 +24,9 @@
 //
 // Reference call sites replaced: nn.Conv2d / nn.ConvTranspose2d in src/backbones/conv.py:70-80,
 // 263-271,378-390 and their convolution_backward-input.
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
-
-struct ConvParams {
-    const float* src0;
-    const float* src1;
-    const float* wpk;
-    const float* bias;
-    float* out;
-    const int* valid;
-    int C0, C1, Hin, Win, Cout, CoutP, Hout, Wout, OutH, OutW;
-    int pad_y, pad_x, pad_mode, osy, osx, ooy, oox, accumulate;
-    int log2fc, tiles_x;
-    // reflect adjoint (data gradient of a reflect-padded convolution).  Per dimension the fold of the halo gradient
-    // is:  operand(pos == lo, tap K-1) += input[tap position - d_lo]   and
-    //      operand(pos == hi, tap 0)   += input[tap position + d_hi]      (-1 = rule absent; d = K-1 except in the
-    //      parity sub-kernels of the 6x6 stride-2 data gradient, where the mirrored row is one or two rows away)
-    int adj, ay_lo, ay_hi, ax_lo, ax_hi;
-    int dy_lo, dy_hi, dx_lo, dx_hi;
-};
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int plane_for(int K, int S, int log2fc, int NF) {      // NF = position fragments of the tile (8 / SP)
@@ -64,34 +46,20 @@ struct Cfg {
 };
 
 template <int K, int S, int MF, bool ADJ, int SP = 1>
-__global__ __launch_bounds__((Cfg<K, S, SP>::NTHR)) void conv_igemm_kernel(ConvParams p) {
+__global__ __launch_bounds__((Cfg<K, S, SP>::NTHR)) void conv_igemm_kernel(TileParams p) {
     static_assert(SP == 1 || ((SP == 2 || SP == 4) && MF == 1), "the split tiles exist for 32-channel tiles");
     constexpr int CK = Cfg<K, S, SP>::CK;
     constexpr int NT = Cfg<K, S, SP>::NT;
-    constexpr int MAXE = Cfg<K, S, SP>::MAXE;
-    constexpr int NTHR = Cfg<K, S, SP>::NTHR;
     constexpr int NF = 8 / SP;                   // position fragments of the tile
     constexpr int NQ = SP == 1 ? 2 : 1;          // fragments (accumulators per channel fragment) of a wave
     constexpr int LA = SP == 1 ? 1 : 2;          // k-steps the operand reads run ahead of the MFMAs
     constexpr int COT = 32 * MF;
-    constexpr int WV = COT / 4;                  // float4 per (tap, channel) weight row
-    constexpr int NWV = NT * CK * WV;            // float4 items of the weight slab
-    constexpr int WPT = (NWV + NTHR - 1) / NTHR;
     constexpr int NS = NT * (CK / 2);            // MFMA k-steps per chunk
+    typedef TileStage<CK, Cfg<K, S, SP>::MAXE, Cfg<K, S, SP>::NTHR, NT, COT> Stage;
     extern __shared__ float lds[];
 
-    // XCD-aware placement (workgroups go to the 8 XCDs round-robin in linear order): each XCD takes a contiguous eighth of the
-    // (frame, tile) range, so tiles that share halo rows are processed behind the same L2
-    int bxi = blockIdx.x, n = blockIdx.z;
-    {
-        const unsigned tot = gridDim.x * gridDim.z;
-        if (gridDim.y == 1 && (tot & 7) == 0) {
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.z;
-            const unsigned l2_ = (lin & 7) * (tot >> 3) + (lin >> 3);
-            n = (int)(l2_ / gridDim.x);
-            bxi = (int)(l2_ - (unsigned)n * gridDim.x);
-        }
-    }
+    int bxi, n;
+    tile_frame_order(bxi, n);
     if (p.valid != nullptr && p.valid[n] == 0) return;
 
     const int FC = 1 << p.log2fc, FR = 32 >> p.log2fc;
@@ -99,48 +67,21 @@ __global__ __launch_bounds__((Cfg<K, S, SP>::NTHR)) void conv_igemm_kernel(ConvP
     const int rows = (tile_h - 1) * S + K, cols = (tile_w - 1) * S + K;
     const int plane = rows * cols;
     float* Xl = lds;                 // [2][ [CK][plane] | [NT][CK][COT] ]
-    const int xsz = (CK * plane + 3) & ~3;
-    float* Wl = lds + xsz;
-    const int BUF = xsz + NT * CK * COT;
+    float* Wl = lds + tile_x_floats(CK, plane);
+    const int BUF = tile_buf_floats(CK, plane, Stage::WFLOATS);
 
     const int tyi = bxi / p.tiles_x, txi = bxi % p.tiles_x;
     const int oy0 = tyi * tile_h, ox0 = txi * tile_w;
     const int co0 = blockIdx.y * COT;
     const int tid = threadIdx.x;
-    const int Cin = p.C0 + p.C1;
-    const int HWin = p.Hin * p.Win;
 
-    // ---- byte offsets (within a frame, relative to the chunk's first channel) of this thread's staging elements;
-    //      negative = zero padding / outside the tile.  Reflection is resolved here, once per tile.
-    int goff[MAXE];
-    const int total = CK * plane;
-#pragma unroll
-    for (int i = 0; i < MAXE; ++i) {
-        const int e = tid + i * NTHR;
-        int off = -1;
-        if (e < total) {
-            const int c = e / plane;
-            const int rem = e - c * plane;
-            const int r = rem / cols;
-            const int cc = rem - r * cols;
-            int gy = oy0 * S - p.pad_y + r;
-            int gx = ox0 * S - p.pad_x + cc;
-            bool ok;
-            if (p.pad_mode == C2S_PAD_REFLECT) {
-                ok = gy >= -p.pad_y && gy < p.Hin + p.pad_y && gx >= -p.pad_x && gx < p.Win + p.pad_x;
-                gy = reflect_idx(gy, p.Hin);
-                gx = reflect_idx(gx, p.Win);
-            } else {
-                ok = gy >= 0 && gy < p.Hin && gx >= 0 && gx < p.Win;
-            }
-            if (ok) off = (c * HWin + gy * p.Win + gx) * 4;
-        }
-        goff[i] = off;
-    }
+    Stage st;
+    st.init(tid, n, p.src0, p.src1, p.wpk, p.C0, p.C1, p.Hin, p.Win, p.CoutP, co0, plane, cols, oy0 * S - p.pad_y,
+            ox0 * S - p.pad_x, p.pad_y, p.pad_x, p.pad_mode);
 
-    const int lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lk = lane >> 5;
-    const int fy = li >> p.log2fc, fx = li & (FC - 1);
+    const int wave = tid >> 6;
+    const TileLane ln = tile_lane(tid, p.log2fc);
+    const int li = ln.li, lk = ln.lk, fy = ln.fy, fx = ln.fx;
     int boff[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -171,61 +112,15 @@ __global__ __launch_bounds__((Cfg<K, S, SP>::NTHR)) void conv_igemm_kernel(ConvP
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][q][r] = 0.f;
 
-    // Global -> register prefetch through buffer loads: out-of-range offsets (padding, channels beyond Cin, idle
-    // lanes) return 0 in hardware, so no select follows the load and the wait can sink to the LDS commit.
-    // A chunk never straddles the two concatenated sources (host checks C0 % CK == 0 when C1 > 0).
-    const float* s0n = p.src0 + (size_t)n * p.C0 * HWin;
-    const float* s1n = p.src1 != nullptr ? p.src1 + (size_t)n * p.C1 * HWin : nullptr;
-    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)s0n, 0, p.C0 * HWin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(s1n != nullptr ? s1n : s0n), 0,
-                                                                         p.C1 * HWin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.wpk, 0, NT * Cin * p.CoutP * 4, 0x00020000);
-
-    float xr[MAXE];
-    f32x4 wr[WPT];
-    auto prefetch = [&](int cb) {
-        const bool first = cb < p.C0;
-        const int chan0 = (first ? cb : cb - p.C0) * HWin * 4;
-        if (first) {
-#pragma unroll
-            for (int i = 0; i < MAXE; ++i)
-                xr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r0, goff[i] >= 0 ? goff[i] + chan0 : -1, 0, 0));
-        } else {
-#pragma unroll
-            for (int i = 0; i < MAXE; ++i)
-                xr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r1, goff[i] >= 0 ? goff[i] + chan0 : -1, 0, 0));
-        }
-#pragma unroll
-        for (int i = 0; i < WPT; ++i) {
-            const int e = tid + i * NTHR;
-            const int o4 = e % WV, tc = e / WV;
-            const int c = tc % CK, t = tc / CK;
-            const bool ok = e < NWV && cb + c < Cin;
-            const int off = ok ? (((t * Cin + cb + c) * p.CoutP + co0 + o4 * 4) * 4) : -1;
-            wr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, 0));
-        }
-    };
-    auto commit = [&](int buf) {
-        float* Xd = Xl + buf * BUF;
-        float* Wd = Wl + buf * BUF;
-#pragma unroll
-        for (int i = 0; i < MAXE; ++i) {
-            const int e = tid + i * NTHR;
-            if (e < total) Xd[e] = xr[i];
-        }
-#pragma unroll
-        for (int i = 0; i < WPT; ++i) {
-            const int e = tid + i * NTHR;
-            if (e < NWV) *reinterpret_cast<f32x4*>(Wd + (size_t)e * 4) = wr[i];
-        }
-    };
-
     // operands of k-step s = (tap t, channel pair cp)
-    auto load_ops = [&](const float* Xl, const float* Wl, int s_, float (&a)[MF], float (&b)[NQ]) {
+    struct Ops {
+        float a[MF], b[NQ];
+    };
+    auto load_ops = [&](const float* Xl, const float* Wl, int s_, Ops& o) {
         const int t = s_ / (CK / 2), cp = s_ % (CK / 2);
         const int ky = t / K, kx = t % K;
 #pragma unroll
-        for (int m = 0; m < MF; ++m) a[m] = Wl[(t * CK + 2 * cp) * COT + aoff + m * 32];
+        for (int m = 0; m < MF; ++m) o.a[m] = Wl[(t * CK + 2 * cp) * COT + aoff + m * 32];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int ad = boff[q] + 2 * cp * plane + ky * cols + kx;
@@ -248,127 +143,61 @@ __global__ __launch_bounds__((Cfg<K, S, SP>::NTHR)) void conv_igemm_kernel(ConvP
                     }
                 }
             }
-            b[q] = v;
+            o.b[q] = v;
         }
     };
+    tile_chunk_loop<NS, LA, NS / 2, Ops>(st, Xl, Wl, BUF, load_ops, [&](const Ops& o) {
+#pragma unroll
+        for (int m = 0; m < MF; ++m)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.a[m], o.b[q], acc[m][q], 0, 0, 0);
+    });
 
-    // K loop, LDS double-buffered: one barrier per chunk.  While chunk k is multiplied out of buffer k&1, the
-    // registers holding chunk k+1 (requested one chunk earlier) are committed to the other buffer and the request
-    // for chunk k+2 is issued, both in the middle of the MFMA sequence so that neither sits next to the barrier.
-    constexpr int COMMIT_AT = NS / 2;
-    prefetch(0);
-    commit(0);
-    if (CK < Cin) prefetch(CK);
-    __syncthreads();
-    int cur = 0;
-    for (int cb = 0; cb < Cin; cb += CK, cur ^= 1) {
-        const float* Xc = Xl + cur * BUF;
-        const float* Wc = Wl + cur * BUF;
-        float a[LA + 1][MF], b[LA + 1][NQ];
-#pragma unroll
-        for (int s_ = 0; s_ < LA; ++s_) load_ops(Xc, Wc, s_, a[s_], b[s_]);
-#pragma unroll
-        for (int s_ = 0; s_ < NS; ++s_) {
-            // operands LA k-steps ahead; the scheduling barriers keep hipcc from sinking the ds_reads below the
-            // MFMAs that hide them (it would then wait on them right away) or hoisting a whole chunk's reads
-            if (s_ + LA < NS) load_ops(Xc, Wc, s_ + LA, a[(s_ + LA) % (LA + 1)], b[(s_ + LA) % (LA + 1)]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < MF; ++m)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s_ % (LA + 1)][m], b[s_ % (LA + 1)][q], acc[m][q], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s_ == COMMIT_AT && cb + CK < Cin) {
-                commit(cur ^ 1);
-                if (cb + 2 * CK < Cin) prefetch(cb + 2 * CK);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue: row (channel) = (r&3) + 8*(r>>2) + 4*lk ; col (position) = li
+    // ---- epilogue: one float per channel at (oy*osy+ooy, ox*osx+oox)
     const size_t outHW = (size_t)p.OutH * p.OutW;
     float* on = p.out + (size_t)n * p.Cout * outHW;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
+    // (one call per fragment, not a loop over q: out of a loop hipcc hoists the sixteen 64-bit channel offsets, 32 VGPRs)
+    auto store = [&](int q) __attribute__((always_inline)) {
         const int f = NQ * wave + q;
         const int oy = oy0 + f * FR + fy, ox = ox0 + fx;
-        if (oy >= p.Hout || ox >= p.Wout) continue;
+        if (oy >= p.Hout || ox >= p.Wout) return;
         const size_t sp = (size_t)(oy * p.osy + p.ooy) * p.OutW + (ox * p.osx + p.oox);
-        // (accumulation: eight reads in flight, then their adds and stores -- read-add-store per element serialised 32 memory
-        // round trips, the compiler cannot move a read above the store before it)
-#pragma unroll
-        for (int m = 0; m < MF; ++m) {
-#pragma unroll
-            for (int r0 = 0; r0 < 16; r0 += 8) {
-                float old[8];
-                if (p.accumulate) {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int r = r0 + u;
-                        const int co = co0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                        old[u] = co < p.Cout ? on[(size_t)co * outHW + sp] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int r = r0 + u;
-                    const int co = co0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    if (co < p.Cout) {
-                        float v = acc[m][q][r];
-                        if (p.bias != nullptr) v += p.bias[co];
-                        if (p.accumulate) v += old[u];
-                        on[(size_t)co * outHW + sp] = v;
-                    }
-                }
-            }
-        }
-    }
+        tile_store<MF>(on, sp, outHW, co0, lk, p.Cout, p.bias, p.accumulate,
+                              [&](int m, int r) __attribute__((always_inline)) { return acc[m][q][r]; });
+    };
+    store(0);
+    if constexpr (NQ == 2) store(1);
 }
 
 template <int K, int S, int MF, bool ADJ, int SP = 1>
-int launch_conv(const ConvParams& p, int N, int tiles, hipStream_t st) {
+int launch_conv(const TileParams& p, int N, int tiles, hipStream_t st) {
     constexpr int CK = Cfg<K, S, SP>::CK;
     constexpr int NT = Cfg<K, S, SP>::NT;
-    const int FC = 1 << p.log2fc, FR = 32 >> p.log2fc;
-    const int rows = ((8 / SP) * FR - 1) * S + K, cols = (FC - 1) * S + K;
-    const size_t lds = 2 * ((((size_t)CK * rows * cols + 3) & ~(size_t)3) + (size_t)NT * CK * 32 * MF) * sizeof(float);
+    const size_t lds = tile_lds_bytes(CK, plane_for(K, S, p.log2fc, 8 / SP), NT * CK * 32 * MF);
     dim3 grid(tiles, p.CoutP / (32 * MF), N);
     hipLaunchKernelGGL((conv_igemm_kernel<K, S, MF, ADJ, SP>), grid, dim3(Cfg<K, S, SP>::NTHR), lds, st, p);
     C2S_CHECK_LAUNCH("conv_igemm");
     return C2S_OK;
 }
 
+// the (K, S, reflect adjoint) the kernel is built for: the dispatch and the LDS limits below
+#define C2S_IGEMM_KINDS(X) \
+    X(3, 1, false) X(3, 1, true) X(1, 1, false) X(2, 1, false) X(2, 1, true) X(4, 2, false) X(2, 2, false) X(6, 2, false)
+
 void init_hook() {
-#define C2S_RAISE4(K_, S_)                               \
-    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, false>)); \
-    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 2, false>));
-    C2S_RAISE4(3, 1) C2S_RAISE4(1, 1) C2S_RAISE4(2, 1) C2S_RAISE4(4, 2) C2S_RAISE4(2, 2) C2S_RAISE4(6, 2)
-#undef C2S_RAISE4
-    C2S_RAISE_LDS((conv_igemm_kernel<3, 1, 1, true>));
-    C2S_RAISE_LDS((conv_igemm_kernel<3, 1, 2, true>));
-    C2S_RAISE_LDS((conv_igemm_kernel<2, 1, 1, true>));
-    C2S_RAISE_LDS((conv_igemm_kernel<2, 1, 2, true>));
-#define C2S_RAISE_SP(K_, S_, A_)                              \
-    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, A_, 2>));     \
+#define C2S_RAISE(K_, S_, A_)                              \
+    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, A_>));     \
+    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 2, A_>));     \
+    C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, A_, 2>));  \
     C2S_RAISE_LDS((conv_igemm_kernel<K_, S_, 1, A_, 4>));
-    C2S_RAISE_SP(3, 1, false) C2S_RAISE_SP(3, 1, true) C2S_RAISE_SP(1, 1, false) C2S_RAISE_SP(2, 1, false)
-    C2S_RAISE_SP(2, 1, true) C2S_RAISE_SP(4, 2, false) C2S_RAISE_SP(2, 2, false) C2S_RAISE_SP(6, 2, false)
-#undef C2S_RAISE_SP
+    C2S_IGEMM_KINDS(C2S_RAISE)
+#undef C2S_RAISE
 }
 C2sInitRegistrar registrar(init_hook);
 
-// log2 of the fragment width and the workgroups of a launch at split sp (32-channel tiles)
-int frag_log2(const c2s_conv_desc* d) {
-    int l2 = 5;
-    while (l2 > 2 && (1 << l2) > d->Wout) --l2;
-    return l2;
-}
+// the workgroups of a launch at split sp (32-channel tiles)
 long split_wgs(const c2s_conv_desc* d, int sp) {
-    const int l2 = frag_log2(d);
-    return (long)cdiv(d->Wout, 1 << l2) * cdiv(d->Hout, (8 / sp) * (32 >> l2)) * d->N * (d->CoutP / 32);
+    return (long)tile_count(d->Hout, d->Wout, tile_log2fc(d->Wout), 8 / sp) * d->N * (d->CoutP / 32);
 }
 // C2S_IGEMM_SPLIT=1|2|4 forces the split (A/B runs, tests); anything else: the rule
 int forced_split() {
@@ -391,28 +220,19 @@ extern "C" int c2s_conv_igemm_split(const c2s_conv_desc* d, int cus) {
 
 extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const float* src1, const float* wpk,
                               const float* bias, float* out, const int* valid, void* stream) {
-    C2S_REQUIRE(d && src0 && wpk && out, "conv_igemm: null pointer");
+    if (const int rc = tile_check("conv_igemm", d, src0 && wpk && out)) return rc;
+    C2S_REQUIRE(d->Cout > 0, "conv_igemm: CoutP must be a multiple of 32");      // (the message this case has always had)
     C2S_REQUIRE(d->N > 0 && d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv_igemm: bad channels");
-    C2S_REQUIRE(d->CoutP % 32 == 0 && d->CoutP >= d->Cout && d->Cout > 0, "conv_igemm: CoutP must be a multiple of 32");
     C2S_REQUIRE(d->KH == d->KW, "conv_igemm: square kernels only");
-    C2S_REQUIRE(d->N <= C2S_CONV_MAX_FRAMES, "conv_igemm: more than 65535 frames in one launch (N = %d): the frame index is gridDim.z", d->N);
     C2S_REQUIRE(d->C1 == 0 || d->C0 % 16 == 0, "conv_igemm: with two sources C0 must be a multiple of 16");
-    C2S_REQUIRE((long)(d->C0 > d->C1 ? d->C0 : d->C1) * d->Hin * d->Win * 4 < (1L << 31), "conv_igemm: frame too large");
     C2S_REQUIRE((long)d->Hin * d->Win < (1 << 20), "conv_igemm: input plane too large");
     C2S_REQUIRE(d->Hout > 0 && d->Wout > 0, "conv_igemm: empty output");
     C2S_REQUIRE((d->Hout - 1) * d->osy + d->ooy < d->OutH && (d->Wout - 1) * d->osx + d->oox < d->OutW,
                 "conv_igemm: output placement exceeds the output plane");
     if (d->pad_mode == C2S_PAD_REFLECT)
         C2S_REQUIRE(d->pad_y < d->Hin && d->pad_x < d->Win, "conv_igemm: reflect padding needs pad < size");
-    ConvParams p;
-    p.src0 = src0; p.src1 = src1; p.wpk = wpk; p.bias = bias; p.out = out; p.valid = valid;
-    p.C0 = d->C0; p.C1 = d->C1; p.Hin = d->Hin; p.Win = d->Win; p.Cout = d->Cout; p.CoutP = d->CoutP;
-    p.Hout = d->Hout; p.Wout = d->Wout; p.OutH = d->OutH; p.OutW = d->OutW;
-    p.pad_y = d->pad_y; p.pad_x = d->pad_x; p.pad_mode = d->pad_mode;
-    p.osy = d->osy; p.osx = d->osx; p.ooy = d->ooy; p.oox = d->oox; p.accumulate = d->accumulate;
-    p.adj = d->reflect_adjoint;
-    p.ay_lo = p.ay_hi = p.ax_lo = p.ax_hi = -1;
-    p.dy_lo = p.dy_hi = p.dx_lo = p.dx_hi = d->KH - 1;
+    TileParams p;
+    tile_fill(p, d, src0, src1, wpk, bias, out, valid);
     if (d->reflect_adjoint == 2) {
         // parity sub-kernel (3x3, pad 1, output rows 2*a + parity) of the dgrad of conv6x6s2(reflect pad 2); per dimension
         // the input gradient of padded rows -1 / -2 / H / H+1 is the sub-kernel evaluated one row beyond either end:
@@ -445,33 +265,20 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
             if (d->pad_x == 0) p.ax_lo = 0; else p.ax_hi = d->Wout - 1;
         }
     }
-    const int l2 = frag_log2(d);
-    p.log2fc = l2;
-    const int FC = 1 << l2, FR = 32 >> l2;
-    p.tiles_x = cdiv(d->Wout, FC);
     hipStream_t st = (hipStream_t)stream;
-    // 64-channel tiles halve the LDS reads per MFMA, but on small planes (16x16 and below) they leave the grid short of
-    // two workgroups per CU: fall back to 32-channel tiles there
     const int cus = c2s_cus();
-    // launches that still leave CUs empty run on smaller tiles with one fragment per wave (c2s_conv_igemm_split)
+    // launches that leave CUs empty run on smaller tiles with one fragment per wave (c2s_conv_igemm_split)
     const int forced = forced_split();
     const int sp = forced ? forced : c2s_conv_igemm_split(d, cus);
-    const int tiles = p.tiles_x * cdiv(d->Hout, (8 / sp) * FR);
-    const bool wide = sp == 1 && d->CoutP % 64 == 0 && (long)tiles * d->N * (d->CoutP / 64) >= 2L * cus;
+    const int tiles = tile_count(d->Hout, d->Wout, p.log2fc, 8 / sp);
+    const bool wide = sp == 1 && tile_wide(d->CoutP, tiles, d->N, cus);
 #define C2S_DISPATCH(K_, S_, A_)                                                   \
     if (d->KH == K_ && d->S == S_ && (p.adj != 0) == A_) {                         \
         if (sp == 2) return launch_conv<K_, S_, 1, A_, 2>(p, d->N, tiles, st);     \
         if (sp == 4) return launch_conv<K_, S_, 1, A_, 4>(p, d->N, tiles, st);     \
         return wide ? launch_conv<K_, S_, 2, A_>(p, d->N, tiles, st) : launch_conv<K_, S_, 1, A_>(p, d->N, tiles, st); \
     }
-    C2S_DISPATCH(3, 1, false)
-    C2S_DISPATCH(3, 1, true)
-    C2S_DISPATCH(1, 1, false)
-    C2S_DISPATCH(2, 1, false)
-    C2S_DISPATCH(2, 1, true)
-    C2S_DISPATCH(4, 2, false)
-    C2S_DISPATCH(2, 2, false)
-    C2S_DISPATCH(6, 2, false)
+    C2S_IGEMM_KINDS(C2S_DISPATCH)
 #undef C2S_DISPATCH
     c2s_set_error("conv_igemm: unsupported (K=%d,S=%d)", d->KH, d->S);
     return C2S_EINVAL;

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
         for (int i = 0; i < D2_MAXE; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (C2S_AS3 void*)(Xd + i * 512), 4, goff[i], chan0, 0, 0);
     };
-    const int wg0 = (gridDim.x & 7) == 0 ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
+    const int wg0 = (int)C2S_XCD_ORDER(blockIdx.x, gridDim.x);
     int tile = next_valid(wg0);
     if (tile >= ntotal) return;
     int stile = tile, sk = 0;                          // next chunk to stage: chunk sk of tile stile (stile >= ntotal: none left)

@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(WgradParams p) 
 
     // XCD-aware start (see conv_winograd.hip): each XCD walks a contiguous eighth of the tiles in flight, so vertically
     // adjacent tiles (shared halo rows) meet in one L2; the slab index stays the workgroup index
-    int tile = next_tile((p.nslices & 7) == 0 ? (slice & 7) * (p.nslices >> 3) + (slice >> 3) : slice);
+    int tile = next_tile(C2S_XCD_ORDER(slice, p.nslices));
     if (tile < p.ntiles) prefetch(tile);
     while (tile < p.ntiles) {
         // the next tile's frame flag is fetched under the LDS commit and the barrier (read right after the barrier it stalled
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(256 * CB, CB == 1 ? 2 : 1) void conv_wgrad_winograd
 
     // XCD-aware start (see conv_winograd.hip): each XCD walks a contiguous eighth of the tiles in flight, so vertically
     // adjacent tiles (shared halo rows) meet in one L2; the slab index stays the workgroup index
-    int tile = next_tile((p.nslices & 7) == 0 ? (slice & 7) * (p.nslices >> 3) + (slice >> 3) : slice);
+    int tile = next_tile(C2S_XCD_ORDER(slice, p.nslices));
     if (tile < p.ntiles) prefetch(tile);
 #ifdef C2S_WW_STAMP
     unsigned long long st_commit = 0, st_loop = 0, st_tail = 0;
@@ -947,7 +947,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_s2wino_kernel(WgradParams p) {
         g[1] = *reinterpret_cast<const f32x2w*>(gbase + (2 * by + 1) * 32 + 2 * bx);
     };
 
-    int tile = next_tile((p.nslices & 7) == 0 ? (slice & 7) * (p.nslices >> 3) + (slice >> 3) : slice);
+    int tile = next_tile(C2S_XCD_ORDER(slice, p.nslices));
     if (tile < p.ntiles) prefetch(tile);
     while (tile < p.ntiles) {
         const int cand = tile + p.nslices;

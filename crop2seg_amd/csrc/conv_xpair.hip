@@ -14,10 +14,12 @@
 // Reference call sites replaced: nn.ConvTranspose2d(k=4,s=2,p=1) forward (src/backbones/conv.py:384-390) and the
 // convolution_backward-input of the 4x4 stride-2 down convolutions (conv.py:263-271), including the adjoint of
 // their reflection padding (conv.py:72-79).
-#include "common.h"
+#include "conv_tile.h"
 
 namespace {
 
+// The kernel keeps its own parameter block, staging, chunk loop and float2 epilogue (the design of conv_tile.h, written out):
+// its launches are latency-sized or epilogue-bound, and each shared piece cost them 1-3 % (profiles/conv_tile_refactor.txt 4).
 struct XpParams {
     const float* src;
     const float* wpk;      // [px 2][tap 4][Cin][CoutP]
@@ -47,18 +49,8 @@ __global__ __launch_bounds__(256) void conv_xpair_kernel(XpParams p) {
     constexpr int NS = 4 * (CK / 2);             // k-steps per chunk: (tap, channel pair)
     extern __shared__ float lds[];
 
-    // XCD-aware placement (workgroups go to the 8 XCDs round-robin in linear order): each XCD takes a contiguous eighth of the
-    // (frame, tile) range, so tiles that share halo rows are processed behind the same L2
-    int bxi = blockIdx.x, n = blockIdx.z;
-    {
-        const unsigned tot = gridDim.x * gridDim.z;
-        if (gridDim.y == 1 && (tot & 7) == 0) {
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.z;
-            const unsigned l2_ = (lin & 7) * (tot >> 3) + (lin >> 3);
-            n = (int)(l2_ / gridDim.x);
-            bxi = (int)(l2_ - (unsigned)n * gridDim.x);
-        }
-    }
+    int bxi, n;
+    tile_frame_order(bxi, n);
     if (p.valid != nullptr && p.valid[n] == 0) return;
 
     const int FC = 1 << p.log2fc, FR = 32 >> p.log2fc;
@@ -94,9 +86,9 @@ __global__ __launch_bounds__(256) void conv_xpair_kernel(XpParams p) {
         goff[i] = off;
     }
 
-    const int lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lk = lane >> 5;
-    const int fy = li >> p.log2fc, fx = li & (FC - 1);
+    const int wave = tid >> 6;
+    const TileLane ln = tile_lane(tid, p.log2fc);
+    const int li = ln.li, lk = ln.lk, fy = ln.fy, fx = ln.fx;
     const int oy = oy0 + wave * FR + fy, ox = ox0 + fx;
     const int boff = lk * plane + (wave * FR + fy) * cols + fx;
     const int aoff = lk * COT + li;
@@ -248,9 +240,7 @@ __global__ __launch_bounds__(256) void conv_xpair_kernel(XpParams p) {
 
 template <int MF, bool ADJ>
 int launch_xpair(const XpParams& p, int N, int tiles, hipStream_t st) {
-    const int FC = 1 << p.log2fc, FR = 32 >> p.log2fc;
-    const int plane = (4 * FR + 1) * (FC + 2);
-    const size_t lds = 2 * ((((size_t)XP_CK * plane + 3) & ~(size_t)3) + (size_t)2 * 4 * XP_CK * 32 * MF) * sizeof(float);
+    const size_t lds = tile_lds_bytes(XP_CK, xp_plane(p.log2fc), 2 * 4 * XP_CK * 32 * MF);
     dim3 grid(tiles, p.CoutP / (32 * MF), N);
     hipLaunchKernelGGL((conv_xpair_kernel<MF, ADJ>), grid, dim3(256), lds, st, p);
     C2S_CHECK_LAUNCH("conv_xpair");
@@ -261,36 +251,29 @@ int launch_xpair(const XpParams& p, int N, int tiles, hipStream_t st) {
 
 extern "C" int c2s_conv_xpair(const c2s_conv_desc* d, const float* src, const float* wpk, const float* bias, float* out,
                               const int* valid, void* stream) {
-    C2S_REQUIRE(d && src && wpk && out, "conv_xpair: null pointer");
+    if (const int rc = tile_check("conv_xpair", d, src && wpk && out)) return rc;
     C2S_REQUIRE(d->N > 0 && d->C0 > 0 && d->C1 == 0 && d->Cout > 0, "conv_xpair: bad channels (single source only)");
-    C2S_REQUIRE(d->CoutP % 32 == 0 && d->CoutP >= d->Cout, "conv_xpair: CoutP must be a multiple of 32");
-    C2S_REQUIRE(d->N <= C2S_CONV_MAX_FRAMES, "conv_xpair: more than 65535 frames in one launch (N = %d): the frame index is gridDim.z", d->N);
     C2S_REQUIRE(d->KH == 2 && d->KW == 2 && d->S == 1 && d->pad_mode == C2S_PAD_ZEROS, "conv_xpair: 2x2 zero-padded sub-kernels only");
     C2S_REQUIRE(d->pad_y == 0 || d->pad_y == 1, "conv_xpair: pad_y = 1 - py");
     C2S_REQUIRE(d->osy == 2 && d->osx == 2 && d->ooy == 1 - d->pad_y, "conv_xpair: output rows 2*i + py, columns 2*j + {0,1}");
     C2S_REQUIRE(d->Hout == d->Hin && d->Wout == d->Win && d->OutH == 2 * d->Hout && d->OutW == 2 * d->Wout,
                 "conv_xpair: output plane must be twice the input plane");
-    C2S_REQUIRE((long)d->C0 * d->Hin * d->Win * 4 < (1L << 31), "conv_xpair: frame too large");
     if (d->reflect_adjoint) C2S_REQUIRE(d->Hin >= 2 && d->Win >= 2, "conv_xpair: reflect_adjoint needs planes >= 2");
     XpParams p;
     p.src = src; p.wpk = wpk; p.bias = bias; p.out = out; p.valid = valid;
     p.Cin = d->C0; p.Hin = d->Hin; p.Win = d->Win; p.Cout = d->Cout; p.CoutP = d->CoutP;
     p.Hout = d->Hout; p.Wout = d->Wout; p.OutH = d->OutH; p.OutW = d->OutW;
     p.pad_y = d->pad_y; p.ooy = d->ooy; p.accumulate = d->accumulate;
+    p.log2fc = tile_log2fc(d->Wout);
+    p.tiles_x = cdiv(d->Wout, 1 << p.log2fc);
     p.ay_lo = p.ay_hi = -1;
     if (d->reflect_adjoint) {
         // parity 1 (pad 0): position 0 / tap 1 additionally reads input 0; parity 0 (pad 1): position H-1 / tap 0 reads H-1
         if (d->pad_y == 0) p.ay_lo = 0; else p.ay_hi = d->Hout - 1;
     }
-    int l2 = 5;
-    while (l2 > 2 && (1 << l2) > d->Wout) --l2;
-    p.log2fc = l2;
-    const int FC = 1 << l2, FR = 32 >> l2;
-    p.tiles_x = cdiv(d->Wout, FC);
-    const int tiles = p.tiles_x * cdiv(d->Hout, 4 * FR);
+    const int tiles = tile_count(d->Hout, d->Wout, p.log2fc, 4);
     hipStream_t st = (hipStream_t)stream;
-    const int cus = c2s_cus();
-    const bool wide = d->CoutP % 64 == 0 && (long)tiles * d->N * (d->CoutP / 64) >= 2L * cus;
+    const bool wide = tile_wide(d->CoutP, tiles, d->N, c2s_cus());
     if (d->reflect_adjoint)
         return wide ? launch_xpair<2, true>(p, d->N, tiles, st) : launch_xpair<1, true>(p, d->N, tiles, st);
     return wide ? launch_xpair<2, false>(p, d->N, tiles, st) : launch_xpair<1, false>(p, d->N, tiles, st);

@@ -68,13 +68,9 @@ __device__ __forceinline__ float keep_scale(const LtaeParams& p, int h, long P_t
     return drop_pick(d, drop_bits(d, (long)h * P_total + pidx, t >> 1), t);
 }
 
-
-// XCD-aware tile order: workgroups go to the 8 XCDs round-robin, so XCD k gets the k-th contiguous eighth of the tiles (tiles that
-// share 128-byte lines sit behind the same L2).  (Visiting the eighth with a stride, so that the tiles running at the same time
-// are spread over the [HW] rows instead of a 2 KB window, changed nothing: 1.36 vs 1.37 ms forward, 4.17 vs 4.20 ms backward.)
-__device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned grid) {
-    return (grid & 7) ? bid : (bid & 7) * (grid >> 3) + (bid >> 3);
-}
+// Tile order: C2S_XCD_ORDER (common.h), so that tiles that share 128-byte lines sit behind the same L2.  (Visiting an XCD's eighth
+// with a stride, so that the tiles running at the same time are spread over the [HW] rows instead of a 2 KB window, changed
+// nothing: 1.36 vs 1.37 ms forward, 4.17 vs 4.20 ms backward.)
 
 // ------------------------------------------------------------------------------------------ forward
 // Workgroup = 16 adjacent pixels.  Streaming phases use threads = (pixel quad q, slot) with float4 loads (4 pixels
@@ -335,7 +331,7 @@ __global__ __launch_bounds__(256) void ltae_lds_fwd_kernel(LtaeParams p) {
     float* ASl = red + 1024;                      // [16][4]      sum_t attention
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);      // the four tiles that share a 64-byte row segment: same L2
+    const unsigned tile = C2S_XCD_ORDER(blockIdx.x, gridDim.x);      // the four tiles that share a 64-byte row segment: same L2
     const int tiles_per_b = HW / 4;
     const int b = (int)(tile / tiles_per_b), pix0 = (int)(tile % tiles_per_b) * 4;
     const long Ptot = (long)p.B * HW;
@@ -871,7 +867,7 @@ __global__ __launch_bounds__(256) void ltae_lds_bwd_kernel(LtaeParams p, StreamB
     float* SUMl = red + 1024;                     // [2][16][4]   sum_t attn, sum_t gs
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
+    const unsigned tile = C2S_XCD_ORDER(blockIdx.x, gridDim.x);
     const int tiles_per_b = HW / 4;
     const int b = (int)(tile / tiles_per_b), pix0 = (int)(tile % tiles_per_b) * 4;
     const long Ptot = (long)p.B * HW;
@@ -1841,7 +1837,7 @@ __global__ __launch_bounds__(512) void ltae_reg_fwd_kernel(LtaeParams p) {
     // XCD-aware tile order: workgroups go to the 8 XCDs round-robin, so give each XCD a contiguous eighth of the tiles --
     // the two 16-pixel tiles that share every 128-byte line of x then sit behind the same L2.
     // (A persistent tile loop was tried: the loop-carried state pushed the kernel from 234 to 256 VGPRs + 65 spills, 1.39 -> 2.07 ms.)
-    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);
+    const unsigned tile = C2S_XCD_ORDER(blockIdx.x, gridDim.x);
     const int tiles_per_b = HW / RPX;
     const int b = (int)(tile / tiles_per_b);
     const int pix = (int)(tile % tiles_per_b) * RPX + px;
@@ -2706,7 +2702,7 @@ __global__ __launch_bounds__(512) void ltae_reg_bwd_heads_kernel(LtaeParams p, S
     const int T = p.T, HW = p.HW;
     const int tid = threadIdx.x, lane = tid & 63, px = lane & 15, q = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);                              // XCD-aware order (partials: by tile)
+    const unsigned tile = C2S_XCD_ORDER(blockIdx.x, gridDim.x);                              // XCD-aware order (partials: by tile)
     const int tiles_per_b = HW / RPX;
     const int b = (int)(tile / tiles_per_b);
     const int pix0 = (int)(tile % tiles_per_b) * RPX, pix = pix0 + px;
@@ -3210,7 +3206,7 @@ __global__ __launch_bounds__(1024) void ltae_stream_bwd_gx64_kernel(LtaeParams p
     const int T = p.T, HW = p.HW;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned tile = xcd_tile(blockIdx.x, gridDim.x);                              // XCD-aware order
+    const unsigned tile = C2S_XCD_ORDER(blockIdx.x, gridDim.x);                              // XCD-aware order
     const int tiles_per_b = HW / 64;
     const int b = (int)(tile / tiles_per_b);
     const int pix = (int)(tile % tiles_per_b) * 64 + lane;

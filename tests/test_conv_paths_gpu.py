@@ -198,6 +198,10 @@ ROWS = [
     # gy narrower than 32: implicit GEMM forward, transposed-row fallback of the data gradient (conv_xpair.hip)
     Row("xpair", 3, (64,), 64, 32, 32, 4, 2, "reflect", (0,), "igemm", ("xpair",), 2),
     Row("xpair-acc", 3, (64,), 64, 32, 32, 4, 2, "reflect", (1,), "igemm", ("xpair",), 2),
+    # the XCD-aware (frame, tile) order of conv_igemm / conv_xpair in effect: 8 frames of 16 x 16 and 32 output channels, so
+    # gridDim.y = 1 and the workgroups are a multiple of 8 at every split; the padded frames 1 and 3 return early after the remap
+    Row("igemm-8frames-acc", 8, (32,), 32, 16, 16, 3, 1, "reflect", (1,), "igemm", ("igemm",), 2),
+    Row("xpair-8frames-acc", 8, (32,), 32, 32, 32, 4, 2, "reflect", (1,), "igemm", ("xpair",), 2),
 ]
 
 
