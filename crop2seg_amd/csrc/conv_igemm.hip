@@ -36,10 +36,12 @@ constexpr int max_plane(int K, int S, int NF) {
     return cmax(cmax(plane_for(K, S, 2, NF), plane_for(K, S, 3, NF)), cmax(plane_for(K, S, 4, NF), plane_for(K, S, 5, NF)));
 }
 
+// channels per LDS chunk: enough MFMA k-steps per barrier pair (>= 16) without growing the prefetch registers
+constexpr int chunk_channels(int K) { return K == 1 ? 16 : (K == 2 ? 8 : (K >= 4 ? 2 : 4)); }
+
 template <int K, int S, int SP = 1>
 struct Cfg {
-    // channels per LDS chunk: enough MFMA k-steps per barrier pair (>= 16) without growing the prefetch registers
-    static constexpr int CK = K == 1 ? 16 : (K == 2 ? 8 : (K >= 4 ? 2 : 4));
+    static constexpr int CK = chunk_channels(K);
     static constexpr int NT = K * K;
     static constexpr int NTHR = SP == 4 ? 128 : 256;             // threads of a workgroup
     static constexpr int MAXE = (CK * max_plane(K, S, 8 / SP) + NTHR - 1) / NTHR;
@@ -224,7 +226,9 @@ extern "C" int c2s_conv_igemm(const c2s_conv_desc* d, const float* src0, const f
     C2S_REQUIRE(d->Cout > 0, "conv_igemm: CoutP must be a multiple of 32");      // (the message this case has always had)
     C2S_REQUIRE(d->N > 0 && d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv_igemm: bad channels");
     C2S_REQUIRE(d->KH == d->KW, "conv_igemm: square kernels only");
-    C2S_REQUIRE(d->C1 == 0 || d->C0 % 16 == 0, "conv_igemm: with two sources C0 must be a multiple of 16");
+    // (a chunk of the K loop never straddles the two sources: decoder widths such as 24 and 40 reach the 3x3 layers)
+    C2S_REQUIRE(d->C1 == 0 || d->C0 % chunk_channels(d->KH) == 0,
+                "conv_igemm: with two sources C0 must be a multiple of the channel chunk (16 for 1x1, 8 for 2x2, 4 for 3x3, 2 above)");
     C2S_REQUIRE((long)d->Hin * d->Win < (1 << 20), "conv_igemm: input plane too large");
     C2S_REQUIRE(d->Hout > 0 && d->Wout > 0, "conv_igemm: empty output");
     C2S_REQUIRE((d->Hout - 1) * d->osy + d->ooy < d->OutH && (d->Wout - 1) * d->osx + d->oox < d->OutW,

@@ -77,7 +77,7 @@ __device__ __forceinline__ int tile_pixel_offset(int gy, int gx, int Hin, int Wi
 
 // Global -> register -> LDS staging of one chunk: CK channels of a rows x cols input tile as [CK][plane], and the weight slab
 // [NSLAB][CK][COT] out of wpk[NSLAB][Cin][CoutP].  The channels are the concatenation of two sources (a chunk never straddles
-// them: the host checks C0 % 16 == 0 when C1 > 0, and CK divides 16).
+// them: the host checks C0 % CK == 0 when C1 > 0).
 // Buffer loads: out-of-range offsets (padding = -1, channels beyond Cin, idle lanes) return 0 in hardware, so no select
 // follows the load and the wait can sink to the LDS commit.
 template <int CK_, int MAXE, int NTHR, int NSLAB, int COT>

@@ -77,16 +77,16 @@ def checksum(sd: Dict[str, torch.Tensor]) -> torch.Tensor:
 
 
 def make_inputs(B: int, T: int, C: int, H: int, W: int, seed: int, lengths: Sequence[int] | None = None,
-                n_classes: int = 15) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                n_classes: int = 15, pad_value: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Synthetic batch in the shape pad_collate produces (reference src/utils.py:14-32):
-    x ~ N(0,1) f32 [B,T,C,H,W], dates = 5*t (+b) int64, frames t >= lengths[b] are exactly 0
-    in x and dates; y ~ U{0..n_classes-1} int64 [B,H,W]."""
+    x ~ N(0,1) f32 [B,T,C,H,W], dates = 5*t (+b) int64, frames t >= lengths[b] are exactly pad_value
+    in x and 0 in dates; y ~ U{0..n_classes-1} int64 [B,H,W]."""
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(B, T, C, H, W, generator=g)
     dates = (5 * torch.arange(T)[None, :] + torch.arange(B)[:, None]).to(torch.int64)
     if lengths is not None:
         for b, L in enumerate(lengths):
-            x[b, L:] = 0
+            x[b, L:] = pad_value
             dates[b, L:] = 0
     y = torch.randint(0, n_classes, (B, H, W), generator=g)
     return x, dates, y

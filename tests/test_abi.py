@@ -167,6 +167,19 @@ def test_offdefault_flags_fail_loudly():
         C2S.WTAE(input_dim=10, str_conv_k=3, str_conv_s=1, str_conv_p=1)
     with pytest.raises(NotImplementedError, match="multiple of 64"):
         C2S.UTAE(input_dim=10, encoder_widths=[64, 64, 64, 96], decoder_widths=[32, 32, 64, 96])
+    # skip maps whose width n_head = 16 does not divide into groups of 1, 2, 4, 8 or 16 channels (the reference's att_group
+    # raises on 40 and 72 in its first forward); W-TAE aggregates its first width only, TimeUNet_v1 none
+    with pytest.raises(NotImplementedError, match=r"temporal aggregation takes widths.*\[40, 72\]"):
+        C2S.UTAE(input_dim=10, encoder_widths=[32, 40, 72, 128], decoder_widths=[16, 24, 40, 128])
+    with pytest.raises(NotImplementedError, match=r"temporal aggregation takes widths.*\[40\]"):
+        C2S.WTAE(input_dim=10, encoder_widths=[40, 64, 64, 128], decoder_widths=[16, 24, 40, 128])
+    C2S.WTAE(input_dim=10, encoder_widths=[32, 40, 72, 128], decoder_widths=[16, 24, 40, 128])
+    # decoder widths: whole 4-channel chunks in front of the skip map (16 channels for the 1x1 of MBConv)
+    with pytest.raises(NotImplementedError, match=r"multiples of 4; got widths \[18\]"):
+        C2S.UTAE(input_dim=10, encoder_widths=[64, 64, 64, 128], decoder_widths=[32, 18, 64, 128])
+    with pytest.raises(NotImplementedError, match=r"multiples of 16 with use_mbconv; got widths \[24, 40\]"):
+        C2S.UTAE(input_dim=10, out_conv=[32, 20], use_mbconv=True, encoder_widths=[64, 64, 64, 128], decoder_widths=[16, 24, 40, 128])
+    C2S.TimeUNet_v1(input_dim=10, encoder_widths=[64, 32, 40, 72], decoder_widths=[16, 24, 40, 72])
     # use_abs_rel_enc together with use_doy / add_linear builds both encoders, as the reference does (tae.py:407-423)
     sd = C2S.UTAE(input_dim=10, use_abs_rel_enc=True, use_doy=True).state_dict()
     assert tuple(sd["temporal_encoder.positional_encoder.fc.weight"].shape) == (16, 365)

@@ -26,6 +26,8 @@ test_conv_paths_gpu.py are not copied.  Observed worst ratios:
 
     direct 4.94   f23 2.47   f22 3.23
 
+(the five zero-padded 3x3 rows added later: direct 3.51, f23 3.45)
+
 The tests can fail.  Three local builds of the library (not part of the project), each changing arithmetic only, one per
 loop; "existing" are the 165 convolution tests of test_conv_paths_gpu.py, test_conv_modes_gpu.py,
 test_strided_geometry_gpu.py and test_ops_gpu.py:

@@ -8,7 +8,8 @@ nslices is a multiple of 8, the XCD permutation (slice & 7) * (nslices / 8) + (s
 
 ROWS holds one row per kernel instantiation c2s_conv_wgrad can launch (fifteen (family, K) pairs in seven families), each on
 the smallest plane its plan (choose<K, S>) accepts, with enough frames that one slice walks six tiles or more and each of two
-slices three or more.  tile_grid() re-derives the tiling of each family from the same conditions.
+slices three or more; five more rows repeat the 64-channel 3x3 ones under zero padding (the F(2x3,3x3) kernels read a zero
+halo there).  tile_grid() re-derives the tiling of each family from the same conditions.
 """
 from typing import NamedTuple, Tuple
 
@@ -63,6 +64,13 @@ ROWS = [
     Row("generic-4x4s2-ragged", 3, (8,), 72, 24, 80, 4, 2, 1, "reflect", AUTO, 0),
     Row("generic-2x2s2", 6, (16,), 64, 16, 16, 2, 2, 0, "zeros", AUTO, 0),
     Row("generic-6x6s2", 3, (16,), 64, 24, 24, 6, 2, 2, "reflect", AUTO, 0),          # three tap groups
+    # zero-padded 3x3 with 64 channels: the F(2x3,3x3) kernels read a zero halo, the tile kernels mask instead of mirroring
+    # (new rows go at the end: make_inputs seeds a row by its index)
+    Row("f23-8wave-zeros", 6, (64,), 64, 8, 32, 3, 1, 1, "zeros", AUTO, 5),
+    Row("f23-4wave-two-sources-zeros", 6, (32, 64), 40, 8, 32, 3, 1, 1, "zeros", AUTO, 4),
+    Row("f23-8wave-interior-zeros", 4, (32, 32), 64, 12, 32, 3, 1, 1, "zeros", AUTO, 5),
+    Row("tile32-3x3-zeros-forced", 4, (64,), 64, 8, 32, 3, 1, 1, "zeros", DIRECT, 1),
+    Row("tile16-3x3-zeros", 6, (64,), 64, 8, 16, 3, 1, 1, "zeros", AUTO, 2),
 ]
 # the instantiations of the switch in c2s_conv_wgrad
 INSTANTIATIONS = {(0, 3), (0, 1), (0, 4), (0, 2), (0, 6), (1, 3), (1, 1), (1, 4), (2, 3), (2, 1), (2, 4), (3, 3), (4, 3),
