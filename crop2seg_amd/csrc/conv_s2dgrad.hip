@@ -21,7 +21,7 @@
 // Reference call site replaced: convolution_backward-input of nn.Conv2d(4, stride 2, padding 1, reflect) in DownConvBlock
 // (src/backbones/conv.py:263-271), for layers with a multiple of 8 (>= 24) output channels on planes at least 32 wide
 // (C2S_S2WINO=0 keeps conv_xpair_kernel).
-#include "common.h"
+#include "conv_ring.h"
 #include <stdlib.h>
 
 namespace {
@@ -41,27 +41,15 @@ struct S2dParams {
     int T, cpg_log2, a_bytes;      // a_bytes: ((n_head - 1) N + 1) 4 Ho Wo * 4, the bytes of a_up a frame's resource spans
 };
 
-constexpr int D2_UHALF = 4 * 128 * D2_UP;            // one k-step (4 gy channels x 128 virtual channels): 6,144 floats = 24 KB
-constexpr int D2_USLAB = 2 * D2_UHALF;               // a chunk of 8 gy channels: 48 KB
-constexpr int D2_URING = 5 * D2_UHALF;               // 120 KB
-constexpr int D2_RR = 9, D2_RC = 34;                 // raw gy tile: 9 rows x 34 columns per channel
-constexpr int D2_PLANE = D2_RR * D2_RC;              // 306
-constexpr int D2_XP = 352;                           // LDS pitch per channel (= 32 mod 64 banks)
-constexpr int D2_MAXE = 6;
-constexpr int D2_XS = D2_MAXE * 512;                 // 3,072 floats per raw slot
-constexpr int D2_XSLOTS = 3;
-constexpr int D2_LDS_FLOATS = D2_URING + D2_XSLOTS * D2_XS;      // 159,744 B (+ frame flag bits)
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// a k-step = 4 gy channels x 128 virtual channels: a half slab of 6,144 floats = 24 KB of U; a chunk of 8 gy channels: 48 KB, six
+// 16-byte pieces per thread; raw ring of three slots of the chunk's 8 channels (9 rows x 34 columns); no bias: 159,744 B (+ flags)
+using D2G = RingGeom<4 * 128 * D2_UP, 3, 8, 9, 34, 352, 0>;
 
 // a * b rounded on its own: what a kernel that stores the product and one that adds it to something must agree on
 __device__ __forceinline__ f32x4 rounded_product(f32x4 a, f32x4 b) {
 #pragma clang fp contract(off)
     return a * b;
 }
-#define C2S_AS1 __attribute__((address_space(1)))
-#define C2S_AS3 __attribute__((address_space(3)))
 #define C2S_AS4 __attribute__((address_space(4)))
 
 template <bool SKIP>
@@ -73,107 +61,60 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
     const int ch = w & 1, brow = w >> 1;            // input-channel half (32) and block row of this wave
     const int ey = blockIdx.y & 1, cblk = blockIdx.y >> 1;
     const int HWo = p.Ho * p.Wo, Hin = 2 * p.Ho, Win = 2 * p.Wo, HWin = Hin * Win;
-    const int ntotal = p.N * p.tiles;
     const int K = p.nchunks;
 
-    unsigned* lvalid = reinterpret_cast<unsigned*>(lds + D2_LDS_FLOATS);
-    for (int wi = tid; wi < (p.N + 31) / 32; wi += 512) {
-        unsigned m = 0;
-        for (int b = 0; b < 32; ++b) {
-            const int f = wi * 32 + b;
-            if (f < p.N && (p.valid == nullptr || p.valid[f] != 0)) m |= 1u << b;
-        }
-        lvalid[wi] = m;
-    }
+    const RingWalk walk = {reinterpret_cast<unsigned*>(lds + D2G::FLAGS), p.N * p.tiles, p.tiles, p.tiles_x};
+    ring_frame_flags(reinterpret_cast<unsigned*>(lds + D2G::FLAGS), p.valid, p.N, tid);
     __syncthreads();
-    auto next_valid = [&](int tt) {
-        while (tt < ntotal) {
-            const int f = tt / p.tiles;
-            if ((lvalid[f >> 5] >> (f & 31)) & 1u) break;
-            tt += gridDim.x;
-        }
-        return tt;
-    };
-    // tile (ty, tx): parity-plane rows 8 ty .. 8 ty + 7 (4 block rows), columns 32 tx .. 32 tx + 31 (16 block columns)
-    auto tile_origin = [&](int tt, int& n, int& m0, int& n0) {
-        n = tt / p.tiles;
-        const int ti = tt - n * p.tiles;
-        const int tyi = ti / p.tiles_x, txi = ti - tyi * p.tiles_x;
-        m0 = tyi * 8; n0 = txi * 32;
-    };
 
-    // ---- staging side: raw tile element (c, r, q) = gy[8 k + c][m0 - 1 + ey + r][n0 - 1 + q], zero outside the plane
-    int goff[D2_MAXE];
+    // ---- staging side.  Tile (ty, tx): parity-plane rows 8 ty .. 8 ty + 7 (4 block rows), columns 32 tx .. 32 tx + 31 (16 block
+    // columns); raw tile element (c, r, q) = gy[8 k + c][m0 - 1 + ey + r][n0 - 1 + q], zero outside the plane.  The gather table
+    // and the U requests are this kernel's own text: through ring_gather / ring_stage_u (conv_ring.h) it came out with more
+    // scratch and a spill inside the chunk loop (profiles/conv_ring_refactor.txt)
+    int goff[D2G::MAXE];
     __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, 0, 0x00020000);
     auto begin_staging = [&](int tt) {
         int n, m0, n0;
-        tile_origin(tt, n, m0, n0);
+        walk.origin<8, 32>(tt, n, m0, n0);
 #pragma unroll
-        for (int i = 0; i < D2_MAXE; ++i) {
+        for (int i = 0; i < D2G::MAXE; ++i) {
             const int e = tid + i * 512;
-            const int c = e / D2_XP, rem = e - c * D2_XP;
-            const int r = rem / D2_RC, q = rem - r * D2_RC;
+            const int c = e / D2G::XP, rem = e - c * D2G::XP;
+            const int r = rem / D2G::RC, q = rem - r * D2G::RC;
             const int gy = m0 - 1 + ey + r, gx = n0 - 1 + q;
-            const bool ok = rem < D2_PLANE && c < 8 && gy >= 0 && gy < p.Ho && gx >= 0 && gx < p.Wo;
-            goff[i] = ok ? ((c * HWo + gy * p.Wo + gx) * 4) : 0x7FFF0000;
+            const bool ok = rem < D2G::PLANE && c < 8 && gy >= 0 && gy < p.Ho && gx >= 0 && gx < p.Wo;
+            goff[i] = ok ? ((c * HWo + gy * p.Wo + gx) * 4) : RING_OOB;
         }
         r0 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.src + (size_t)n * p.Kc * HWo), 0, p.Kc * HWo * 4, 0x00020000);
     };
-    // one chunk's requests: U (48 KB: six 16-byte pieces per thread, three per half slab), then the raw tile
-    auto stage = [&](int k, int h0, int slot) {
+    auto stage_u = [&](int k, int h0) {                // U chunk k (48 KB): three pieces per half slab h0, h0 + 1 (mod 5)
         const int h1 = h0 == 4 ? 0 : h0 + 1;
-        const C2S_AS1 char* g = (const C2S_AS1 char*)p.upk + ((size_t)(ey * (p.CsP / 64) + cblk) * K + k) * (D2_USLAB * 4);
-        float* d0 = lds + h0 * D2_UHALF + w * 256;
-        float* d1 = lds + h1 * D2_UHALF + w * 256;
+        const C2S_AS1 char* g = (const C2S_AS1 char*)p.upk + ((size_t)(ey * (p.CsP / 64) + cblk) * K + k) * (D2G::USLAB * 4);
+        float* d0 = lds + h0 * D2G::UHALF + w * 256;
+        float* d1 = lds + h1 * D2G::UHALF + w * 256;
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             float* dst = (i < 3 ? d0 : d1) + (i % 3) * 2048;
             __builtin_amdgcn_global_load_lds((const C2S_AS1 void*)(g + i * 8192 + (unsigned)(tid * 16)), (C2S_AS3 void*)dst, 16, 0, 0);
         }
-        const int chan0 = 8 * k * HWo * 4;
-        float* Xd = lds + D2_URING + slot * D2_XS + w * 64;
-#pragma unroll
-        for (int i = 0; i < D2_MAXE; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (C2S_AS3 void*)(Xd + i * 512), 4, goff[i], chan0, 0, 0);
     };
-    const int wg0 = (int)C2S_XCD_ORDER(blockIdx.x, gridDim.x);
-    int tile = next_valid(wg0);
-    if (tile >= ntotal) return;
-    int stile = tile, sk = 0;                          // next chunk to stage: chunk sk of tile stile (stile >= ntotal: none left)
-    begin_staging(stile);
-    auto stage_next = [&](int h0, int slot) {          // (uniform across the workgroup)
-        if (stile >= ntotal) return;
-        stage(sk, h0, slot);
-        if (++sk == K) {                               // once per multiplied tile (K >= 3), at its chunk K - 3
-            sk = 0;
-            stile = next_valid(stile + gridDim.x);
-            if (stile < ntotal) begin_staging(stile);
-        }
-    };
+    auto stage_raw = [&](int k, int slot) { ring_stage_raw<D2G>(lds, r0, goff, 8 * k * HWo * 4, slot, w); };
+    int tile = walk.first();
+    if (tile >= walk.ntotal) return;
+    RingCursor<false> cur = {tile};                    // both operands two chunks ahead: one ring slot less than the forward kernels
+    begin_staging(tile);
+    auto request = [&](int h0, int slot) { cur.request(walk, K, h0, slot, begin_staging, stage_u, stage_raw); };
     int u0 = 0, rc = 0;                                // ring positions of the chunk being multiplied
-    stage_next(0, 0);
-    stage_next(2, 1);
+    request(0, 0);
+    request(2, 1);
 
     // LDS offsets of this lane's operands
     const int aoff = (kq * 128 + 32 * ch + t) * D2_UP;                          // in a half slab; + (ex * 64 + mt * 16) * UP
-    const int boff = D2_URING + kq * D2_XP + (2 * brow) * D2_RC + 2 * t;        // in a raw slot; + s * 4 * XP + r * RC
-    auto load_a = [&](const float* ab, int ex, int mt, float (&a)[12]) {
-#pragma unroll
-        for (int q4 = 0; q4 < 3; ++q4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(ab + (ex * 64 + mt * 16) * D2_UP + 4 * q4);
-            a[4 * q4] = v[0]; a[4 * q4 + 1] = v[1]; a[4 * q4 + 2] = v[2]; a[4 * q4 + 3] = v[3];
-        }
-    };
-    int boff0 = boff, boff1 = boff + 4 * D2_XP;
-    asm volatile("" : "+v"(boff0), "+v"(boff1));
-    auto load_d = [&](const float* bufp, int s, f32x2 (&dl)[3], f32x2 (&dh)[3]) {      // patch rows as (cols 0,1), (cols 2,3)
-        const float* bb = bufp + (s ? boff1 : boff0);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            dl[r] = *reinterpret_cast<const f32x2*>(bb + r * D2_RC);
-            dh[r] = *reinterpret_cast<const f32x2*>(bb + r * D2_RC + 2);
-        }
-    };
+    const int boff = D2G::URING + kq * D2G::XP + (2 * brow) * D2G::RC + 2 * t;  // in a raw slot; + s * 4 * XP + r * RC
+    auto load_a = [&](const float* ab, int ex, int mt, float (&a)[12]) { ring_load_a<3, 4>(ab + (ex * 64 + mt * 16) * D2_UP, a); };
+    int boff0 = boff, boff1 = boff + 4 * D2G::XP;      // (the two k-steps)
+    ring_opaque(boff0, boff1);
+    auto load_d = [&](const float* bufp, int s, f32x2 (&dl)[3], f32x2 (&dh)[3]) { ring_load_d<3, D2G::RC>(bufp + (s ? boff1 : boff0), dl, dh); };
     // fold state of the tile being multiplied: rows per wave (rt: 0 standard, 1 first output folds, 2 last output folds),
     // columns per lane (fl: column parity 1 of block column 0; fr: column parity 0 of the last block column)
     int rt = 0;
@@ -226,7 +167,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
     load_d(lds, 0, dl, dh);
     while (true) {
         int n, m0, n0;
-        tile_origin(tile, n, m0, n0);
+        walk.origin<8, 32>(tile, n, m0, n0);
         {
             const int gbr = (m0 >> 1) + brow, gbc = (n0 >> 1) + t;          // global block row / column
             const int lastr = (p.Ho >> 1) - 1, lastc = (p.Wo >> 1) - 1;
@@ -267,15 +208,14 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
             const int u1 = u0 == 4 ? 0 : u0 + 1, u2 = u1 == 4 ? 0 : u1 + 1;
             const int rn = rc == 2 ? 0 : rc + 1;
             // the first k-step's tail reads this chunk's second half slab and raw slot: landed a chunk ago
-            kstep(lds + u0 * D2_UHALF + aoff, lds + u1 * D2_UHALF + aoff, lds + rc * D2_XS, 1, first);
+            kstep(lds + u0 * D2G::UHALF + aoff, lds + u1 * D2G::UHALF + aoff, lds + rc * D2G::XS, 1, first);
             // everyone's requests for the NEXT chunk (issued one chunk ago) have landed; everyone has left the previous chunk's
             // raw slot and this chunk's first half slab
-            __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0)
-            __builtin_amdgcn_s_barrier();
+            ring_wait_landed<D2G>(cur.young_raw);                   // (never young: vmcnt(0))
             __builtin_amdgcn_sched_barrier(0);
-            stage_next(u0 == 0 ? 4 : u0 - 1, rc == 0 ? 2 : rc - 1);      // chunk after next: half slabs u0 + 4, u0 (mod 5); raw slot rc + 2 (mod 3)
+            request(u0 == 0 ? 4 : u0 - 1, rc == 0 ? 2 : rc - 1);         // chunk after next: half slabs u0 + 4, u0 (mod 5); raw slot rc + 2 (mod 3)
             // (after the last chunk of the last tile the tail reads are stale and unused)
-            kstep(lds + u1 * D2_UHALF + aoff, lds + u2 * D2_UHALF + aoff, lds + rn * D2_XS, 0, false);
+            kstep(lds + u1 * D2G::UHALF + aoff, lds + u2 * D2G::UHALF + aoff, lds + rn * D2G::XS, 0, false);
             u0 = u2;
             rc = rn;
         };
@@ -288,8 +228,8 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
         const __amdgpu_buffer_rsrc_t ro =
             __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)n * p.Cs * HWin), 0, p.Cs * HWin * 4, 0x00020000);
         const bool in0 = ncol < p.Wo && mrow < p.Ho, in1 = in0 && mrow + 1 < p.Ho;
-        const int vo0 = in0 ? (cof * HWin + (2 * mrow + ey) * Win + 2 * ncol) * 4 : 0x7FFF0000;
-        const int vo1 = in1 ? vo0 + 2 * Win * 4 : 0x7FFF0000;
+        const int vo0 = in0 ? (cof * HWin + (2 * mrow + ey) * Win + 2 * ncol) * 4 : RING_OOB;
+        const int vo1 = in1 ? vo0 + 2 * Win * 4 : RING_OOB;
         // SKIP: frame b = n / T of gskip has the layout of frame n of gx (same offsets); plane (head, n) of a_up
         __amdgpu_buffer_rsrc_t rg = ro, ra = ro;
         int cpg_log2 = 0;
@@ -341,7 +281,7 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {                           // per output row: three reads in flight
                         const int vo = i == 0 ? vo0 : vo1;
-                        const u32x4 au = __builtin_amdgcn_raw_buffer_load_b128(ra, vo == 0x7FFF0000 ? vo : vo + ho, 0, 0);
+                        const u32x4 au = __builtin_amdgcn_raw_buffer_load_b128(ra, vo == RING_OOB ? vo : vo + ho, 0, 0);
                         u32x4 o[2];
 #pragma unroll
                         for (int j = 0; j < 2; ++j) o[j] = __builtin_amdgcn_raw_buffer_load_b128(rg, i == 0 ? vo0 : vo1, so + j * HWin * 4, 0);
@@ -349,26 +289,12 @@ __global__ __launch_bounds__(512, 1) void conv_s2dgrad_kernel(S2dParams p) {
                         for (int j = 0; j < 2; ++j) v[j][i] += rounded_product(__builtin_bit_cast(f32x4, au), __builtin_bit_cast(f32x4, o[j]));
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                } else if (p.accumulate) {                                  // the four reads in flight before the first add
-                    u32x4 o[2][2];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) o[j][i] = __builtin_amdgcn_raw_buffer_load_b128(ro, i == 0 ? vo0 : vo1, so + j * HWin * 4, 0);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) v[j][i] += __builtin_bit_cast(f32x4, o[j][i]);
                 }
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[j][i]), ro, i == 0 ? vo0 : vo1, so + j * HWin * 4, 0);
+                ring_store_rows(ro, vo0, vo1, so, HWin * 4, SKIP ? 0 : p.accumulate, v);
             }
         }
-        if (stile >= ntotal) break;
-        tile = stile;
+        if (cur.stile >= walk.ntotal) break;
+        tile = cur.stile;
     }
 }
 
@@ -385,7 +311,7 @@ C2sInitRegistrar registrar(init_hook);
 extern "C" int c2s_conv4x4s2_dgrad_winograd_supported(const c2s_conv_desc* d) {
     return d && d->KH == 4 && d->KW == 4 && d->S == 2 && d->pad_y == 1 && d->pad_x == 1 && d->C1 == 0 && d->C0 % 8 == 0 &&
            d->C0 >= 24 && d->Hout == 2 * d->Hin && d->Wout == 2 * d->Win && d->Hin % 2 == 0 && d->Win % 2 == 0 &&
-           d->Win >= 32 && d->Hin >= 8 && d->CoutP % 64 == 0 && d->N <= 32768;
+           d->Win >= 32 && d->Hin >= 8 && d->CoutP % 64 == 0 && d->N <= ring_max_frames<D2G>();
 }
 
 namespace {
@@ -393,14 +319,9 @@ namespace {
 // a_up == NULL: gx (+)= the gradient; else gx = the gradient + round(a_up * gskip) (the descriptor's accumulate must be 0)
 int s2dgrad(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx, const int* valid, const float* a_up,
             const float* gskip, int T, int n_head, void* stream) {
-    C2S_REQUIRE(d && gy && upk && gx, "conv4x4s2_dgrad_winograd: null pointer");
+    if (int rc = ring_check("conv4x4s2_dgrad_winograd", d, gy && upk && gx, ring_max_frames<D2G>(), RING_OOB, true)) return rc;
     C2S_REQUIRE(c2s_conv4x4s2_dgrad_winograd_supported(d), "conv4x4s2_dgrad_winograd: data gradient of a 4x4 stride 2 pad 1 convolution, gy channels a multiple of 8 (>= 24), even gy planes at least 32 wide and 8 high, CoutP %% 64");
-    C2S_REQUIRE(d->N > 0 && d->N <= 32768 && d->Cout > 0 && d->CoutP >= d->Cout,
-                "conv4x4s2_dgrad_winograd: bad N / channels (at most 32768 frames: their flag bits share the last 4 KB of LDS)");
-    C2S_REQUIRE(d->OutH == d->Hout && d->OutW == d->Wout && d->osy == 1 && d->osx == 1 && d->ooy == 0 && d->oox == 0,
-                "conv4x4s2_dgrad_winograd: dense output only");
-    C2S_REQUIRE((long)d->C0 * d->Hin * d->Win * 4 < 0x7FFF0000L && (long)d->CoutP * d->Hout * d->Wout * 4 < 0x7FFF0000L,
-                "conv4x4s2_dgrad_winograd: frame too large");
+    C2S_REQUIRE(d->Cout > 0 && d->CoutP >= d->Cout, "conv4x4s2_dgrad_winograd: bad channels");
     S2dParams p;
     p.src = gy; p.upk = upk; p.out = gx; p.valid = valid;
     p.Kc = d->C0; p.Ho = d->Hin; p.Wo = d->Win; p.Cs = d->Cout; p.CsP = d->CoutP;
@@ -417,13 +338,8 @@ int s2dgrad(const c2s_conv_desc* d, const float* gy, const float* upk, float* gx
                     "(CoutP / (Cout / n_head) + 1) N Hout Wout floats below 2 GB");
         while ((d->Cout / n_head) >> (p.cpg_log2 + 1)) ++p.cpg_log2;
     }
-    const int cus = c2s_cus();
-    const int yblocks = 2 * (d->CoutP / 64);
-    const long ntotal = (long)d->N * p.tiles;
-    long gx_ = ((long)cus + yblocks - 1) / yblocks;  // persistent: one 8-wave workgroup per CU
-    if (gx_ > ntotal) gx_ = ntotal;
-    dim3 grid((unsigned)gx_, yblocks, 1);
-    const size_t ldsb = (size_t)(D2_LDS_FLOATS + (d->N + 31) / 32) * sizeof(float);
+    const dim3 grid = ring_grid(2 * (d->CoutP / 64), (long)d->N * p.tiles, 1);
+    const size_t ldsb = ring_lds_bytes<D2G>(d->N);
     if (a_up != nullptr) hipLaunchKernelGGL(conv_s2dgrad_kernel<true>, grid, dim3(512), ldsb, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(conv_s2dgrad_kernel<false>, grid, dim3(512), ldsb, (hipStream_t)stream, p);
     C2S_CHECK_LAUNCH("conv4x4s2_dgrad_winograd");

@@ -19,7 +19,8 @@
 //
 // Reference call sites replaced: nn.Conv2d 3x3 (src/backbones/conv.py:70-80,378-382) and its
 // convolution_backward-input, including reflection_pad2d_backward (conv.py:72-79).
-#include "common.h"
+#include "conv_ring.h"      // the host side and the padding rule; the ring itself is the 8-wave kernels'
+#include <limits.h>
 #include <stdlib.h>
 
 namespace {
@@ -37,8 +38,6 @@ struct WinoParams {
 };
 
 constexpr int WN_EXCH = 4 * 2 * 16 * 64;           // floats of the epilogue exchange [xi][x][row group][lane][4 rows] (one 32-channel half)
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef C2S_WN_STAMP
 // diagnostic build only: per-workgroup cycles spent in each phase, summed over the tiles the workgroup processed
@@ -68,9 +67,6 @@ __device__ unsigned long long wn_stamps[8192 * 8];
 // exchange and the stores instead of sitting in front of the next K loop.
 // Staging: the U chunk goes global -> LDS directly (global_load_lds_dwordx4: its LDS image [xn][c][o] is lane-linear),
 // which keeps 32 staging registers free next to the 128 accumulators; the gathered raw tile is register-staged.
-#define C2S_AS1 __attribute__((address_space(1)))
-#define C2S_AS3 __attribute__((address_space(3)))
-
 template <int LOG2BC, bool ADJ>
 __global__ __launch_bounds__(256, 2) void conv_winograd_kernel(WinoParams p) {
     constexpr int CK = WN_CK;
@@ -102,7 +98,6 @@ __global__ __launch_bounds__(256, 2) void conv_winograd_kernel(WinoParams p) {
     const int boffa = lk * plane + (2 * by + ra) * RC + 2 * bx;
     const int boffb = lk * plane + (2 * by + rb) * RC + 2 * bx;
     const int aoff = (xi * 4 * CK + lk) * 64 + li;
-    const bool reflect = p.pad_mode == C2S_PAD_REFLECT;
 
     // staging element of this thread packed as (channel << 20 | tile row << 10 | tile col); -1 = none
     int epk[MAXE];
@@ -132,16 +127,8 @@ __global__ __launch_bounds__(256, 2) void conv_winograd_kernel(WinoParams p) {
 #pragma unroll
         for (int i = 0; i < MAXE; ++i) {
             const int pk = epk[i];
-            int gy = oy0 - 1 + ((pk >> 10) & 1023), gx = ox0 - 1 + (pk & 1023);
-            bool ok = pk >= 0;
-            if (reflect) {
-                ok = ok && gy <= p.H && gx <= p.W;       // gy, gx >= -1 by construction
-                gy = reflect_idx(gy, p.H);
-                gx = reflect_idx(gx, p.W);
-            } else {
-                ok = ok && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-            }
-            goff[i] = ok ? (((pk >> 20) * HW + gy * p.W + gx) * 4) : -1;
+            const int px = tile_pixel_offset(oy0 - 1 + ((pk >> 10) & 1023), ox0 - 1 + (pk & 1023), p.H, p.W, 1, 1, p.pad_mode);
+            goff[i] = pk >= 0 && px >= 0 ? (((pk >> 20) * HW + px) * 4) : -1;
         }
         if constexpr (ADJ) {
             const int gby = (oy0 >> 1) + by, gbx = (ox0 >> 1) + bx;      // global block coordinates
@@ -403,15 +390,13 @@ extern "C" int c2s_debug_winograd_stamps(unsigned long long* host_out) {
 
 extern "C" int c2s_conv3x3_winograd(const c2s_conv_desc* d, const float* src0, const float* src1, const float* upk,
                                     const float* bias, float* out, const int* valid, void* stream) {
-    C2S_REQUIRE(d && src0 && upk && out, "conv3x3_winograd: null pointer");
-    C2S_REQUIRE(d->N > 0 && d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv3x3_winograd: bad channels");
+    if (int rc = ring_check("conv3x3_winograd", d, src0 && upk && out, INT_MAX, 1L << 31, false)) return rc;     // (the frame travels in gridDim.x)
+    C2S_REQUIRE(d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv3x3_winograd: bad channels");
     C2S_REQUIRE(d->KH == 3 && d->KW == 3 && d->S == 1 && d->pad_y == 1 && d->pad_x == 1, "conv3x3_winograd: 3x3 stride 1 pad 1 only");
-    C2S_REQUIRE(d->Hout == d->Hin && d->Wout == d->Win && d->OutH == d->Hout && d->OutW == d->Wout && d->osy == 1 &&
-                d->osx == 1 && d->ooy == 0 && d->oox == 0, "conv3x3_winograd: dense same-size output only");
+    C2S_REQUIRE(d->Hout == d->Hin && d->Wout == d->Win, "conv3x3_winograd: same-size output only");
     C2S_REQUIRE(d->Hin % 2 == 0 && d->Win % 4 == 0 && d->Hin >= 2 && d->Win >= 8, "conv3x3_winograd: even H, W a multiple of 4 and >= 8");
     C2S_REQUIRE(d->CoutP % 64 == 0 && d->CoutP >= d->Cout && d->Cout > 0, "conv3x3_winograd: CoutP must be a multiple of 64");
     C2S_REQUIRE(d->C1 == 0 || d->C0 % WN_CK == 0, "conv3x3_winograd: with two sources C0 must be a multiple of 8");
-    C2S_REQUIRE((long)(d->C0 > d->C1 ? d->C0 : d->C1) * d->Hin * d->Win * 4 < (1L << 31), "conv3x3_winograd: frame too large");
     if (d->reflect_adjoint) C2S_REQUIRE(d->pad_mode == C2S_PAD_ZEROS, "conv3x3_winograd: the reflect adjoint is a zero-padded launch");
     WinoParams p;
     p.src0 = src0; p.src1 = src1; p.upk = upk; p.bias = bias; p.out = out; p.valid = valid;
@@ -427,17 +412,12 @@ extern "C" int c2s_conv3x3_winograd(const c2s_conv_desc* d, const float* src0, c
     const int plane = (2 * BR + 2) * (2 * BC + 2);
     size_t fl = 2 * ((size_t)WN_CK * plane + WN_USLAB);
     if (fl < (size_t)WN_EXCH) fl = WN_EXCH;
-    const int cus = c2s_cus();
     // persistent workgroups: two per CU (register / LDS limit), split over the output-channel blocks
-    const int cblocks = d->CoutP / 64;
-    const long ntotal = (long)d->N * p.tiles;
     int wpc = 2;
 #ifdef C2S_WN_STAMP
     if (const char* e = getenv("C2S_WN_WGS_PER_CU")) wpc = atoi(e);     // diagnostic build: solo-workgroup timing
 #endif
-    long gx = ((long)wpc * cus + cblocks - 1) / cblocks;
-    if (gx > ntotal) gx = ntotal;
-    dim3 grid((unsigned)gx, cblocks, 1);
+    const dim3 grid = ring_grid(d->CoutP / 64, (long)d->N * p.tiles, wpc);
     hipStream_t st = (hipStream_t)stream;
     const size_t ldsb = fl * sizeof(float);
 #define C2S_WN_LAUNCH(L2_)                                                                                          \

@@ -29,7 +29,7 @@
 // Reference call sites replaced: as conv_winograd.hip (nn.Conv2d 3x3: src/backbones/conv.py:70-80,378-382 and its
 // convolution_backward-input incl. reflection_pad2d_backward).  Planes at least 32 pixels wide; narrower ones stay with the
 // 4-wave kernel.
-#include "common.h"
+#include "conv_ring.h"
 #include <stdlib.h>
 
 namespace {
@@ -53,26 +53,17 @@ struct Wino16Params {
     int N, tiles, tiles_x, nchunks;
 };
 
-constexpr int W16_USLAB = W16_CK * 64 * W16_UP;     // 8,192 floats = 32 KB per chunk
-constexpr int W16_UHALF = W16_USLAB / 2;            // a k-step's half slab (4 channels): 16 KB; ring of five
-constexpr int W16_URING = 5 * W16_UHALF;            // 80 KB
-constexpr int W16_XSLOTS = 4;                       // raw-tile ring
-constexpr int W16_WPT = W16_USLAB / 4 / 512;        // 4 LDS-DMA pieces per thread: two per half slab
-// tile of BR x BC blocks of 2 x 2 output pixels (BR * BC = 64: one block row of 16 blocks per wave and channel half)
+// tile of BR x BC blocks of 2 x 2 output pixels (BR * BC = 64: one block row of 16 blocks per wave and channel half).  A k-step = 4
+// channels: a half slab of 4,096 floats = 16 KB of U; a chunk of 8: 32 KB, four 16-byte pieces per thread; raw ring of four slots
+// of the chunk's 8 channels; the bias of the 64 channels
 template <int BR, int BC>
 struct W16Shape {
     static_assert(BR * BC == 64 && BC % 16 == 0, "eight waves: 2 channel halves x BR block rows x BC / 16 column groups");
     static constexpr int RR = 2 * BR + 2, RC = 2 * BC + 2;          // raw tile: 10 x 34 (4 x 16 blocks), 6 x 66 (2 x 32)
-    static constexpr int PLANE = RR * RC;                           // 340 / 396
-    static constexpr int XP = (PLANE + 31) / 64 * 64 + 32;          // LDS pitch per channel >= PLANE, = 32 mod 64 banks (the four
-                                                                    // k groups of a wave do not collide): 352 / 416
-    static constexpr int MAXE = (W16_CK * XP + 511) / 512;          // raw-tile LDS-DMA pieces per thread (one float each): 6 / 7
-    static constexpr int XS = MAXE * 512;                           // floats per raw slot (8 x XP and a zero-filled tail)
-    static constexpr int LDS_FLOATS = W16_URING + W16_XSLOTS * XS + 64;     // + the bias of the 64 channels: 131,328 / 139,520 B
-};                                                                          // (+ frame flag bits)
+    static constexpr int XP = (RR * RC + 31) / 64 * 64 + 32;        // LDS pitch per channel >= the plane (340 / 396): 352 / 416
+    using G = RingGeom<W16_CK / 2 * 64 * W16_UP, 4, W16_CK, RR, RC, XP, 64>;      // MAXE 6 / 7: 131,328 / 139,520 B (+ frame flag bits)
+};
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // tools/wino16_diag.py builds diagnostic copies with one part of the kernel removed (results are then wrong by design):
 //   1 = no MFMA, 2 = no staging after the first two chunks, 3 = no output stores, 4 = no LDS operand reads in the K loop,
 //   5 = 2 and 4 together (MFMA + transform + epilogue only), 6 = 5 without the barrier per chunk, 7 = 5 without the transforms,
@@ -83,8 +74,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define C2S_W16_DIAG 0
 #endif
 #define C2S_W16_BARE (C2S_W16_DIAG == 11 || C2S_W16_DIAG == 12)       // 7-like: nothing but MFMAs in the K loop
-#define C2S_AS1 __attribute__((address_space(1)))
-#define C2S_AS3 __attribute__((address_space(3)))
 
 // a - b - c on channel pairs as two v_pk_add_f32 with negated second operands (the compiler leaves vector subtractions
 // scalar).  Only used after the s_nop block that follows the K loop: asm operands are invisible to the MFMA -> VALU hazard
@@ -98,9 +87,7 @@ __device__ __forceinline__ f32x2 sub2(f32x2 a, f32x2 b, f32x2 c) {
 
 template <bool ADJ, int BR, int BC>
 __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p) {
-    using SH = W16Shape<BR, BC>;
-    constexpr int W16_RC = SH::RC, W16_PLANE = SH::PLANE, W16_XP = SH::XP, W16_MAXE = SH::MAXE, W16_XS = SH::XS;
-    constexpr int W16_BR = BR, W16_BC = BC;
+    using G = typename W16Shape<BR, BC>::G;
     extern __shared__ float lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);    // (scalar: row masks and bases in SGPRs)
@@ -109,155 +96,90 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
                                                                                   // column of this wave
     const int co0 = blockIdx.y * 64;
     const int HW = p.H * p.W;
-    const bool reflect = p.pad_mode == C2S_PAD_REFLECT;
-    const int ntotal = p.N * p.tiles;
     const int K = p.nchunks;
 
-    // frame flags as a bit mask in LDS (behind the rings and the bias): the tile walk must not touch the vector-memory
-    // counter, which orders the LDS-DMA requests in flight
-    unsigned* lvalid = reinterpret_cast<unsigned*>(lds + W16_URING + W16_XSLOTS * W16_XS + 64);
-    for (int wi = tid; wi < (p.N + 31) / 32; wi += 512) {
-        unsigned m = 0;
-        for (int b = 0; b < 32; ++b) {
-            const int f = wi * 32 + b;
-            if (f < p.N && (p.valid == nullptr || p.valid[f] != 0)) m |= 1u << b;
-        }
-        lvalid[wi] = m;
-    }
+    const RingWalk walk = {reinterpret_cast<unsigned*>(lds + G::FLAGS), p.N * p.tiles, p.tiles, p.tiles_x};
+    ring_frame_flags(reinterpret_cast<unsigned*>(lds + G::FLAGS), p.valid, p.N, tid);
     __syncthreads();
 #ifdef C2S_W16_STAMP
     unsigned long long st_wait = 0, st_epi = 0, st_chunks = 0, st_first = 0;
     const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
 #endif
-    auto next_valid = [&](int tt) {
-        while (tt < ntotal) {
-            const int f = tt / p.tiles;
-            if ((lvalid[f >> 5] >> (f & 31)) & 1u) break;
-            tt += gridDim.x;
-        }
-        return tt;
-    };
-    auto tile_origin = [&](int tt, int& n, int& oy0, int& ox0) {
-        n = tt / p.tiles;
-        const int ti = tt - n * p.tiles;
-        const int tyi = ti / p.tiles_x, txi = ti - tyi * p.tiles_x;
-        oy0 = tyi * 2 * W16_BR; ox0 = txi * 2 * W16_BC;
-    };
 
-    // ---- the staging side runs two chunks ahead of the MFMAs, across tile boundaries: its own tile state
-    int goff[W16_MAXE];
+    // ---- the staging side runs ahead of the MFMAs, across tile boundaries: its own tile state.  Raw tile element (c, r, q) is
+    // input pixel (oy0 - 1 + r, ox0 - 1 + q) of the chunk's channel c
+    int goff[G::MAXE];
     int diag_staged = 0;
     __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.src0, 0, 0, 0x00020000), r1 = r0;
     auto begin_staging = [&](int tt) {
         int n, oy0, ox0;
-        tile_origin(tt, n, oy0, ox0);
+        walk.origin<2 * BR, 2 * BC>(tt, n, oy0, ox0);
         if (C2S_W16_DIAG == 10) n = 0;
         if (C2S_W16_DIAG >= 100) n %= (C2S_W16_DIAG - 100);       // 100 + F: raw tiles from the first F frames only
+        // (this kernel's own table: through ring_gather its forward launches ran 1.0-1.7 % slower: profiles/conv_ring_refactor.txt)
+        const bool reflect = p.pad_mode == C2S_PAD_REFLECT;
 #pragma unroll
-        for (int i = 0; i < W16_MAXE; ++i) {              // LDS float e = tid + 512 i of the raw tile: (channel, row, col)
+        for (int i = 0; i < G::MAXE; ++i) {              // LDS float e = tid + 512 i of the raw tile: (channel, row, col)
             const int e = tid + i * 512;
-            const int c = e / W16_XP, rem = e - c * W16_XP;
-            int gy = oy0 - 1 + rem / W16_RC, gx = ox0 - 1 + rem % W16_RC;
+            const int c = e / G::XP, rem = e - c * G::XP;
+            int gy = oy0 - 1 + rem / G::RC, gx = ox0 - 1 + rem % G::RC;
             if (C2S_W16_DIAG == 13) gx += 1;
-            if (C2S_W16_DIAG == 14) gx = ox0 + (rem % W16_RC < 32 ? rem % W16_RC : 31);
+            if (C2S_W16_DIAG == 14) gx = ox0 + (rem % G::RC < 32 ? rem % G::RC : 31);
             if (C2S_W16_DIAG == 15 && gx < ox0) gx = ox0;                                  // no left halo column
-            if (C2S_W16_DIAG == 16 && gx >= ox0 + 2 * W16_BC) gx = ox0 + 2 * W16_BC - 1;     // no right halo column
-            if (C2S_W16_DIAG == 17) { if (gx < ox0) gx = ox0; if (gx >= ox0 + 2 * W16_BC) gx = ox0 + 2 * W16_BC - 1; }     // neither
-            const bool ok = rem < W16_PLANE && c < W16_CK &&
+            if (C2S_W16_DIAG == 16 && gx >= ox0 + 2 * BC) gx = ox0 + 2 * BC - 1;             // no right halo column
+            if (C2S_W16_DIAG == 17) { if (gx < ox0) gx = ox0; if (gx >= ox0 + 2 * BC) gx = ox0 + 2 * BC - 1; }     // neither
+            const bool ok = rem < G::PLANE && c < W16_CK &&
                             (reflect ? (gy <= p.H && gx <= p.W) : (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W));
             gy = reflect_idx(gy, p.H);                    // (identity inside the plane)
             gx = reflect_idx(gx, p.W);
-            goff[i] = ok ? ((c * HW + gy * p.W + gx) * 4) : 0x7FFF0000;     // (out of range whatever the channel offset)
+            goff[i] = ok ? ((c * HW + gy * p.W + gx) * 4) : RING_OOB;
         }
         const float* s0n = p.src0 + (size_t)n * p.C0 * HW;
         const float* s1n = p.src1 != nullptr ? p.src1 + (size_t)n * p.C1 * HW : nullptr;
         r0 = __builtin_amdgcn_make_buffer_rsrc((void*)s0n, 0, p.C0 * HW * 4, 0x00020000);
         r1 = __builtin_amdgcn_make_buffer_rsrc((void*)(s1n != nullptr ? s1n : s0n), 0, p.C1 * HW * 4, 0x00020000);
     };
-    // both operands by LDS-DMA.  U: 32 KB per chunk, packed lane-linear.  Raw tile: one float per lane and piece, lane-linear in
-    // LDS, gathered (reflected) global addresses; out-of-range offsets (-1: zero padding, tile overhang, the tail) read as 0
-    // U chunk k -> half slabs h0 and h0 + 1 (mod 5) of the ring; the 32 KB are contiguous in global memory, two pieces per half
-    // (addresses of the requests: LDS destinations and channel offsets are wave-uniform and stay in scalar registers -- a
-    // VALU instruction costs the SIMD ~8 cycles of MFMA issue, see the header)
+    // Requests (ring_stage_u / ring_stage_raw: the raw tile comes from HBM and is requested THREE chunks ahead of the MFMAs --
+    // tools/wino16_diag.py: with two, ~130 us of the 64->64 @128^2 launch were waits for it -- U (L2 hits) two ahead).
+    // Diagnostic builds 2, 5-7, 11, 12: nothing is staged after the first two chunks; 8 / 9 stop ONE stream (round 4: they had
+    // fallen under the same switch since round 3 and measured 'no staging' three times over -- likewise 10)
+    constexpr bool diag_stage = C2S_W16_DIAG != 2 && (C2S_W16_DIAG < 5 || (C2S_W16_DIAG >= 8 && C2S_W16_DIAG <= 10) || C2S_W16_DIAG >= 100);
     auto stage_u = [&](int k, int h0) {
-        if (C2S_W16_DIAG == 9 && diag_staged >= 2) return;
-        const int h1 = h0 == 4 ? 0 : h0 + 1;
-        const C2S_AS1 char* g = (const C2S_AS1 char*)p.upk + ((size_t)blockIdx.y * K + k) * (W16_USLAB * 4);
-        float* d0 = lds + h0 * W16_UHALF + w * 256;
-        float* d1 = lds + h1 * W16_UHALF + w * 256;
-#pragma unroll
-        for (int i = 0; i < W16_WPT; ++i)
-            __builtin_amdgcn_global_load_lds((const C2S_AS1 void*)(g + i * 8192 + (unsigned)(tid * 16)),
-                                             (C2S_AS3 void*)((i < 2 ? d0 : d1) + (i & 1) * 2048), 16, 0, 0);
+        if ((C2S_W16_DIAG == 9 || !diag_stage) && diag_staged >= 2) return;
+        ring_stage_u<G>(lds, (const C2S_AS1 char*)p.upk + ((size_t)blockIdx.y * K + k) * (G::USLAB * 4), h0, w, tid);
     };
     auto stage_raw = [&](int k, int slot) {
-        if (C2S_W16_DIAG == 8 && diag_staged >= 2) return;
+        const bool staged = !((C2S_W16_DIAG == 8 || !diag_stage) && diag_staged >= 2);
+        ++diag_staged;
+        if (!staged) return;
         const int cb_ = k * W16_CK;
         const bool first = cb_ < p.C0;
         const int chan0 = (first ? cb_ : cb_ - p.C0) * HW * 4;            // scalar offset of the request
-        float* Xd = lds + W16_URING + slot * W16_XS + w * 64;
-#pragma unroll
-        for (int i = 0; i < W16_MAXE; ++i) {
-            if (first) __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (C2S_AS3 void*)(Xd + i * 512), 4, goff[i], chan0, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (C2S_AS3 void*)(Xd + i * 512), 4, goff[i], chan0, 0, 0);
-        }
+        if (first) ring_stage_raw<G>(lds, r0, goff, chan0, slot, w);
+        else ring_stage_raw<G>(lds, r1, goff, chan0, slot, w);
     };
-    // XCD-aware start (as conv_winograd.hip): each XCD walks a contiguous eighth of the tiles in flight
-    const int wg0 = (int)C2S_XCD_ORDER(blockIdx.x, gridDim.x);
-    int tile = next_valid(wg0);
-    if (tile >= ntotal) return;
-    int stile = tile, sk = 0;                          // next chunk to stage: chunk sk of tile stile (stile >= ntotal: none left)
-    begin_staging(stile);
-    // Requests (uniform across the workgroup).  The raw tile comes from HBM and is requested THREE chunks ahead of the MFMAs
-    // (tools/wino16_diag.py: with two, ~130 us of the 64->64 @128^2 launch were waits for it), U (L2 hits) two ahead.  The U
-    // chunk to request next is the one the raw side requested a step earlier: (u_ok, u_k).
-    // 2, 5-7, 11, 12: nothing is staged after the first two chunks; 8 / 9 stop ONE stream (round 4: they had fallen under the
-    // same switch since round 3 and measured 'no staging' three times over -- likewise 10)
-    const bool diag_stage = C2S_W16_DIAG != 2 && (C2S_W16_DIAG < 5 || (C2S_W16_DIAG >= 8 && C2S_W16_DIAG <= 10) || C2S_W16_DIAG >= 100);
-    bool u_ok = false, young_raw = false;
-    int u_k = 0;
-    auto stage_next_u = [&](int h0) {
-        if (u_ok && (diag_stage || diag_staged < 2)) stage_u(u_k, h0);
-    };
-    auto stage_next_raw = [&](int slot) {
-        u_ok = stile < ntotal;
-        u_k = sk;
-        young_raw = u_ok;
-        if (!u_ok) return;
-        if (diag_stage || diag_staged < 2) stage_raw(sk, slot);
-        ++diag_staged;
-        if (++sk == K) {                               // once per multiplied tile (K >= 4), at its chunk K - 4
-            sk = 0;
-            stile = next_valid(stile + gridDim.x);
-            if (stile < ntotal) begin_staging(stile);
-        }
-    };
+    int tile = walk.first();
+    if (tile >= walk.ntotal) return;
+    RingCursor<true> cur = {tile};
+    begin_staging(tile);
+    auto request = [&](int h0, int slot) { cur.request(walk, K, h0, slot, begin_staging, stage_u, stage_raw); };
     int u0 = 0, rc = 0;                                // ring positions of the chunk being multiplied: U half slab of k-step 0, raw slot
-    stage_next_raw(0); stage_next_u(0);
-    stage_next_raw(1); stage_next_u(2);
-    stage_next_raw(2);
+    request(0, 0);
+    request(0, 1);
+    request(2, 2);
 
     // LDS offsets of this lane's operands inside a buffer
     const int aoff = kq * (4 * 64 * 4) + (32 * ch + t) * 4;                     // in a half slab [c 4][xi 4][o 64][nu 4]; + mt * 64 + xi * 256
-    const int boff = W16_URING + kq * W16_XP + (2 * brow) * W16_RC + 2 * (bcol0 + t);     // in a raw slot; + s * 4 * XP + r * RC
+    const int boff = G::URING + kq * G::XP + (2 * brow) * G::RC + 2 * (bcol0 + t);        // in a raw slot; + s * 4 * XP + r * RC
     auto load_a = [&](const float* ab, int mt, float (&a)[16]) {                 // ab: this lane's row of a half slab
         if (((C2S_W16_DIAG >= 4 && C2S_W16_DIAG <= 7) || C2S_W16_BARE) && ab != lds + aoff) return;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(ab + mt * 64 + q4 * 256);       // (16 lanes: 256 contiguous bytes)
-            a[4 * q4] = v[0]; a[4 * q4 + 1] = v[1]; a[4 * q4 + 2] = v[2]; a[4 * q4 + 3] = v[3];
-        }
+        ring_load_a<4, 256>(ab + mt * 64, a);          // one read per row xi (16 lanes: 256 contiguous bytes)
     };
-    int boff0 = boff, boff1 = boff + 4 * W16_XP;       // (the two k-steps; opaque, so that the row offsets stay ds_read2 immediates)
-    asm volatile("" : "+v"(boff0), "+v"(boff1));
+    int boff0 = boff, boff1 = boff + 4 * G::XP;        // (the two k-steps)
+    ring_opaque(boff0, boff1);
     auto load_d = [&](const float* bufp, int s, f32x2 (&dl)[4], f32x2 (&dh)[4]) {     // patch rows as (cols 0,1), (cols 2,3)
         if (((C2S_W16_DIAG >= 4 && C2S_W16_DIAG <= 7) || C2S_W16_BARE) && bufp != lds) return;
-        const float* bb = bufp + (s ? boff1 : boff0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            dl[r] = *reinterpret_cast<const f32x2*>(bb + r * W16_RC);
-            dh[r] = *reinterpret_cast<const f32x2*>(bb + r * W16_RC + 2);
-        }
+        ring_load_d<4, G::RC>(bufp + (s ? boff1 : boff0), dl, dh);
     };
     // adjoint folds of this wave's block row (scalar) and of this lane's block column
     float mtop = 0.f, mbot = 0.f;
@@ -313,7 +235,7 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
         }
     };
     f32x4 acc[16][2];
-    float* lbias = lds + W16_URING + W16_XSLOTS * W16_XS;      // the 64 channels' bias (behind the rings)
+    float* lbias = lds + G::BIAS;                      // the 64 channels' bias (behind the rings)
     // first = the first k-step of a tile: the accumulators start at 0 (an inline constant: no 128 v_mov per tile), those of
     // point (1,1) at the bias: At e11 A = [[1,1],[1,1]]
     auto mma = [&](const float (&a)[16], const float (&V)[16], int mt, bool first) {
@@ -345,7 +267,7 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
     load_d(lds, 0, dl, dh);
     while (true) {
         int n, oy0, ox0;
-        tile_origin(tile, n, oy0, ox0);
+        walk.origin<2 * BR, 2 * BC>(tile, n, oy0, ox0);
         if constexpr (ADJ) {
             const int gbx = (ox0 >> 1) + bcol0 + t, gby = (oy0 >> 1) + brow, lastx = (p.W >> 1) - 1, lasty = (p.H >> 1) - 1;
             mleft = (f32x2){0.f, gbx == 0 ? 1.f : 0.f};
@@ -353,12 +275,12 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
             mtop = gby == 0 ? 1.f : 0.f;
             mbot = gby == lasty ? 1.f : 0.f;
             rowfold = gby == 0 || gby == lasty;
-            colfold = ox0 == 0 || (ox0 >> 1) + W16_BC > lastx;
+            colfold = ox0 == 0 || (ox0 >> 1) + BC > lastx;
         }
         auto chunk = [&](bool first) {
             const int u1 = u0 == 4 ? 0 : u0 + 1, u2 = u1 == 4 ? 0 : u1 + 1;    // this chunk's second half slab; the next chunk's first
-            const float* xb = lds + rc * W16_XS;
-            load_a(lds + u0 * W16_UHALF + aoff, 1, a1);
+            const float* xb = lds + rc * G::XS;
+            load_a(lds + u0 * G::UHALF + aoff, 1, a1);
             __builtin_amdgcn_sched_barrier(0);
             if ((C2S_W16_DIAG != 7 && !C2S_W16_BARE) || first) transform(dl, dh, V);
             __builtin_amdgcn_sched_barrier(0);
@@ -366,7 +288,7 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
             __builtin_amdgcn_sched_barrier(0);
             mma(a0, V, 0, first);
             __builtin_amdgcn_sched_barrier(0);
-            load_a(lds + u1 * W16_UHALF + aoff, 0, a0);
+            load_a(lds + u1 * G::UHALF + aoff, 0, a0);
             __builtin_amdgcn_sched_barrier(0);
             mma(a1, V, 1, first);
             __builtin_amdgcn_sched_barrier(0);
@@ -375,26 +297,21 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
 #ifdef C2S_W16_STAMP
             const unsigned long long st_t0 = __builtin_amdgcn_s_memtime();
 #endif
-            if (C2S_W16_DIAG != 6 && C2S_W16_DIAG != 12) {
-                if (young_raw) __builtin_amdgcn_s_waitcnt(0x0F70 | W16_MAXE);       // vmcnt(6) / vmcnt(7): the raw pieces of a chunk
-                else __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0)
-                __builtin_amdgcn_s_barrier();
-            }
+            if (C2S_W16_DIAG != 6 && C2S_W16_DIAG != 12) ring_wait_landed<G>(cur.young_raw);
 #ifdef C2S_W16_STAMP
             st_wait += __builtin_amdgcn_s_memtime() - st_t0;
             if (first) st_first += __builtin_amdgcn_s_memtime() - st_t0;
             ++st_chunks;
 #endif
             __builtin_amdgcn_sched_barrier(0);
-            stage_next_u(u0 == 0 ? 4 : u0 - 1);        // chunk after next: half slabs u0 + 4, u0 + 5 = u0 (mod 5)
-            stage_next_raw((rc + 3) & 3);
-            load_a(lds + u1 * W16_UHALF + aoff, 1, a1);
+            request(u0 == 0 ? 4 : u0 - 1, (rc + 3) & 3);       // U of the chunk after next: half slabs u0 + 4, u0 + 5 = u0 (mod 5)
+            load_a(lds + u1 * G::UHALF + aoff, 1, a1);
             __builtin_amdgcn_sched_barrier(0);
             if (C2S_W16_DIAG != 7 && !C2S_W16_BARE) transform(el, eh, V);
             mma(a0, V, 0, false);
             __builtin_amdgcn_sched_barrier(0);
-            load_a(lds + u2 * W16_UHALF + aoff, 0, a0);                  // (after the last chunk of the last tile: stale, unused)
-            load_d(lds + ((rc + 1) & 3) * W16_XS, 0, dl, dh);
+            load_a(lds + u2 * G::UHALF + aoff, 0, a0);                  // (after the last chunk of the last tile: stale, unused)
+            load_d(lds + ((rc + 1) & 3) * G::XS, 0, dl, dh);
             __builtin_amdgcn_sched_barrier(0);
             mma(a1, V, 1, false);
             __builtin_amdgcn_sched_barrier(0);
@@ -423,12 +340,12 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
             for (int q = 0; q < 16; ++q) keepalive += acc[q][0][0] + acc[q][1][0];
             if (keepalive == 12345.678f) p.out[0] = keepalive;
         }
-        if (stile >= ntotal) break;
-        tile = stile;
+        if (cur.stile >= walk.ntotal) break;
+        tile = cur.stile;
         continue;
 #endif
-        const int vo0 = in0 ? (cof * HW + oy * p.W + ox) * 4 : 0x7FFF0000;
-        const int vo1 = in1 ? vo0 + p.W * 4 : 0x7FFF0000;
+        const int vo0 = in0 ? (cof * HW + oy * p.W + ox) * 4 : RING_OOB;
+        const int vo1 = in1 ? vo0 + p.W * 4 : RING_OOB;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
@@ -446,32 +363,14 @@ __global__ __launch_bounds__(512, 1) void conv_winograd16_kernel(Wino16Params p)
                 const f32x2 Y10 = sub2(P0[1], P0[2], P0[3]), Y11 = sub2(P1[1], P1[2], P1[3]);
                 f32x2 y[2][2] = {{(f32x2){Y00[0], Y01[0]}, (f32x2){Y10[0], Y11[0]}},        // [channel of the pair][output row]
                                  {(f32x2){Y00[1], Y01[1]}, (f32x2){Y10[1], Y11[1]}}};
-                const int so = (16 * mt + 2 * h) * HW * 4;
-                if (p.accumulate) {                    // the four reads in flight before the first add
-                    u32x2 o[2][2];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        o[j][0] = __builtin_amdgcn_raw_buffer_load_b64(ro, vo0, so + j * HW * 4, 0);
-                        o[j][1] = __builtin_amdgcn_raw_buffer_load_b64(ro, vo1, so + j * HW * 4, 0);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        y[j][0] += __builtin_bit_cast(f32x2, o[j][0]);
-                        y[j][1] += __builtin_bit_cast(f32x2, o[j][1]);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y[j][0]), ro, vo0, so + j * HW * 4, 0);
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y[j][1]), ro, vo1, so + j * HW * 4, 0);
-                }
+                ring_store_rows(ro, vo0, vo1, (16 * mt + 2 * h) * HW * 4, HW * 4, p.accumulate, y);
             }
         }
 #ifdef C2S_W16_STAMP
         st_epi += __builtin_amdgcn_s_memtime() - st_e0;
 #endif
-        if (stile >= ntotal) break;
-        tile = stile;
+        if (cur.stile >= walk.ntotal) break;
+        tile = cur.stile;
     }
 #ifdef C2S_W16_STAMP
     if (tid == 0 && blockIdx.x < 1024 && blockIdx.y == 0) {
@@ -500,41 +399,34 @@ extern "C" int c2s_debug_w16_stamps(unsigned long long* host_out) {
 extern "C" int c2s_conv3x3_winograd16_supported(const c2s_conv_desc* d) {
     return d && d->KH == 3 && d->KW == 3 && d->S == 1 && d->pad_y == 1 && d->pad_x == 1 && d->Hin % 2 == 0 && d->Win % 2 == 0 &&
            d->Win >= 32 && d->Hin >= 8 && d->CoutP % 64 == 0 && d->C0 + d->C1 > 3 * W16_CK && d->C0 % W16_CK == 0 &&
-           d->C1 % W16_CK == 0 && d->N <= 65536;   // whole chunks only: the chunk's channel base travels in the SGPR offset of the
+           d->C1 % W16_CK == 0 && d->N <= ring_max_frames<W16Shape<4, 16>::G>();
+                                                   // whole chunks only: the chunk's channel base travels in the SGPR offset of the
                                                    // LDS-DMA loads, which takes no part in the buffer range check -- a ragged
                                                    // last chunk would read the next frame (ragged counts: the 4-wave kernel)
 }
 
 extern "C" int c2s_conv3x3_winograd16(const c2s_conv_desc* d, const float* src0, const float* src1, const float* upk,
                                       const float* bias, float* out, const int* valid, void* stream) {
-    C2S_REQUIRE(d && src0 && upk && out, "conv3x3_winograd16: null pointer");
-    C2S_REQUIRE(d->N > 0 && d->N <= 65536, "conv3x3_winograd16: more than 65536 frames in one launch (N = %d)", d->N);   // (the predicate holds the same limit)
+    // tile shape: 4 x 16 blocks = 8 x 32 output pixels (the kernel is a template on it; 2 x 32 blocks = 4 x 64 pixels, with one
+    // 66-float raw row per request instead of two of 34, measured 696 / 755 us against 684 / 742 on the 64 -> 64 @128^2 layer)
+    constexpr int BRh = 4, BCh = 16;
+    using G = W16Shape<BRh, BCh>::G;
+    if (int rc = ring_check("conv3x3_winograd16", d, src0 && upk && out, ring_max_frames<G>(), 1L << 31, true)) return rc;
     C2S_REQUIRE(c2s_conv3x3_winograd16_supported(d), "conv3x3_winograd16: 3x3 stride 1 pad 1, even planes at least 32 wide and 8 high, CoutP %% 64, channels of each source a multiple of 8");
     C2S_REQUIRE(d->C0 > 0 && d->C1 >= 0 && (d->C1 == 0 || src1), "conv3x3_winograd16: bad channels");
-    C2S_REQUIRE(d->Hout == d->Hin && d->Wout == d->Win && d->OutH == d->Hout && d->OutW == d->Wout && d->osy == 1 &&
-                d->osx == 1 && d->ooy == 0 && d->oox == 0, "conv3x3_winograd16: dense same-size output only");
+    C2S_REQUIRE(d->Hout == d->Hin && d->Wout == d->Win, "conv3x3_winograd16: same-size output only");
     C2S_REQUIRE(d->CoutP >= d->Cout && d->Cout > 0, "conv3x3_winograd16: bad CoutP");
-    C2S_REQUIRE((long)(d->C0 > d->C1 ? d->C0 : d->C1) * d->Hin * d->Win * 4 < (1L << 31) &&
-                (long)d->CoutP * d->Hin * d->Win * 4 < 0x7FFF0000L, "conv3x3_winograd16: frame too large");
     if (d->reflect_adjoint) C2S_REQUIRE(d->pad_mode == C2S_PAD_ZEROS, "conv3x3_winograd16: the reflect adjoint is a zero-padded launch");
     Wino16Params p;
     p.src0 = src0; p.src1 = src1; p.upk = upk; p.bias = bias; p.out = out; p.valid = valid;
     p.C0 = d->C0; p.C1 = d->C1; p.H = d->Hin; p.W = d->Win; p.Cout = d->Cout; p.CoutP = d->CoutP;
     p.pad_mode = d->pad_mode; p.accumulate = d->accumulate;
-    // tile shape: 4 x 16 blocks = 8 x 32 output pixels (the kernel is a template on it; 2 x 32 blocks = 4 x 64 pixels, with one
-    // 66-float raw row per request instead of two of 34, measured 696 / 755 us against 684 / 742 on the 64 -> 64 @128^2 layer)
-    constexpr int BRh = 4, BCh = 16;
     p.tiles_x = cdiv(d->Win, 2 * BCh);
     p.tiles = p.tiles_x * cdiv(d->Hin, 2 * BRh);
     p.N = d->N;
     p.nchunks = cdiv(d->C0 + d->C1, W16_CK);
-    const int cus = c2s_cus();                     // (runs the init hooks: dynamic LDS limit)
-    const int cblocks = d->CoutP / 64;
-    const long ntotal = (long)d->N * p.tiles;
-    long gx = ((long)cus + cblocks - 1) / cblocks;  // persistent: one 8-wave workgroup per CU
-    if (gx > ntotal) gx = ntotal;
-    dim3 grid((unsigned)gx, cblocks, 1);
-    const size_t ldsb = (size_t)(W16Shape<BRh, BCh>::LDS_FLOATS + (d->N + 31) / 32) * sizeof(float);
+    const dim3 grid = ring_grid(d->CoutP / 64, (long)d->N * p.tiles, 1);
+    const size_t ldsb = ring_lds_bytes<G>(d->N);
     hipStream_t st = (hipStream_t)stream;
     if (d->reflect_adjoint) hipLaunchKernelGGL((conv_winograd16_kernel<true, BRh, BCh>), grid, dim3(512), ldsb, st, p);
     else hipLaunchKernelGGL((conv_winograd16_kernel<false, BRh, BCh>), grid, dim3(512), ldsb, st, p);

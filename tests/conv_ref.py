@@ -30,12 +30,13 @@ def _conv(x, w, stride, pad, mode, groups, transpose):
     return F.conv2d(x, w, None, stride=stride, padding=pad, groups=groups)
 
 
-def conv_refs(x, w, b, gout, stride, pad, mode, groups=1, transpose=False):
+def conv_refs(x, w, b, gout, stride, pad, mode, groups=1, transpose=False, weight_grad=True):
     """float64 forward output, data gradient and weight gradient of the convolution at (x, w, b, gout), and their bounds
-    A (same map on absolute values).  All tensors on the CPU, real frames only."""
+    A (same map on absolute values).  All tensors on the CPU, real frames only.  weight_grad=False leaves "gw" / "Agw" None
+    (a third of the work, for callers that check the forward and the data gradient of many frames)."""
     def run(xs, ws, bs, gs):
         xs = xs.detach().double().requires_grad_(True)
-        ws = ws.detach().double().requires_grad_(True)
+        ws = ws.detach().double().requires_grad_(weight_grad)
         y = _conv(xs, ws, stride, pad, mode, groups, transpose)
         if bs is not None:
             y = y + bs.detach().double().view(1, -1, 1, 1)

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import conv_trace as T
+import test_conv_walk_gpu as W
 from crop2seg_amd import _lib
 from crop2seg_amd import engine as E
 from test_conv_modes_gpu import PERSISTENT, TABLES, persistent_frames
@@ -71,6 +72,21 @@ def test_the_persistent_row_outruns_the_grid():
     assert (N, tiles) == (160, 640) and tiles > 2 * 256
     assert padded == [1, 3, 4, 5, 6, 10, 136, 137, 138, 159]
     assert _plan("fwd", N, row.chans, row.Cout, row.H, row.W, row.K, row.S, row.mode).family == "smallcin"
+
+
+def test_the_walk_rows_outrun_the_grid():
+    """The rows of test_conv_walk_gpu on 256 compute units: planned on the families of the table, and every workgroup of a ring
+    launch's first grid pass reaches a third tile across every padded / real pattern (walk_frames asserts both)."""
+    frames = {}
+    for row in W.ROWS:
+        N, padded = W.walk_frames(row, 256)
+        frames[row.id] = (N, len(padded))
+        args = (N, row.chans, row.Cout, row.H, row.W, row.K, row.S, row.mode)
+        for acc in row.acc:
+            assert (_plan("fwd", *args).family, _plan("dgrad", *args, accumulate=acc).family) == (row.fwd, row.dgrad[0])
+    assert frames == {"wino16-walk": (208, 10), "wino16-walk-zeros": (208, 10), "wino16-walk-dgrad": (208, 10),
+                      "wino16-walk-dgrad-zeros": (208, 10), "s2-walk": (416, 19), "s2-walk-k5": (416, 19)}
+    assert W.ring_passes(W.ROWS[4], 256)[0] == [128, 32]       # s2wino: two tiles per frame; s2dgrad: four, and grid y = 2
 
 
 def test_frame_count_bounds():
